@@ -33,12 +33,6 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-# Steps in flight need their streams on different hardware queues.  The runtime folds a process's streams onto GPU_MAX_HW_QUEUES of
-# them (4 by default), in the order they are made; with four, the stream of the position-hinted pass and the stream of the queues
-# behind it now and then share one (the library's scratch makes side streams of its own as calls overlap), and the schedule runs at
-# the one-at-a-time rate (with 2 queues always: 1.18 against 0.79 ms per step).  Eight leave room.  (A host application sets the
-# same variable before it initialises HIP; an explicit setting of the caller's wins.)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ALGO_BYTES_PER_READ = 3296  # B(L) = 86 + 796*n_k + (L - 31*n_k) at L=150, n_k=4
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 EXCHANGE_STREAM = os.environ.get("GTX_BENCH_EXCHANGE_STREAM", "1") != "0"  # N > 1, staggered schedule: the exchange and the calls on a stream of their own
@@ -96,6 +90,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launch logic only (ranks, process group, one packed all-reduce, max-over-ranks timing): no GPU work, "
                          "the line carries value null; used by the CPU test of the N>1 launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (calls, PL, accumulators; rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -307,6 +303,7 @@ class Workload:
         self.sets = []   # resident read sets (bases, meta, score items); step k works on set k mod len(sets)
         self.words = {}  # items' data_ptr -> their compact form (gtx_score_batch_words), or None
         self.steps_done = 0
+        self.last_lane = None  # the lane of the step queued last: its records and accumulators hold that step's results
         self.add_reads(d_seq, d_pos)
         self.align_fn = self.L.gtx_align_batch_planes if PLANE_INPUT else self.L.gtx_align_batch_flags
         self.d_rec = torch.zeros(n * 2 * REC_WORDS, dtype=torch.int32, device=device)
@@ -444,7 +441,7 @@ class Workload:
         """one step on `lane`; zero=False: the accumulators keep what they hold (several read sets into one block)"""
         gtx, L, ctx = self.gtx, self.L, self.ctx
         torch = self.torch
-        ln = self.lanes[lane]
+        ln = self.last_lane = self.lanes[lane]
         stream, sp, buf, d_rec, d_flags = ln["stream"], ln["sp"], ln["buf"], ln["d_rec"], ln["d_flags"]
         d_seq, d_meta, d_items = self.sets[self.steps_done % len(self.sets)]
         self.steps_done += 1
@@ -567,7 +564,7 @@ class Workload:
         if score_on == "S" and not hasattr(self, "score_stream"):
             self.score_stream = torch.cuda.Stream(device=self.device)
         for _ in range(steps):
-            ln = self.lanes[self.steps_done % n_l]
+            ln = self.last_lane = self.lanes[self.steps_done % n_l]
             if pace:
                 # The host stays at most n_l steps ahead of the device: the lane's last scoring is through before its next step is
                 # queued.  Unpaced, the host queues ten steps in a millisecond, every call finds all earlier ones still in flight
@@ -817,6 +814,23 @@ class Workload:
         raw = self.gtx.download(self.lanes[lane]["buf"].d_stat_u64, np.uint8, self.reduced_bytes)
         return hashlib.sha256(raw.tobytes()).hexdigest()
 
+    def last_step_outputs(self):
+        """what the step queued last handed its caller, on the host: the SampleCalls and PL of gtx_calls_batch and the accumulator
+        block they were called from (N > 1: summed over the ranks)"""
+        gtx, ctx = self.gtx, self.ctx
+        self.torch.cuda.synchronize()
+        ln, buf = self.last_lane, self.last_lane["buf"]
+        ns, nh, ta, tt = self.n_samples, ctx.n_hap, ctx.total_allele, ctx.total_tri
+        calls = ln["d_calls"].cpu().numpy().view(gtx.SAMPLE_CALL)[:ns * nh]
+        out = {"calls_" + f: calls[f] for f in gtx.SAMPLE_CALL.names if f != "reserved"}
+        out["phred"] = ln["d_phred"].cpu().numpy()[:ns * tt]
+        out["log_score"] = gtx.download(buf.d_log_score, np.uint32, ns * tt)
+        out["gt_cov"] = gtx.download(buf.d_gt_cov, np.uint32, ns * ta)
+        out["hap_u32"] = gtx.download(buf.d_hap_u32, np.uint32, ns * nh * 4)
+        out["stat_u64"] = gtx.download(buf.d_stat_u64, np.uint64, nh + 2 * ta)
+        out["stat_u32"] = gtx.download(buf.d_stat_u32, np.uint32, nh + 6 * ta)
+        return out
+
     def result_facts(self):
         """sanity on the results of the last step: every record must be a result, not an overflow"""
         gtx, ctx = self.gtx, self.ctx
@@ -862,6 +876,25 @@ def pinned_digest(checksum, n_reads, args):
         return {"matches_pinned": None, "pinned": "tests/golden/cfg2_vcf_digest.json is for the default workload (this run's differs)"}
     return {"matches_pinned": checksum["vcf_sha256"] == pin["vcf_sha256"] and checksum["vcf_bytes"] == pin["vcf_bytes"],
             "pinned": "tests/golden/cfg2_vcf_digest.json"}
+
+
+DUMP_ARRAY_BYTES = 4 << 20  # per array: the 13 arrays of Workload.last_step_outputs stay under 64 MB together
+
+
+def dump_outputs(path, arrays):
+    """arrays -> path/<name>.npy: 8- and 16-bit integers as float32, wider ones as float64 (both exact).  An array over
+    DUMP_ARRAY_BYTES is cut to a seeded sample of its elements (the same ones in every run of the same shape), in order."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        cap = DUMP_ARRAY_BYTES // a.itemsize
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, total
 
 
 def cpu_model():
@@ -1749,6 +1782,8 @@ def main(argv=None):
         w.setup_reduce(dist, rank, world, local_rank)
     w.staggered = args.schedule == "staggered" and len(w.lanes) >= 2
     dt, align_ms = w.run(args.steps, args.warmup, dist)
+    if args.dump_outputs and rank == 0:  # (before anything below queues another step on a lane)
+        dump_outputs(args.dump_outputs, w.last_step_outputs())
     pass_ms, n_pass2 = ctx.pass_times()  # last step: express / general / HBM-table kernels
     kern = ctx.kernel_times() if hasattr(ctx, "kernel_times") else None
     step_alone_ms = None

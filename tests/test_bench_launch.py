@@ -79,3 +79,24 @@ def test_the_line_of_stdout_fits_the_drivers_tail():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert line["cpu_baseline"][k] == out["cpu_baseline"][k]
     assert set(line["config"]["extra"]) == set(out["config"]["extra"])
+
+
+def test_dump_outputs_writes_exact_floats_under_the_cap(tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (8- / 16-bit integers) or float64 (wider ones), values exact;
+    an array over the per-array cap becomes the same seeded sample of its elements, in order, in every run"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    big = np.arange(3 * bench.DUMP_ARRAY_BYTES // 8, dtype=np.uint64) * 3
+    arrays = {"gq": np.array([0, 99, 255], np.uint8), "depth": np.array([1, 65535], np.uint16),
+              "cov": np.array([0, 2 ** 32 - 1], np.uint32), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    for name, a in arrays.items():
+        x = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert x.dtype == (np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        assert np.array_equal(x, np.load(str(tmp_path / "b" / (name + ".npy"))))
+        if name != "big":
+            assert np.array_equal(x, a.astype(x.dtype)) and x.astype(a.dtype).tolist() == a.tolist()
+    x = np.load(str(tmp_path / "a" / "big.npy"))
+    assert x.nbytes == bench.DUMP_ARRAY_BYTES and (np.diff(x) > 0).all() and np.isin(x, big).all()
