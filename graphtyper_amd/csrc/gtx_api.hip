@@ -1503,15 +1503,9 @@ static void scratch_free(CallScratch & s)
     if (p)
       (void)gtx::dev_free(p);
   for (auto & slot : s.time_ring)
-    for (auto & row : slot)
-      for (auto & e : row)
-        if (e)
-          (void)hipEventDestroy(static_cast<hipEvent_t>(e));
-  for (auto & e : s.sync_events)
-    if (e)
-      (void)hipEventDestroy(static_cast<hipEvent_t>(e));
-  if (s.side_stream)
-    (void)hipStreamDestroy(static_cast<hipStream_t>(s.side_stream));
+    for (auto & e : slot)
+      if (e)
+        (void)hipEventDestroy(static_cast<hipEvent_t>(e));
   if (s.done)
     (void)hipEventDestroy(static_cast<hipEvent_t>(s.done));
   if (s.h_span)
@@ -1524,8 +1518,8 @@ static void counter_set_select(CallScratch & s, uint32_t k)
 {
   s.counter_set = k;
   s.d_counters = s.d_counter_sets + static_cast<size_t>(k) * CallScratch::COUNTER_PITCH;
-  s.d_span = reinterpret_cast<unsigned long long *>(s.d_counters + 8 * CallScratch::MAX_PARTS + 48); // (its pinned home is made by the first timed call)
-  s.d_big_state = s.has_big ? s.d_counters + 8 * CallScratch::MAX_PARTS : nullptr;
+  s.d_span = reinterpret_cast<unsigned long long *>(s.d_counters + 8 + 48); // (its pinned home is made by the first timed call)
+  s.d_big_state = s.has_big ? s.d_counters + 8 : nullptr;
   s.d_wide_state = s.has_wide ? s.d_big_state + 8 : nullptr;
   s.d_exact_state = s.has_big ? s.d_big_state + 16 : nullptr;
 }
@@ -1537,7 +1531,7 @@ static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
   bool ok = hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "scratch event");
   if (ok)
     s->done = ev;
-  static_assert(CallScratch::COUNTER_WORDS == 8 * CallScratch::MAX_PARTS + 48 + 4 && CallScratch::COUNTER_WORDS <= CallScratch::COUNTER_PITCH, "counter sets");
+  static_assert(CallScratch::COUNTER_WORDS == 8 + 48 + 4 && CallScratch::COUNTER_WORDS <= CallScratch::COUNTER_PITCH, "counter sets");
   ok = ok && dev_alloc(s->d_counter_sets, 2 * CallScratch::COUNTER_PITCH, "task counters + second-pass state", true); // (two sets: gtx_ctx.hpp)
   s->has_big = !c.params.no_second_pass;
   s->has_wide = s->has_big && c.has_wide_sites;
@@ -1996,12 +1990,6 @@ struct ScratchHold
 };
 } // namespace
 
-extern "C" int gtx_align_batch(gtx_ctx * c, const uint8_t * d_seq, uint32_t seq_stride, const gtx_read_meta * d_meta,
-                               uint32_t n_reads, uint32_t * d_records, uint32_t rec_words, void * stream)
-{
-  return gtx_align_batch_flags(c, d_seq, seq_stride, d_meta, n_reads, d_records, rec_words, nullptr, stream);
-}
-
 static int launch_planes_kernel(const uint8_t * d_seq, uint32_t seq_stride, uint32_t n_reads, uint8_t * d_planes, uint32_t plane_stride,
                                 hipStream_t st)
 {
@@ -2098,10 +2086,458 @@ struct TriageRequest
   uint32_t * d_work; // [0] = count, [GTX_WORK_HEADER_WORDS ...] = the items with work
   bool items_are_reads; // GTX_TRIAGE_ITEMS_ARE_READS: item i is read i, alone and aligned forward only
 };
-static int align_planes(gtx_ctx * c, CallScratch * s, const uint8_t * d_seq, uint32_t seq_stride, const gtx_read_meta * d_meta, uint32_t n_reads,
-                        uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, hipStream_t st, hipEvent_t front_event = nullptr,
-                        hipStream_t tail_stream = nullptr, hipEvent_t done_event = nullptr, hipStream_t * last_stream = nullptr,
-                        uint32_t * d_compact = nullptr, TriageRequest const * triage = nullptr);
+
+// One align call as the six align entry points hand it on, after their argument checks (align_call)
+struct AlignRequest
+{
+  uint8_t const * seq; // plane rows -- or, with `nibbles`, BAM nibble rows (seq_stride: their pitch)
+  uint32_t seq_stride;
+  gtx_read_meta const * meta;
+  uint32_t n_reads;
+  uint32_t * records;
+  uint32_t rec_words;
+  uint8_t * task_flags;
+  hipStream_t stream;
+  hipEvent_t front_event = nullptr;
+  hipStream_t tail_stream = nullptr;
+  hipEvent_t done_event = nullptr;
+  uint32_t * compact = nullptr;
+  TriageRequest const * triage = nullptr;
+  bool nibbles = false; // gtx_align_batch[_flags]: repacked into plane rows in the call's scratch first
+};
+
+// What the steps of one align call share; they run in launch order: align_setup, align_front, align_hbm, align_side_bytes,
+// align_end
+struct AlignCall
+{
+  gtx_ctx * c;
+  CallScratch * s;
+  AlignRequest const & r;
+  // The stream of the short queues: the caller's until the front event, then the tail stream when one is given.  From then on
+  // the tail stream holds launches that use the scratch, so the call ends there -- after an error as well: the scratch is handed
+  // back on THAT stream, else the next call on the caller's stream would reset counters and queues the tail stream may still read.
+  hipStream_t sq;
+  bool timed = false;
+  uint32_t slot = 0;     // the call's slot of CallScratch::time_ring
+  bool hinted = false;   // the position-hinted pass ran (its queue and the general pass' queue hold what it did not settle)
+  unsigned long long * var_masks = nullptr; // gtx_align_batch_planes_triaged where item i is read i: a bit per read
+  void mark(int k, hipStream_t on) const
+  {
+    if (timed)
+      (void)hipEventRecord(static_cast<hipEvent_t>(s->time_ring[slot][k]), on);
+  }
+};
+
+// set-up: the counter set, the queues, the timing slot
+static int align_setup(AlignCall & a)
+{
+  gtx_ctx * const c = a.c;
+  CallScratch * const s = a.s;
+  uint32_t const n_reads = a.r.n_reads;
+  // (the pass counters and, behind them, the state of the HBM-table and wide-site passes: the set the last call left zeroed --
+  //  CallScratch::d_counter_sets; after a call that failed on its way the set is zeroed here, as every call did before round 6)
+  uint32_t const use = s->counter_set ^ 1u;
+  if (!s->spare_set_clean &&
+      !hip_ok(hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(use) * CallScratch::COUNTER_PITCH, 0, CallScratch::COUNTER_PITCH * sizeof(uint32_t), a.r.stream), "task counter reset"))
+    return GTX_ERR_HIP;
+  counter_set_select(*s, use);
+  s->spare_set_clean = false;
+  // queues: room for every task (a graph on which no read is simple sends them all)
+  if (!grow(s->d_queue, s->queue_cap, 2ull * n_reads, "pass-2 queue") || !grow(s->d_queue1, s->queue1_cap, n_reads, "pass-1 queue"))
+    return GTX_ERR_HIP;
+  if (s->d_big_state)
+  {
+    // the queue holds every task of a small batch and 8 Mi tasks of a large one (tasks beyond it keep their status bit)
+    uint64_t const want = std::min<uint64_t>(2ull * n_reads, 8ull << 20);
+    uint64_t cap = s->big_task_cap;
+    if (!grow(s->d_big_tasks, cap, want, "second-pass queue"))
+      return GTX_ERR_HIP;
+    s->big_task_cap = static_cast<uint32_t>(cap);
+  }
+  uint32_t epoch = 0;
+  {
+    std::lock_guard<std::mutex> lock(c->pool_mutex);
+    a.timed = c->timing_armed;
+    if (a.timed && c->epoch_queried) // the first timed call behind a query: a new epoch
+    {
+      ++c->time_epoch;
+      c->epoch_queried = false;
+    }
+    epoch = c->time_epoch;
+    // (GTX_TIME_EVERY=n: one call in n is timed -- a timed call brackets its launches with events, packets the streams carry
+    //  between the kernels; the means of gtx_ctx_kernel_times are over the timed calls)
+    static uint32_t const every = [] { char const * e = std::getenv("GTX_TIME_EVERY"); int const v = e ? std::atoi(e) : 1; return static_cast<uint32_t>(v > 0 ? v : 1); }();
+    if (a.timed && every > 1 && (c->timed_seq++ % every) != 0)
+      a.timed = false;
+  }
+  if (a.timed && s->ring_epoch != epoch)
+  {
+    s->ring_epoch = epoch;
+    s->ring_used = 0;
+  }
+  // (calls beyond the ring are not timed: a query empties it)
+  if (a.timed && s->ring_used >= CallScratch::TIME_RING)
+    a.timed = false;
+  a.slot = a.timed ? s->ring_used : 0u;
+  if (a.timed && !s->h_span) // (pinned: only a host that asks for kernel times pays for it; without it pass 0's time is the interval between its events)
+  {
+    if (hipHostMalloc(reinterpret_cast<void **>(&s->h_span), CallScratch::TIME_RING * 2 * sizeof(unsigned long long)) != hipSuccess)
+      s->h_span = nullptr;
+  }
+  if (a.timed && s->h_span)
+    s->h_span[2 * a.slot] = s->h_span[2 * a.slot + 1] = 0ull;
+  if (a.timed && !s->time_ring[a.slot][0])
+    for (auto & e : s->time_ring[a.slot])
+    {
+      hipEvent_t ev;
+      if (!hip_ok(hipEventCreate(&ev), "pass events"))
+        return GTX_ERR_HIP;
+      e = ev;
+    }
+  // (gtx_align_batch_planes_triaged where item i is read i: a bit per read, written by the position-hinted pass, completed behind
+  //  the last pass)
+  if (a.r.triage && a.r.triage->items_are_reads)
+  {
+    if (!grow(s->d_var_masks, s->var_mask_cap, (static_cast<uint64_t>(n_reads) + 63u) / 64u, "variant-site bits of the reads"))
+      return GTX_ERR_HIP;
+    a.var_masks = s->d_var_masks;
+  }
+  return GTX_OK;
+}
+
+// the front passes: the position-hinted pass (pass 0) on the caller's stream, then the front event, then the express and general
+// passes on the stream of the short queues
+static int align_front(AlignCall & a)
+{
+  gtx_ctx * const c = a.c;
+  CallScratch * const s = a.s;
+  AlignRequest const & r = a.r;
+  uint32_t const n = r.n_reads;
+  uint32_t * const counters = s->d_counters;
+  // test switch: 1 = every task goes through all passes (the last one decides), 2 = every task is done by pass 2
+  char const * fb = std::getenv("GTX_FORCE_SECOND_PASS");
+  uint32_t const force = fb ? static_cast<uint32_t>(std::atoi(fb)) : 0u;
+  uint32_t const n_cu = static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256);
+  uint32_t const force_both = static_cast<uint32_t>(c->params.force_align_both_orientations != 0);
+  char const * e4 = std::getenv("GTX_EXPRESS4"); // A/B switch: 0 = one read per wavefront in pass 1
+  char const * eh = std::getenv("GTX_HINT");     // A/B switch: 0 = no position-hinted pass
+  bool const four = !(e4 && e4[0] == '0');
+  a.hinted = four && !(eh && eh[0] == '0');
+  // GTX_EXPRESS4=lean / wide force a build (tests); else by the graph's density
+  bool const wide = e4 && e4[0] == 'w' ? true : e4 && e4[0] == 'l' ? false : c->express4_wide;
+  // grids: as many single-wave workgroups as are resident at once; they pull work from shared counters
+  uint64_t const chunks = (static_cast<uint64_t>(n) + TASK_CHUNK - 1) / TASK_CHUNK;
+  uint32_t const express4_per_cu = static_cast<uint32_t>(wide ? c->express4_wide_blocks_per_cu : c->express4_blocks_per_cu);
+  a.mark(0, r.stream);
+  if (a.hinted)
+  {
+    // pass 0: one read per lane from the position hint; what it declines is queued for pass 1.  (GTX_HINT=decline: the
+    // pass runs but declines everything -- a test of the queue plumbing)
+    bool const sv_skips_express = c->params.is_sv_graph != 0 && force == 0;
+    char const * hb = std::getenv("GTX_HINT_BUILD"); // (test switch: lean | dense build of pass 0; default: dense beside the wide express pass)
+    bool const hint_dense = hb && hb[0] == 'd' ? true : hb && hb[0] == 'l' ? false : c->express4_wide;
+    bool const hint_long = r.seq_stride > HintGeom<AlignCfg::KC>::ROW_BYTES; // (rows for reads of more than 160 bases: the eight-k-mer build)
+    uint32_t const hint_threads = 64u * ((hint_long || hint_dense) ? GTX_HINT_WAVES : GTX_HINT_WAVES_LEAN);
+    hipLaunchKernelGGL(hint_long ? gtx_align_hinted_long_kernel : hint_dense ? gtx_align_hinted_dense_kernel : gtx_align_hinted_kernel,
+                       dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, r.stream, c->dev_graph, c->dev_index, r.seq, r.seq_stride,
+                       r.meta, n, r.records, r.rec_words, force_both, s->d_queue1, s->d_queue, reinterpret_cast<unsigned long long *>(counters + 2),
+                       static_cast<uint32_t>(force != 0 || (eh && eh[0] == 'd')) | (sv_skips_express ? 4u : 0u)
+#ifdef GTX_PROF
+                         | (eh && eh[0] == 'x' ? 2u : 0u)
+#endif
+                         ,
+                       r.task_flags, r.compact, a.timed && s->h_span ? s->d_span : static_cast<unsigned long long *>(nullptr), a.var_masks);
+    if (!hip_ok(hipGetLastError(), "gtx_align_hinted_kernel launch"))
+      return GTX_ERR_HIP;
+  }
+  a.mark(1, r.stream);
+  // (gtx_align_batch_planes_staged: from here on the call is short queues -- the caller's other streams may come in.  Without a
+  //  position-hinted pass the event marks the call's start.)
+  if (r.front_event)
+  {
+    (void)hipEventRecord(r.front_event, r.stream);
+    if (r.tail_stream && r.tail_stream != r.stream)
+    {
+      (void)hipStreamWaitEvent(r.tail_stream, r.front_event, 0);
+      a.sq = r.tail_stream;
+    }
+  }
+  if (a.hinted)
+  {
+    // (the queue's length is known on the device only: the grid is what can be resident, or one wavefront per group of four
+    //  reads of a small batch; the kernel sizes its claims to the queue)
+    uint32_t const blocks4q = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(n) + 3u) / 4u, static_cast<uint64_t>(n_cu) * express4_per_cu));
+    hipLaunchKernelGGL(wide ? gtx_align_express4q_wide_kernel : gtx_align_express4q_kernel, dim3(blocks4q), dim3(64), 0, a.sq, c->dev_graph,
+                       c->dev_index, r.seq, r.seq_stride, r.meta, r.records, r.rec_words, counters, s->d_queue1, counters + 3, s->d_queue, counters + 2,
+                       counters + 4, static_cast<uint32_t>(force != 0));
+    // (the call's launch of the position-hinted pass has added to the span: home with it -- on the stream of the short queues,
+    //  behind the express launch: on the caller's stream the copy sat between the pass and whatever the caller queues behind it)
+    if (a.timed && s->h_span)
+      (void)hipMemcpyAsync(s->h_span + 2 * a.slot, s->d_span, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, a.sq);
+  }
+  else if (four)
+    hipLaunchKernelGGL(wide ? gtx_align_express4_wide_kernel : gtx_align_express4_kernel,
+                       dim3(static_cast<uint32_t>(std::min<uint64_t>(chunks, static_cast<uint64_t>(n_cu) * express4_per_cu))), dim3(64), 0, a.sq,
+                       c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, n, r.records, r.rec_words, force_both, counters, s->d_queue,
+                       counters + 2, static_cast<uint32_t>(force != 0));
+  else
+    hipLaunchKernelGGL(gtx_align_express_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>(chunks, static_cast<uint64_t>(n_cu) * c->express_blocks_per_cu))),
+                       dim3(64), 0, a.sq, c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, n, r.records, r.rec_words, force_both, counters,
+                       s->d_queue, counters + 2, static_cast<uint32_t>(force != 0));
+  if (!hip_ok(hipGetLastError(), "express kernel launch"))
+    return GTX_ERR_HIP;
+  a.mark(2, a.sq);
+  // (a long queue -- the cfg3 graph: 48 k tasks -- is not done faster by more than 12 wavefronts per CU: 4 / 8 / 12 / 20 per CU =
+  //  1.51 / 0.91 / 0.70 / 0.76 ms, the longest task 0.5 M cycles with 4 per CU and 3.4 M with 20; what they queue for is per CU)
+  uint32_t const general_per_cu = std::min<uint32_t>(static_cast<uint32_t>(c->align_blocks_per_cu), 12u);
+  uint32_t const blocks2 = static_cast<uint32_t>(std::min<uint64_t>(2ull * n, static_cast<uint64_t>(n_cu) * general_per_cu));
+  a.mark(3, a.sq);
+  // (task base 0 and claim 0: the kernel sizes its claims to its queue)
+  hipLaunchKernelGGL(gtx_align_kernel, dim3(blocks2), dim3(64), 0, a.sq, c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, r.records,
+                     r.rec_words, s->d_queue, counters + 2, counters + 1, s->d_big_state ? s->d_big_tasks : nullptr, s->big_task_cap, s->d_big_state,
+                     static_cast<uint32_t>(force == 1), 0u, 0u, counters + 5);
+  if (!hip_ok(hipGetLastError(), "gtx_align_kernel launch"))
+    return GTX_ERR_HIP;
+  a.mark(4, a.sq);
+  return GTX_OK;
+}
+
+// the passes behind the general one: the HBM-table pass (and the wide-site pass), then the exact pass with one of the
+// context's slabs
+static int align_hbm(AlignCall & a)
+{
+#ifdef GTX_EXPERIMENT
+  // (experiment builds only -- never the product: what a step would take if the passes that find empty queues cost nothing)
+  static bool const skip_hbm_passes = std::getenv("GTX_SKIP_HBM_PASSES") != nullptr;
+#else
+  constexpr bool skip_hbm_passes = false;
+#endif
+  gtx_ctx * const c = a.c;
+  CallScratch * const s = a.s;
+  AlignRequest const & r = a.r;
+  if (!s->d_big_state || skip_hbm_passes)
+    return GTX_OK;
+  // (GTX_BIG_GRID_ADAPTIVE=0, A/B switch: both passes are launched whole, not sized by what the batch before sent them)
+  static bool const adaptive = !(std::getenv("GTX_BIG_GRID_ADAPTIVE") && std::getenv("GTX_BIG_GRID_ADAPTIVE")[0] == '0');
+  HbmPassArgs h;
+  h.g = c->dev_graph;
+  h.ix = c->dev_index;
+  h.seq = r.seq;
+  h.seq_stride = r.seq_stride;
+  h.meta = r.meta;
+  h.records = r.records;
+  h.rec_words = r.rec_words;
+  h.big_tasks = s->d_big_tasks;
+  h.big_task_cap = s->big_task_cap;
+  h.big_state = s->d_big_state;
+  // (a large batch: the HBM-table pass with all its workgroups -- the workspaces grow once, the scratch is this call's)
+  if (r.n_reads >= gtx_ctx::HBM_SMALL_BATCH && s->big_blocks < c->big_blocks)
+  {
+    void * ws = nullptr;
+    if (!hip_ok(gtx::dev_malloc(&ws, static_cast<size_t>(c->big_blocks) * big_workspace_bytes()), "second-pass workspaces"))
+      return GTX_ERR_HIP;
+    // (the scratch came back to this stream in stream order only -- scratch_acquire does not wait for the host: an earlier,
+    //  small call's HBM-table pass may still be running on the old block, and a block goes back to the cache only when no
+    //  kernel can still use it, gtx_devmem.hpp: another context's thread could be handed it for another stream.  Once per
+    //  scratch, at its first large batch.)
+    if (s->d_big_ws && s->used && s->done)
+      (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
+    (void)gtx::dev_free(s->d_big_ws);
+    s->d_big_ws = ws;
+    s->big_blocks = c->big_blocks;
+  }
+  h.big_blocks = r.n_reads >= gtx_ctx::HBM_SMALL_BATCH ? s->big_blocks : std::min<uint32_t>(s->big_blocks, static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256));
+  if (c->h_big_seen)
+  {
+    // (tasks are claimed one by one from the queue: any number of workgroups does them all -- fewer only take longer when the
+    //  guess is too low, and the next call knows better)
+    uint32_t const seen = *static_cast<uint32_t volatile *>(c->h_big_seen);
+    if (adaptive && seen != 0xFFFFFFFFu)
+      h.big_blocks = static_cast<uint32_t>(std::min<uint64_t>(h.big_blocks, 2ull * seen + 32u));
+  }
+  h.big_ws = s->d_big_ws;
+  h.wide_tasks = s->d_wide_tasks;
+  h.wide_state = s->d_wide_state;
+  h.wide_ws = s->d_wide_ws;
+  h.exact_tasks = s->d_exact_tasks;
+  h.exact_state = s->d_exact_state;
+  h.exact_slab = nullptr;
+  h.exact_slab_bytes = c->exact_slab_bytes;
+  h.exact_cand_cap = c->exact_cand_cap;
+  h.exact_part_cand_cap = std::min<uint32_t>(c->exact_cand_cap, CallScratch::EXACT_PART_CANDIDATES);
+  h.exact_parts = c->exact_parts;
+  h.exact_fixed_parts = c->exact_fixed_parts;
+  h.wide_sites = c->has_wide_sites;
+  h.arena = c->d_big_records;
+  h.arena_words = c->big_record_words;
+  h.arena_cursor = c->d_arena_cursor;
+  char const * what = launch_hbm_passes(h, a.sq);
+
+  if (!what)
+  {
+    // the exact launches, with one of the context's slabs: chosen, waited for if need be, used and marked busy again in one
+    // critical section (the next call's wait has to see this call's record)
+    std::lock_guard<std::mutex> lock(c->exact_mutex);
+    bool wait = false;
+    gtx_ctx::ExactSlot const * slot = exact_slot_for_call(*c, exact_slab_for(*c, r.n_reads), &wait);
+    if (!slot)
+      return GTX_ERR_HIP;
+    if (wait)
+      (void)hipStreamWaitEvent(a.sq, static_cast<hipEvent_t>(slot->idle), 0);
+    h.exact_slab = slot->slab;
+    h.exact_slab_bytes = slot->bytes;
+    if (!c->exact_fixed_parts) // (as many parts as the slab has room for: none smaller than 2 MB, 32 MB where allele sets are wide)
+      h.exact_parts = static_cast<uint32_t>(std::min<uint64_t>(c->exact_parts, std::max<uint64_t>(1u, (slot->bytes >> 20) / (c->has_wide_sites ? 32u : 2u))));
+    // (the launches' grids by what the batch before sent this way -- tasks are claimed one by one, any number of workgroups does
+    //  them all: a workgroup of the pass wants 32 KB of LDS, and beside the position-hinted pass of the next batch a thousand of them
+    //  waited for that pass' end to find an empty queue -- 150-200 us on the stream of the short queues, the scoring behind them)
+    uint32_t const seen_exact = c->h_big_seen ? static_cast<uint32_t volatile *>(c->h_big_seen)[2] : 0xFFFFFFFFu;
+    h.exact_grid_limit = (!adaptive || c->exact_fixed_parts || seen_exact == 0xFFFFFFFFu) ? 0u : 2u * seen_exact + 4u;
+    what = launch_exact_passes(h, a.sq);
+    if (!what && c->h_big_seen)
+      hipLaunchKernelGGL(gtx_seen_kernel, dim3(1), dim3(64), 0, a.sq, c->h_big_seen, s->d_big_state, s->d_exact_state);
+    (void)hipEventRecord(static_cast<hipEvent_t>(slot->idle), a.sq);
+  }
+  if (what)
+  {
+    (void)hip_ok(hipErrorLaunchFailure, what);
+    return GTX_ERR_HIP;
+  }
+  return GTX_OK;
+}
+
+// the side bytes and the scorer's first stage
+static int align_side_bytes(AlignCall & a)
+{
+  gtx_ctx * const c = a.c;
+  CallScratch * const s = a.s;
+  AlignRequest const & r = a.r;
+  uint32_t const n = r.n_reads;
+  uint32_t const * counters = s->d_counters;
+  if (r.task_flags)
+  {
+    // the dense side array for what the position-hinted pass did not settle (its queue and the general pass' queue), or --
+    // without that pass -- for every task
+    if (a.hinted)
+      // (one-wave workgroups: behind the short queues this launch stands beside the position-hinted pass of the NEXT batch, whose
+      //  workgroups of two wavefronts take every pair of slots a retiring one frees -- a workgroup of four wavefronts waited for that
+      //  pass' end, 130-180 us in the trace of the staggered schedule, and the scoring of this batch with it)
+      hipLaunchKernelGGL(gtx_task_flags_fixup_kernel, dim3(static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256) * 16u), dim3(64), 0, a.sq, r.records,
+                         r.rec_words, r.task_flags, s->d_queue1, counters + 3, s->d_queue, counters + 2, a.var_masks);
+    else
+    {
+      hipLaunchKernelGGL(gtx_task_flags_all_kernel, dim3((2u * n + 255u) / 256u), dim3(256), 0, a.sq, r.records, r.rec_words, r.task_flags, 2u * n);
+      if (a.var_masks)
+        hipLaunchKernelGGL(gtx_var_masks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, a.sq, r.task_flags, n, a.var_masks);
+    }
+    if (!hip_ok(hipGetLastError(), "task flags launch"))
+      return GTX_ERR_HIP;
+  }
+  if (TriageRequest const * t = r.triage)
+  {
+    // The scorer's first stage (which items' reads carry a variant site: the side array, complete behind the launch above, and
+    // the items' words) HERE, behind the short queues on their stream, instead of in front of the scoring on the stream that
+    // carries the position-hinted passes: 37 us of a 650 us step there, nothing here -- the queues' stream is idle half of the time.
+    if (!hip_ok(hipMemsetAsync(t->d_work, 0, GTX_WORK_HEADER_WORDS * sizeof(uint32_t), a.sq), "work queue reset"))
+      return GTX_ERR_HIP;
+    if (a.var_masks)
+    {
+      uint32_t const n_words = (n + 63u) / 64u;
+      hipLaunchKernelGGL(gtx_mask_triage_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, a.sq, a.var_masks, n_words, t->d_work + GTX_WORK_HEADER_WORDS,
+                         t->d_work);
+      if (!hip_ok(hipGetLastError(), "gtx_mask_triage_kernel launch"))
+        return GTX_ERR_HIP;
+    }
+    else if (t->n_items)
+    {
+      hipLaunchKernelGGL(gtx_score_triage_kernel, dim3((t->n_items + TRIAGE_THREADS * TRIAGE_PER_THREAD - 1) / (TRIAGE_THREADS * TRIAGE_PER_THREAD)),
+                         dim3(TRIAGE_THREADS), 0, a.sq, t->d_items, t->n_items, r.records, r.rec_words, t->d_work + GTX_WORK_HEADER_WORDS, t->d_work,
+                         static_cast<uint32_t>(c->params.is_sv_graph != 0), r.task_flags, t->d_item_words, static_cast<uint32_t *>(nullptr));
+      if (!hip_ok(hipGetLastError(), "gtx_score_triage_kernel launch (behind the alignment)"))
+        return GTX_ERR_HIP;
+    }
+  }
+  return GTX_OK;
+}
+
+// the end: the done event, the other counter set zeroed, the timing slot kept
+static void align_end(AlignCall & a)
+{
+  CallScratch * const s = a.s;
+  a.mark(5, a.sq);
+  if (a.r.done_event)
+    (void)hipEventRecord(a.r.done_event, a.sq);
+  // the other set of counters, zeroed for the next call behind this call's last launch (the scratch is handed on in the order of
+  // that stream, or when the event recorded behind this is through: scratch_release)
+  s->spare_set_clean = hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(s->counter_set ^ 1u) * CallScratch::COUNTER_PITCH, 0,
+                                      CallScratch::COUNTER_PITCH * sizeof(uint32_t), a.sq) == hipSuccess;
+  s->timed_reads = a.r.n_reads;
+  if (a.timed)
+    ++s->ring_used;
+}
+
+// The one way into the alignment passes, behind the argument checks of the six align entry points
+static int align_call(gtx_ctx * c, AlignRequest r)
+{
+  if (c->device < 0)
+  {
+    g_last_error = "context was created without a device (libgtx has no CPU path)";
+    return GTX_ERR_NO_DEVICE;
+  }
+  if (r.tail_stream && !r.front_event)
+  {
+    g_last_error = "gtx_align_batch_planes_staged: a tail stream needs the front event (it is what the tail stream waits for)";
+    return GTX_ERR_ARG;
+  }
+  if (r.n_reads == 0) // an empty batch is valid (and its buffers may be NULL): its events are recorded, its work queue is empty
+  {
+    if (!r.front_event && !r.done_event && !r.triage)
+      return GTX_OK;
+    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
+      return GTX_ERR_HIP;
+    if (r.front_event && !hip_ok(hipEventRecord(r.front_event, r.stream), "front event"))
+      return GTX_ERR_HIP;
+    if (r.triage && !hip_ok(hipMemsetAsync(r.triage->d_work, 0, GTX_WORK_HEADER_WORDS * sizeof(uint32_t), r.stream), "work queue reset")) // (no read: no item has work)
+      return GTX_ERR_HIP;
+    if (r.done_event && !hip_ok(hipEventRecord(r.done_event, r.stream), "done event"))
+      return GTX_ERR_HIP;
+    return GTX_OK;
+  }
+  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
+    return GTX_ERR_HIP;
+  ScratchHold hold{*c, scratch_acquire(*c, r.stream), r.stream, true};
+  CallScratch * s = hold.s;
+  if (!s)
+    return GTX_ERR_HIP;
+  if (r.nibbles)
+  {
+    uint32_t const plane_stride = (r.seq_stride + PLANE_GROUP_BYTES - 1u) / PLANE_GROUP_BYTES * PLANE_GROUP_BYTES;
+    if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(r.n_reads) * plane_stride, "plane rows"))
+      return GTX_ERR_HIP;
+    if (int const rc = launch_planes_kernel(r.seq, r.seq_stride, r.n_reads, s->d_planes, plane_stride, r.stream))
+      return rc;
+    r.seq = s->d_planes;
+    r.seq_stride = plane_stride;
+  }
+  AlignCall a{c, s, r, r.stream};
+  int rc = align_setup(a);
+  if (rc == GTX_OK)
+    rc = align_front(a);
+  if (rc == GTX_OK)
+    rc = align_hbm(a);
+  if (rc == GTX_OK)
+    rc = align_side_bytes(a);
+  if (rc == GTX_OK)
+    align_end(a);
+  hold.stream = a.sq; // (the stream the call's last launch is on)
+  return rc;
+}
+
+extern "C" int gtx_align_batch(gtx_ctx * c, const uint8_t * d_seq, uint32_t seq_stride, const gtx_read_meta * d_meta,
+                               uint32_t n_reads, uint32_t * d_records, uint32_t rec_words, void * stream)
+{
+  return gtx_align_batch_flags(c, d_seq, seq_stride, d_meta, n_reads, d_records, rec_words, nullptr, stream);
+}
 
 // BAM nibble rows: repacked into plane rows in the call's scratch, then the same kernels
 extern "C" int gtx_align_batch_flags(gtx_ctx * c, const uint8_t * d_seq, uint32_t seq_stride, const gtx_read_meta * d_meta,
@@ -2112,26 +2548,22 @@ extern "C" int gtx_align_batch_flags(gtx_ctx * c, const uint8_t * d_seq, uint32_
     g_last_error = "gtx_align_batch: bad argument";
     return GTX_ERR_ARG;
   }
-  if (c->device < 0)
+  AlignRequest r{d_seq, seq_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream)};
+  r.nibbles = true;
+  return align_call(c, r);
+}
+
+// the argument checks every entry point over plane rows makes
+static bool planes_args_ok(gtx_ctx const * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta, uint32_t n_reads,
+                           uint32_t const * d_records, uint32_t rec_words)
+{
+  if (!c || rec_words < 8 || plane_stride == 0 || (plane_stride % PLANE_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(d_planes) & 15u) != 0 ||
+      (n_reads != 0 && (!d_planes || !d_meta || !d_records)))
   {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
+    g_last_error = "gtx_align_batch_planes: bad argument (plane rows are 16-byte groups at a 16-byte aligned address)";
+    return false;
   }
-  if (n_reads == 0) // an empty batch is valid (and its buffers may be NULL)
-    return GTX_OK;
-  hipStream_t const st = static_cast<hipStream_t>(stream);
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
-  ScratchHold hold{*c, scratch_acquire(*c, st), st, true};
-  CallScratch * s = hold.s;
-  if (!s)
-    return GTX_ERR_HIP;
-  uint32_t const plane_stride = (seq_stride + PLANE_GROUP_BYTES - 1u) / PLANE_GROUP_BYTES * PLANE_GROUP_BYTES;
-  if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(n_reads) * plane_stride, "plane rows"))
-    return GTX_ERR_HIP;
-  if (int const rc = launch_planes_kernel(d_seq, seq_stride, n_reads, s->d_planes, plane_stride, st))
-    return rc;
-  return align_planes(c, s, s->d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, st);
+  return true;
 }
 
 extern "C" int gtx_align_batch_planes(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta,
@@ -2140,16 +2572,14 @@ extern "C" int gtx_align_batch_planes(gtx_ctx * c, const uint8_t * d_planes, uin
   return gtx_align_batch_planes_staged(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, stream, nullptr, nullptr, nullptr);
 }
 
-static int align_batch_planes_staged(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta, uint32_t n_reads,
-                                     uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, void * stream, void * front_event,
-                                     void * tail_stream, void * done_event, uint32_t * d_compact, TriageRequest const * triage = nullptr);
-
 extern "C" int gtx_align_batch_planes_staged(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta,
                                              uint32_t n_reads, uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, void * stream,
                                              void * front_event, void * tail_stream, void * done_event)
 {
-  return align_batch_planes_staged(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, stream, front_event, tail_stream,
-                                   done_event, nullptr);
+  if (!planes_args_ok(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words))
+    return GTX_ERR_ARG;
+  return align_call(c, {d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream),
+                        static_cast<hipEvent_t>(front_event), static_cast<hipStream_t>(tail_stream), static_cast<hipEvent_t>(done_event)});
 }
 
 extern "C" int gtx_align_batch_planes_compact(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta,
@@ -2161,8 +2591,10 @@ extern "C" int gtx_align_batch_planes_compact(gtx_ctx * c, const uint8_t * d_pla
     g_last_error = "gtx_align_batch_planes_compact: needs d_task_flags and a 16-byte aligned d_compact";
     return GTX_ERR_ARG;
   }
-  return align_batch_planes_staged(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, stream, front_event, tail_stream,
-                                   done_event, d_compact);
+  if (!planes_args_ok(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words))
+    return GTX_ERR_ARG;
+  return align_call(c, {d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream),
+                        static_cast<hipEvent_t>(front_event), static_cast<hipStream_t>(tail_stream), static_cast<hipEvent_t>(done_event), d_compact});
 }
 
 extern "C" int gtx_align_batch_planes_triaged(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta,
@@ -2184,512 +2616,11 @@ extern "C" int gtx_align_batch_planes_triaged(gtx_ctx * c, const uint8_t * d_pla
     g_last_error = "gtx_align_batch_planes_triaged: GTX_TRIAGE_ITEMS_ARE_READS is not for SV graphs (every read adds to the reference depth)";
     return GTX_ERR_UNSUPPORTED;
   }
+  if (!planes_args_ok(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words))
+    return GTX_ERR_ARG;
   TriageRequest const t{d_items, d_item_words, n_items, d_work, are_reads};
-  return align_batch_planes_staged(c, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, stream, front_event, tail_stream,
-                                   done_event, d_compact, &t);
-}
-
-static int align_batch_planes_staged(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta, uint32_t n_reads,
-                                     uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, void * stream, void * front_event,
-                                     void * tail_stream, void * done_event, uint32_t * d_compact, TriageRequest const * triage)
-{
-  if (!c || rec_words < 8 || plane_stride == 0 || (plane_stride % PLANE_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(d_planes) & 15u) != 0 ||
-      (n_reads != 0 && (!d_planes || !d_meta || !d_records)))
-  {
-    g_last_error = "gtx_align_batch_planes: bad argument (plane rows are 16-byte groups at a 16-byte aligned address)";
-    return GTX_ERR_ARG;
-  }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
-  hipStream_t const st = static_cast<hipStream_t>(stream);
-  if (tail_stream && !front_event)
-  {
-    g_last_error = "gtx_align_batch_planes_staged: a tail stream needs the front event (it is what the tail stream waits for)";
-    return GTX_ERR_ARG;
-  }
-  if (n_reads == 0)
-  {
-    if ((front_event || done_event || triage) && !hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-      return GTX_ERR_HIP;
-    if (front_event && !hip_ok(hipEventRecord(static_cast<hipEvent_t>(front_event), st), "front event"))
-      return GTX_ERR_HIP;
-    if (triage && !hip_ok(hipMemsetAsync(triage->d_work, 0, GTX_WORK_HEADER_WORDS * sizeof(uint32_t), st), "work queue reset")) // (no read: no item has work)
-      return GTX_ERR_HIP;
-    if (done_event && !hip_ok(hipEventRecord(static_cast<hipEvent_t>(done_event), st), "done event"))
-      return GTX_ERR_HIP;
-    return GTX_OK;
-  }
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
-  ScratchHold hold{*c, scratch_acquire(*c, st), st, true};
-  if (!hold.s)
-    return GTX_ERR_HIP;
-  // (with a tail stream the call ends there: the scratch is free when THAT stream is through -- and is not handed to the
-  //  next call on `stream` by stream order, which would reset queues the tail still reads)
-  hipStream_t last = st;
-  int const rc = align_planes(c, hold.s, d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, st,
-                              static_cast<hipEvent_t>(front_event), std::getenv("GTX_PARTS") ? nullptr : static_cast<hipStream_t>(tail_stream),
-                              static_cast<hipEvent_t>(done_event), &last, d_compact, triage);
-  hold.stream = last; // (the stream the call's last launch is on)
-  return rc;
-}
-
-// the passes over plane rows (d_seq / seq_stride: the plane rows and their pitch)
-static int align_planes(gtx_ctx * c, CallScratch * s, const uint8_t * d_seq, uint32_t seq_stride, const gtx_read_meta * d_meta, uint32_t n_reads,
-                        uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, hipStream_t st, hipEvent_t front_event, hipStream_t tail_stream,
-                        hipEvent_t done_event, hipStream_t * last_stream, uint32_t * d_compact, TriageRequest const * triage)
-{
-  // (the pass counters and, behind them, the state of the HBM-table and wide-site passes: the set the last call left zeroed --
-  //  CallScratch::d_counter_sets; after a call that failed on its way the set is zeroed here, as every call did before round 6)
-  {
-    uint32_t const use = s->counter_set ^ 1u;
-    if (!s->spare_set_clean &&
-        !hip_ok(hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(use) * CallScratch::COUNTER_PITCH, 0, CallScratch::COUNTER_PITCH * sizeof(uint32_t), st), "task counter reset"))
-      return GTX_ERR_HIP;
-    counter_set_select(*s, use);
-    s->spare_set_clean = false;
-  }
-  // queues: room for every task (a graph on which no read is simple sends them all)
-  if (!grow(s->d_queue, s->queue_cap, 2ull * n_reads, "pass-2 queue") || !grow(s->d_queue1, s->queue1_cap, n_reads, "pass-1 queue"))
-    return GTX_ERR_HIP;
-  bool const second_pass = s->d_big_state != nullptr;
-  if (second_pass)
-  {
-    // the queue holds every task of a small batch and 8 Mi tasks of a large one (tasks beyond it keep their status bit)
-    uint64_t const want = std::min<uint64_t>(2ull * n_reads, 8ull << 20);
-    uint64_t cap = s->big_task_cap;
-    if (!grow(s->d_big_tasks, cap, want, "second-pass queue"))
-      return GTX_ERR_HIP;
-    s->big_task_cap = static_cast<uint32_t>(cap);
-  }
-  // tasks a wave of the general pass claims per visit to the counter
-  char const * gc = std::getenv("GTX_GENERAL_CLAIM");
-  uint32_t const general_claim = gc && std::atoi(gc) > 0 ? static_cast<uint32_t>(std::atoi(gc)) : 0u; // (0: the kernel sizes its claims to its queue)
-  // test switch: 1 = every task goes through all passes (the last one decides), 2 = every task is done by pass 2
-  char const * fb = std::getenv("GTX_FORCE_SECOND_PASS");
-  uint32_t const force = fb ? static_cast<uint32_t>(std::atoi(fb)) : 0u;
-  uint32_t const n_cu = static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256);
-  bool timed = false;
-  uint32_t epoch = 0;
-  {
-    std::lock_guard<std::mutex> lock(c->pool_mutex);
-    timed = c->timing_armed;
-    if (timed && c->epoch_queried) // the first timed call behind a query: a new epoch
-    {
-      ++c->time_epoch;
-      c->epoch_queried = false;
-    }
-    epoch = c->time_epoch;
-    // (GTX_TIME_EVERY=n: one call in n is timed -- a timed call brackets its launches with events, packets the streams carry
-    //  between the kernels; the means of gtx_ctx_kernel_times are over the timed calls)
-    static uint32_t const every = [] { char const * e = std::getenv("GTX_TIME_EVERY"); int const v = e ? std::atoi(e) : 1; return static_cast<uint32_t>(v > 0 ? v : 1); }();
-    if (timed && every > 1 && (c->timed_seq++ % every) != 0)
-      timed = false;
-  }
-  if (timed && s->ring_epoch != epoch)
-  {
-    s->ring_epoch = epoch;
-    s->ring_used = 0;
-  }
-  uint32_t const force_both = static_cast<uint32_t>(c->params.force_align_both_orientations != 0);
-  char const * e4 = std::getenv("GTX_EXPRESS4"); // A/B switch: 0 = one read per wavefront in pass 1
-  char const * eh = std::getenv("GTX_HINT");     // A/B switch: 0 = no position-hinted pass
-  bool const four = !(e4 && e4[0] == '0');
-  bool const hinted = four && !(eh && eh[0] == '0');
-  // GTX_EXPRESS4=lean / wide force a build (tests); else by the graph's density
-  bool const wide = e4 && e4[0] == 'w' ? true : e4 && e4[0] == 'l' ? false : c->express4_wide;
-  // A batch can be cut into parts whose general passes run on a second stream beside the front passes of the next part
-  // (GTX_PARTS=n).  Measured on cfg2 it does not pay: the general pass is bound by instruction issue and wave slots, not
-  // by memory latency -- ~6 000 wave instructions per task, one task per wavefront, a full grid holds all of a CU's LDS --
-  // so its parts neither shrink with their share of the tasks (0.7 ms for a quarter of them against 1.0 ms for all) nor
-  // leave room for the other stream: 3.1 / 3.6 / 4.7 / 6.6 ms per step with 1 / 2 / 4 / 8 parts.  Default: one part.
-  // (Round 3, same finding with the short queues behind the position-hinted pass: pass 1 on a second stream beside a first
-  //  launch of pass 2 over what pass 0 sent it, a second launch of pass 2 behind both -- 1.53 ms per step against 1.36 ms
-  //  one after the other; side by side pass 1 took 0.41 ms instead of 0.19 ms and the two launches of pass 2 0.74 ms instead
-  //  of 0.38 ms.  Reading every lookup table once in front of pass 1 (to spare it the cold misses) did not move it either:
-  //  the cost of a short queue on this chip is the launch itself, per wavefront, not the tables' first touch.)
-  char const * ep = std::getenv("GTX_PARTS");
-  uint32_t parts = 1u;
-  if (ep)
-    parts = static_cast<uint32_t>(std::min<long>(std::max<long>(std::atol(ep), 1), CallScratch::MAX_PARTS));
-  // (gtx_align_batch_planes_staged with a done event: the HBM-table pass and what follows it on a stream of the scratch's own)
-  // (GTX_OWN_END=1: the HBM-table pass and what follows it on a stream of the scratch's own behind the general pass -- it has no
-  //  task on most batches but wants 196 registers per wavefront to be placed, 0.14 ms of waiting beside a full chip that the
-  //  tail stream need not share.  Measured: 1.12 ms per cfg2 step against 0.85 -- the runtime folds more streams than it has
-  //  hardware queues onto the same ones, and the schedule loses its overlap.  Off; the done event is recorded on the tail
-  //  stream.)
-  char const * eo = std::getenv("GTX_OWN_END");
-  bool const own_end = done_event != nullptr && tail_stream != nullptr && tail_stream != st && parts == 1 && eo && eo[0] == '1';
-  if ((parts > 1 || own_end) && !s->side_stream)
-  {
-    hipStream_t side;
-    if (!hip_ok(hipStreamCreateWithFlags(&side, hipStreamNonBlocking), "side stream"))
-      return GTX_ERR_HIP;
-    s->side_stream = side;
-    for (auto & e : s->sync_events)
-    {
-      hipEvent_t ev;
-      if (!hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "sync events"))
-        return GTX_ERR_HIP;
-      e = ev;
-    }
-  }
-  // (calls beyond the ring are not timed: a query empties it)
-  if (timed && s->ring_used >= CallScratch::TIME_RING)
-    timed = false;
-  uint32_t const slot = timed ? s->ring_used : 0u;
-  if (timed && !s->h_span) // (pinned: only a host that asks for kernel times pays for it; without it pass 0's time is the interval between its events)
-  {
-    if (hipHostMalloc(reinterpret_cast<void **>(&s->h_span), CallScratch::TIME_RING * 2 * sizeof(unsigned long long)) != hipSuccess)
-      s->h_span = nullptr;
-  }
-  if (timed && s->h_span)
-    s->h_span[2 * slot] = s->h_span[2 * slot + 1] = 0ull;
-  if (timed && !s->time_ring[slot][0][0])
-    for (uint32_t p = 0; p < (parts > 1 ? CallScratch::MAX_PARTS : 1u); ++p)
-      for (auto & e : s->time_ring[slot][p])
-      {
-        hipEvent_t ev;
-        if (!hip_ok(hipEventCreate(&ev), "pass events"))
-          return GTX_ERR_HIP;
-        e = ev;
-      }
-  if (timed && parts > 1 && !s->time_ring[slot][1][0]) // (a slot made for a one-part call)
-    for (uint32_t p = 1; p < CallScratch::MAX_PARTS; ++p)
-      for (auto & e : s->time_ring[slot][p])
-      {
-        hipEvent_t ev;
-        if (!hip_ok(hipEventCreate(&ev), "pass events"))
-          return GTX_ERR_HIP;
-        e = ev;
-      }
-  s->timed = false;
-  hipStream_t sg = parts > 1 ? static_cast<hipStream_t>(s->side_stream) : st; // stream of the general / HBM-table passes
-  hipStream_t s1 = st;                                                         // stream of the express pass
-  // gtx_align_batch_planes_staged with a tail stream: everything behind the front event goes there
-  auto front_done = [&]()
-  {
-    if (!front_event)
-      return;
-    (void)hipEventRecord(front_event, st);
-    if (tail_stream && tail_stream != st && parts == 1)
-    {
-      (void)hipStreamWaitEvent(tail_stream, front_event, 0);
-      s1 = sg = tail_stream;
-      // (from here on the tail stream holds launches that use the scratch: an error return below must leave the caller's
-      //  ScratchHold recording `done` on THAT stream, else the next call on the front stream would reset counters and queues the
-      //  tail stream may still be reading)
-      if (last_stream)
-        *last_stream = tail_stream;
-    }
-  };
-  // (gtx_align_batch_planes_triaged where item i is read i: a bit per read, written by the position-hinted pass, completed behind
-  //  the last pass)
-  unsigned long long * var_masks = nullptr;
-  if (triage && triage->items_are_reads)
-  {
-    if (!grow(s->d_var_masks, s->var_mask_cap, (static_cast<uint64_t>(n_reads) + 63u) / 64u, "variant-site bits of the reads"))
-      return GTX_ERR_HIP;
-    var_masks = s->d_var_masks;
-  }
-  auto mark = [&](uint32_t part, int k, hipStream_t on)
-  {
-    if (timed)
-      (void)hipEventRecord(static_cast<hipEvent_t>(s->time_ring[slot][part][k]), on);
-  };
-  if (parts > 1)
-  {
-    // (the side stream starts behind everything the caller's stream holds so far: the resets above, the caller's uploads)
-    (void)hipEventRecord(static_cast<hipEvent_t>(s->sync_events[CallScratch::MAX_PARTS]), st);
-    (void)hipStreamWaitEvent(sg, static_cast<hipEvent_t>(s->sync_events[CallScratch::MAX_PARTS]), 0);
-  }
-  // (whole kilo-reads per part, at least one: n_reads < parts must not give a step of 0, an inexact division must not give
-  //  a part more than asked for -- the counters, events and queues are sized for MAX_PARTS)
-  uint32_t const step = parts == 1 ? n_reads : std::max<uint32_t>(1024u, static_cast<uint32_t>(((static_cast<uint64_t>(n_reads) + parts - 1u) / parts + 1023u) / 1024u * 1024u));
-  uint32_t used_parts = 0;
-  for (uint32_t first = 0; first < n_reads; first += step, ++used_parts)
-  {
-    uint32_t const n = std::min(step, n_reads - first), part = used_parts;
-    uint32_t * counters = s->d_counters + 8 * part;
-    uint8_t const * seq = d_seq + static_cast<uint64_t>(first) * seq_stride;
-    gtx_read_meta const * meta = d_meta + first;
-    uint32_t * records = d_records + static_cast<uint64_t>(first) * 2 * rec_words;
-    uint32_t * queue1 = s->d_queue1 + first;
-    uint32_t * queue2 = s->d_queue + 2ull * first;
-    // grids: as many single-wave workgroups as are resident at once; they pull work from shared counters
-    uint64_t const chunks = (static_cast<uint64_t>(n) + TASK_CHUNK - 1) / TASK_CHUNK;
-    uint32_t const blocks1 = static_cast<uint32_t>(std::min<uint64_t>(chunks, static_cast<uint64_t>(n_cu) * c->express_blocks_per_cu));
-    char const * egw = std::getenv("GTX_GENERAL_PER_WAVE"); // (A/B switch: tasks a wavefront of a short queue should find)
-    uint32_t const general_goal = egw && std::atoi(egw) > 0 ? static_cast<uint32_t>(std::atoi(egw)) : 0u;
-    // (GTX_GENERAL_GRID=<wavefronts per CU>: A/B switch; default: as many as are resident)
-    char const * eg = std::getenv("GTX_GENERAL_GRID");
-    // (a long queue -- the cfg3 graph: 48 k tasks -- is not done faster by more than 12 wavefronts per CU: 4 / 8 / 12 / 20 per CU =
-    //  1.51 / 0.91 / 0.70 / 0.76 ms, the longest task 0.5 M cycles with 4 per CU and 3.4 M with 20; what they queue for is per CU)
-    uint32_t const general_per_cu = eg && std::atoi(eg) > 0 ? static_cast<uint32_t>(std::atoi(eg)) : std::min<uint32_t>(static_cast<uint32_t>(c->align_blocks_per_cu), 12u);
-    uint32_t const blocks2 = static_cast<uint32_t>(std::min<uint64_t>(2ull * n, static_cast<uint64_t>(n_cu) * general_per_cu));
-    uint32_t const blocks4 = static_cast<uint32_t>(std::min<uint64_t>(
-      chunks, static_cast<uint64_t>(n_cu) * (wide ? c->express4_wide_blocks_per_cu : c->express4_blocks_per_cu)));
-    mark(part, 0, st);
-    if (hinted)
-    {
-      // pass 0: one read per lane from the position hint; what it declines is queued for pass 1.  (GTX_HINT=decline: the
-      // pass runs but declines everything -- a test of the queue plumbing)
-      static bool const sv_express = std::getenv("GTX_SV_EXPRESS") && std::getenv("GTX_SV_EXPRESS")[0] == '1'; // (A/B switch: the express pass on SV graphs as well)
-      bool const sv_skips_express = c->params.is_sv_graph != 0 && !sv_express && force == 0;
-      char const * hb = std::getenv("GTX_HINT_BUILD"); // (test switch: lean | dense build of pass 0; default: dense beside the wide express pass)
-      bool const hint_dense = hb && hb[0] == 'd' ? true : hb && hb[0] == 'l' ? false : c->express4_wide;
-      bool const hint_long = seq_stride > HintGeom<AlignCfg::KC>::ROW_BYTES; // (rows for reads of more than 160 bases: the eight-k-mer build)
-      uint32_t const hint_threads = 64u * ((hint_long || hint_dense) ? GTX_HINT_WAVES : GTX_HINT_WAVES_LEAN);
-      hipLaunchKernelGGL(hint_long ? gtx_align_hinted_long_kernel : hint_dense ? gtx_align_hinted_dense_kernel : gtx_align_hinted_kernel,
-                         dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, st, c->dev_graph, c->dev_index, seq, seq_stride,
-                         meta, n, records, rec_words, force_both, queue1, queue2, reinterpret_cast<unsigned long long *>(counters + 2),
-                         static_cast<uint32_t>(force != 0 || (eh && eh[0] == 'd')) | (sv_skips_express ? 4u : 0u)
-#ifdef GTX_PROF
-                           | (eh && eh[0] == 'x' ? 2u : 0u)
-#endif
-                           ,
-                         d_task_flags ? d_task_flags + 2ull * first : static_cast<uint8_t *>(nullptr),
-                         d_compact ? d_compact + static_cast<uint64_t>(first) * GTX_COMPACT_WORDS : static_cast<uint32_t *>(nullptr),
-                         timed && s->h_span ? s->d_span : static_cast<unsigned long long *>(nullptr),
-                         var_masks ? var_masks + first / 64u : static_cast<unsigned long long *>(nullptr));
-      if (!hip_ok(hipGetLastError(), "gtx_align_hinted_kernel launch"))
-        return GTX_ERR_HIP;
-      mark(part, 1, st);
-      // (gtx_align_batch_planes_staged: from here on the call is short queues -- the caller's other streams may come in;
-      //  GTX_STAGED_FRONT=express: the express pass stays on the caller's stream as well and the front event is recorded behind it)
-      static bool const front_with_express = std::getenv("GTX_STAGED_FRONT") && std::getenv("GTX_STAGED_FRONT")[0] == 'e';
-      if (first + step >= n_reads && !front_with_express)
-        front_done();
-      // (the queue's length is known on the device only: the grid is what can be resident, or one wavefront per group of four
-      //  reads of a small batch; the kernel sizes its claims to the queue)
-      char const * ew = std::getenv("GTX_EXPRESS_PER_WAVE"); // (A/B switch: groups a wavefront of a short queue should find)
-      uint32_t const express_goal = ew && std::atoi(ew) > 0 ? static_cast<uint32_t>(std::atoi(ew)) : 0u;
-      char const * eq = std::getenv("GTX_EXPRESS_GRID"); // (A/B switch: wavefronts per CU of the express pass)
-      uint32_t const express_per_cu = eq && std::atoi(eq) > 0 ? static_cast<uint32_t>(std::atoi(eq))
-                                                               : static_cast<uint32_t>(wide ? c->express4_wide_blocks_per_cu : c->express4_blocks_per_cu);
-      uint32_t const blocks4q = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(n) + 3u) / 4u, static_cast<uint64_t>(n_cu) * express_per_cu));
-      hipLaunchKernelGGL(wide ? gtx_align_express4q_wide_kernel : gtx_align_express4q_kernel, dim3(blocks4q), dim3(64), 0, s1, c->dev_graph,
-                         c->dev_index, seq, seq_stride, meta, records, rec_words, counters, queue1, counters + 3, queue2, counters + 2,
-                         counters + 4, static_cast<uint32_t>(force != 0) | (express_goal << 8));
-      if (first + step >= n_reads && front_with_express)
-        front_done();
-      // (the call's launches of the position-hinted pass have added to the span: home with it -- on the stream of the short queues,
-      //  behind the express launch: on the caller's stream the copy sat between the pass and whatever the caller queues behind it)
-      if (timed && s->h_span && first + step >= n_reads)
-        (void)hipMemcpyAsync(s->h_span + 2 * slot, s->d_span, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s1);
-    }
-    else
-    {
-      mark(part, 1, st);
-      if (first + step >= n_reads) // (no position-hinted pass: the event marks the call's start)
-        front_done();
-      if (four)
-        hipLaunchKernelGGL(wide ? gtx_align_express4_wide_kernel : gtx_align_express4_kernel, dim3(blocks4), dim3(64), 0, s1, c->dev_graph,
-                           c->dev_index, seq, seq_stride, meta, n, records, rec_words, force_both, counters, queue2, counters + 2,
-                           static_cast<uint32_t>(force != 0));
-      else
-        hipLaunchKernelGGL(gtx_align_express_kernel, dim3(blocks1), dim3(64), 0, s1, c->dev_graph, c->dev_index, seq, seq_stride, meta, n,
-                           records, rec_words, force_both, counters, queue2, counters + 2, static_cast<uint32_t>(force != 0));
-    }
-    if (!hip_ok(hipGetLastError(), "express kernel launch"))
-      return GTX_ERR_HIP;
-    mark(part, 2, s1);
-    if (parts > 1)
-    {
-      (void)hipEventRecord(static_cast<hipEvent_t>(s->sync_events[part]), st);
-      (void)hipStreamWaitEvent(sg, static_cast<hipEvent_t>(s->sync_events[part]), 0);
-    }
-    mark(part, 3, sg);
-    hipLaunchKernelGGL(gtx_align_kernel, dim3(blocks2), dim3(64), 0, sg, c->dev_graph, c->dev_index, seq, seq_stride, meta, records, rec_words,
-                       queue2, counters + 2, counters + 1, second_pass ? s->d_big_tasks : nullptr, s->big_task_cap, s->d_big_state,
-                       static_cast<uint32_t>(force == 1) | (general_goal << 8), 2u * first, general_claim, counters + 5);
-    if (!hip_ok(hipGetLastError(), "gtx_align_kernel launch"))
-      return GTX_ERR_HIP;
-    mark(part, 4, sg);
-  }
-  if (own_end && sg == tail_stream)
-  {
-    // The HBM-table pass has no task on most batches but wants 196 registers per wavefront to be placed at all: beside a
-    // full chip that is 0.14 ms of waiting, which the tail stream -- the next batch's queues are behind it -- need not share.
-    (void)hipEventRecord(static_cast<hipEvent_t>(s->sync_events[0]), sg);
-    sg = static_cast<hipStream_t>(s->side_stream);
-    (void)hipStreamWaitEvent(sg, static_cast<hipEvent_t>(s->sync_events[0]), 0);
-  }
-#ifdef GTX_EXPERIMENT
-  // (experiment builds only -- never the product: what a step would take if the passes that find empty queues cost nothing)
-  static bool const skip_hbm_passes = std::getenv("GTX_SKIP_HBM_PASSES") != nullptr;
-#else
-  constexpr bool skip_hbm_passes = false;
-#endif
-  if (second_pass && !skip_hbm_passes)
-  {
-    HbmPassArgs a;
-    a.g = c->dev_graph;
-    a.ix = c->dev_index;
-    a.seq = d_seq;
-    a.seq_stride = seq_stride;
-    a.meta = d_meta;
-    a.records = d_records;
-    a.rec_words = rec_words;
-    a.big_tasks = s->d_big_tasks;
-    a.big_task_cap = s->big_task_cap;
-    a.big_state = s->d_big_state;
-    // (a large batch: the HBM-table pass with all its workgroups -- the workspaces grow once, the scratch is this call's)
-    if (n_reads >= gtx_ctx::HBM_SMALL_BATCH && s->big_blocks < c->big_blocks)
-    {
-      void * ws = nullptr;
-      if (!hip_ok(gtx::dev_malloc(&ws, static_cast<size_t>(c->big_blocks) * big_workspace_bytes()), "second-pass workspaces"))
-        return GTX_ERR_HIP;
-      // (the scratch came back to this stream in stream order only -- scratch_acquire does not wait for the host: an earlier,
-      //  small call's HBM-table pass may still be running on the old block, and a block goes back to the cache only when no
-      //  kernel can still use it, gtx_devmem.hpp: another context's thread could be handed it for another stream.  Once per
-      //  scratch, at its first large batch.)
-      if (s->d_big_ws && s->used && s->done)
-        (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
-      (void)gtx::dev_free(s->d_big_ws);
-      s->d_big_ws = ws;
-      s->big_blocks = c->big_blocks;
-    }
-    a.big_blocks = n_reads >= gtx_ctx::HBM_SMALL_BATCH ? s->big_blocks : std::min<uint32_t>(s->big_blocks, static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256));
-    if (c->h_big_seen)
-    {
-      // (tasks are claimed one by one from the queue: any number of workgroups does them all -- fewer only take longer when the
-      //  guess is too low, and the next call knows better)
-      uint32_t const seen = *static_cast<uint32_t volatile *>(c->h_big_seen);
-      static bool const adaptive = !(std::getenv("GTX_BIG_GRID_ADAPTIVE") && std::getenv("GTX_BIG_GRID_ADAPTIVE")[0] == '0'); // (A/B switch)
-      if (adaptive && seen != 0xFFFFFFFFu)
-        a.big_blocks = static_cast<uint32_t>(std::min<uint64_t>(a.big_blocks, 2ull * seen + 32u));
-    }
-    a.big_ws = s->d_big_ws;
-    a.wide_tasks = s->d_wide_tasks;
-    a.wide_state = s->d_wide_state;
-    a.wide_ws = s->d_wide_ws;
-    a.exact_tasks = s->d_exact_tasks;
-    a.exact_state = s->d_exact_state;
-    a.exact_slab = nullptr;
-    a.exact_slab_bytes = c->exact_slab_bytes;
-    a.exact_cand_cap = c->exact_cand_cap;
-    a.exact_part_cand_cap = std::min<uint32_t>(c->exact_cand_cap, CallScratch::EXACT_PART_CANDIDATES);
-    a.exact_parts = c->exact_parts;
-    a.exact_fixed_parts = c->exact_fixed_parts;
-    a.wide_sites = c->has_wide_sites;
-    a.arena = c->d_big_records;
-    a.arena_words = c->big_record_words;
-    a.arena_cursor = c->d_arena_cursor;
-    char const * what = launch_hbm_passes(a, sg);
-
-    if (!what)
-    {
-      // the exact launches, with one of the context's slabs: chosen, waited for if need be, used and marked busy again in one
-      // critical section (the next call's wait has to see this call's record)
-      std::lock_guard<std::mutex> lock(c->exact_mutex);
-      bool wait = false;
-      gtx_ctx::ExactSlot const * slot = exact_slot_for_call(*c, exact_slab_for(*c, n_reads), &wait);
-      if (!slot)
-        return GTX_ERR_HIP;
-      if (wait)
-        (void)hipStreamWaitEvent(sg, static_cast<hipEvent_t>(slot->idle), 0);
-      a.exact_slab = slot->slab;
-      a.exact_slab_bytes = slot->bytes;
-      if (!c->exact_fixed_parts) // (as many parts as the slab has room for: none smaller than 2 MB, 32 MB where allele sets are wide)
-        a.exact_parts = static_cast<uint32_t>(std::min<uint64_t>(c->exact_parts, std::max<uint64_t>(1u, (slot->bytes >> 20) / (c->has_wide_sites ? 32u : 2u))));
-      // (the launches' grids by what the batch before sent this way -- tasks are claimed one by one, any number of workgroups does
-      //  them all: a workgroup of the pass wants 32 KB of LDS, and beside the position-hinted pass of the next batch a thousand of them
-      //  waited for that pass' end to find an empty queue -- 150-200 us on the stream of the short queues, the scoring behind them)
-      {
-        static bool const adaptive = !(std::getenv("GTX_BIG_GRID_ADAPTIVE") && std::getenv("GTX_BIG_GRID_ADAPTIVE")[0] == '0');
-        uint32_t const seen_exact = c->h_big_seen ? static_cast<uint32_t volatile *>(c->h_big_seen)[2] : 0xFFFFFFFFu;
-        a.exact_grid_limit = (!adaptive || c->exact_fixed_parts || seen_exact == 0xFFFFFFFFu) ? 0u : 2u * seen_exact + 4u;
-      }
-      what = launch_exact_passes(a, sg);
-      if (!what && c->h_big_seen)
-        hipLaunchKernelGGL(gtx_seen_kernel, dim3(1), dim3(64), 0, sg, c->h_big_seen, s->d_big_state, s->d_exact_state);
-      (void)hipEventRecord(static_cast<hipEvent_t>(slot->idle), sg);
-    }
-    if (what)
-    {
-      (void)hip_ok(hipErrorLaunchFailure, what);
-      return GTX_ERR_HIP;
-    }
-  }
-  if (d_task_flags)
-  {
-    // the dense side array for what the position-hinted pass did not settle (its queue and the general pass' queue, per
-    // part), or -- without that pass -- for every task
-    uint32_t part = 0;
-    for (uint32_t first = 0; first < n_reads; first += step, ++part)
-    {
-      uint32_t const n = std::min(step, n_reads - first);
-      uint32_t const * counters = s->d_counters + 8 * part;
-      uint32_t const * rec_part = d_records + static_cast<uint64_t>(first) * 2 * rec_words;
-      uint8_t * flags_part = d_task_flags + 2ull * first;
-      if (hinted)
-        // (one-wave workgroups: behind the short queues this launch stands beside the position-hinted pass of the NEXT batch, whose
-        //  workgroups of two wavefronts take every pair of slots a retiring one frees -- a workgroup of four wavefronts waited for that
-        //  pass' end, 130-180 us in the trace of the staggered schedule, and the scoring of this batch with it)
-        hipLaunchKernelGGL(gtx_task_flags_fixup_kernel, dim3(n_cu * 16u), dim3(64), 0, sg, rec_part, rec_words, flags_part, s->d_queue1 + first,
-                           counters + 3, s->d_queue + 2ull * first, counters + 2,
-                           var_masks ? var_masks + first / 64u : static_cast<unsigned long long *>(nullptr));
-      else
-      {
-        hipLaunchKernelGGL(gtx_task_flags_all_kernel, dim3((2u * n + 255u) / 256u), dim3(256), 0, sg, rec_part, rec_words, flags_part, 2u * n);
-        if (var_masks)
-          hipLaunchKernelGGL(gtx_var_masks_kernel, dim3((n + 255u) / 256u), dim3(256), 0, sg, flags_part, n, var_masks + first / 64u);
-      }
-      if (!hip_ok(hipGetLastError(), "task flags launch"))
-        return GTX_ERR_HIP;
-    }
-  }
-  if (triage)
-  {
-    // The scorer's first stage (which items' reads carry a variant site: the side array, complete behind the launch above, and
-    // the items' words) HERE, behind the short queues on their stream, instead of in front of the scoring on the stream that
-    // carries the position-hinted passes: 37 us of a 650 us step there, nothing here -- the queues' stream is idle half of the time.
-    if (!hip_ok(hipMemsetAsync(triage->d_work, 0, GTX_WORK_HEADER_WORDS * sizeof(uint32_t), sg), "work queue reset"))
-      return GTX_ERR_HIP;
-    if (var_masks)
-    {
-      uint32_t const n_words = (n_reads + 63u) / 64u;
-      hipLaunchKernelGGL(gtx_mask_triage_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, sg, var_masks, n_words, triage->d_work + GTX_WORK_HEADER_WORDS,
-                         triage->d_work);
-      if (!hip_ok(hipGetLastError(), "gtx_mask_triage_kernel launch"))
-        return GTX_ERR_HIP;
-    }
-    else if (triage->n_items)
-    {
-      hipLaunchKernelGGL(gtx_score_triage_kernel, dim3((triage->n_items + TRIAGE_THREADS * TRIAGE_PER_THREAD - 1) / (TRIAGE_THREADS * TRIAGE_PER_THREAD)),
-                         dim3(TRIAGE_THREADS), 0, sg, triage->d_items, triage->n_items, d_records, rec_words, triage->d_work + GTX_WORK_HEADER_WORDS, triage->d_work,
-                         static_cast<uint32_t>(c->params.is_sv_graph != 0), d_task_flags, triage->d_item_words, static_cast<uint32_t *>(nullptr));
-      if (!hip_ok(hipGetLastError(), "gtx_score_triage_kernel launch (behind the alignment)"))
-        return GTX_ERR_HIP;
-    }
-  }
-  mark(0, 5, sg);
-  if (done_event)
-    (void)hipEventRecord(done_event, sg);
-  // the other set of counters, zeroed for the next call behind this call's last launch (the scratch is handed on in the order of
-  // that stream, or when the event recorded behind this is through: scratch_release)
-  s->spare_set_clean = hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(s->counter_set ^ 1u) * CallScratch::COUNTER_PITCH, 0,
-                                      CallScratch::COUNTER_PITCH * sizeof(uint32_t), sg) == hipSuccess;
-  if (last_stream)
-    *last_stream = sg;
-  if (parts > 1)
-  {
-    // the caller's stream goes on when the side stream is through
-    (void)hipEventRecord(static_cast<hipEvent_t>(s->sync_events[CallScratch::MAX_PARTS]), sg);
-    (void)hipStreamWaitEvent(st, static_cast<hipEvent_t>(s->sync_events[CallScratch::MAX_PARTS]), 0);
-  }
-  s->timed = timed;
-  s->timed_reads = n_reads;
-  if (timed)
-  {
-    s->ring_parts[slot] = used_parts;
-    ++s->ring_used;
-  }
-  return GTX_OK;
+  return align_call(c, {d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream),
+                        static_cast<hipEvent_t>(front_event), static_cast<hipStream_t>(tail_stream), static_cast<hipEvent_t>(done_event), d_compact, &t});
 }
 
 // (ms[4], tasks[4]): position-hinted pass, express pass, general pass, HBM-table pass.  ms: the mean over the timed
@@ -2721,7 +2652,7 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
   }
   // ("nothing was timed" is decided by the ring's slots below, not by the last call: beyond TIME_RING calls of an epoch the last
   //  one is untimed while up to TIME_RING earlier ones sit in the ring.  The query is meant to come behind the calls in flight:
-  //  ring_used / ring_parts of a scratch another host thread is inside of are read here without its lock.)
+  //  ring_used of a scratch another host thread is inside of is read here without its lock.)
   if (!s)
     return GTX_OK;
   if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
@@ -2733,30 +2664,23 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
     uint32_t const used = std::min(u->ring_used, CallScratch::TIME_RING);
     for (uint32_t slot = 0; slot < used; ++slot)
     {
-      uint32_t const n_parts = u->ring_parts[slot];
-      if (n_parts == 0 || !hip_ok(hipEventSynchronize(static_cast<hipEvent_t>(u->time_ring[slot][0][5])), "pass events"))
+      auto ev = [&](int k) { return static_cast<hipEvent_t>(u->time_ring[slot][k]); };
+      if (!hip_ok(hipEventSynchronize(ev(5)), "pass events"))
         continue;
-      for (uint32_t p = 0; p < n_parts; ++p)
-      {
-        float d = 0.0f;
-        auto ev = [&](int k) { return static_cast<hipEvent_t>(u->time_ring[slot][p][k]); };
-        if (hipEventElapsedTime(&d, ev(0), ev(1)) == hipSuccess)
-        {
-          // (the position-hinted pass by its own clock where the call brought it home: gtx_align_hinted_kernel's span)
-          unsigned long long const t0 = u->h_span ? ~u->h_span[2 * slot] : 0ull, t1 = u->h_span ? u->h_span[2 * slot + 1] : 0ull;
-          if (p == 0 && u->h_span && u->h_span[2 * slot + 1] != 0ull && t1 > t0 && c->wall_clock_khz > 0)
-            d = static_cast<float>(static_cast<double>(t1 - t0) / static_cast<double>(c->wall_clock_khz));
-          else if (p != 0 && u->h_span && u->h_span[2 * slot + 1] != 0ull)
-            d = 0.0f; // (the span covers all parts of the call)
-          sum[0] += d;
-        }
-        if (hipEventElapsedTime(&d, ev(1), ev(2)) == hipSuccess)
-          sum[1] += d;
-        if (hipEventElapsedTime(&d, ev(3), ev(4)) == hipSuccess)
-          sum[2] += d;
-      }
       float d = 0.0f;
-      if (hipEventElapsedTime(&d, static_cast<hipEvent_t>(u->time_ring[slot][n_parts - 1][4]), static_cast<hipEvent_t>(u->time_ring[slot][0][5])) == hipSuccess)
+      if (hipEventElapsedTime(&d, ev(0), ev(1)) == hipSuccess)
+      {
+        // (the position-hinted pass by its own clock where the call brought it home: gtx_align_hinted_kernel's span)
+        unsigned long long const t0 = u->h_span ? ~u->h_span[2 * slot] : 0ull, t1 = u->h_span ? u->h_span[2 * slot + 1] : 0ull;
+        if (u->h_span && u->h_span[2 * slot + 1] != 0ull && t1 > t0 && c->wall_clock_khz > 0)
+          d = static_cast<float>(static_cast<double>(t1 - t0) / static_cast<double>(c->wall_clock_khz));
+        sum[0] += d;
+      }
+      if (hipEventElapsedTime(&d, ev(1), ev(2)) == hipSuccess)
+        sum[1] += d;
+      if (hipEventElapsedTime(&d, ev(3), ev(4)) == hipSuccess)
+        sum[2] += d;
+      if (hipEventElapsedTime(&d, ev(4), ev(5)) == hipSuccess)
         sum[3] += d;
       ++calls;
     }
@@ -2768,18 +2692,12 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
   // (the last call's counters: when that call was beyond the ring its stream may still be busy -- wait for the scratch's own event)
   if (s->done && s->used)
     (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
-  uint32_t cnt[8 * CallScratch::MAX_PARTS] = {}, big[4] = {0, 0, 0, 0};
+  uint32_t cnt[8] = {}, big[4] = {0, 0, 0, 0};
   (void)hipMemcpy(cnt, s->d_counters, sizeof(cnt), hipMemcpyDeviceToHost);
   if (s->d_big_state)
     (void)hipMemcpy(big, s->d_big_state, sizeof(big), hipMemcpyDeviceToHost);
-  uint32_t queued2 = 0, queued1 = 0, handed = 0, direct = 0;
-  for (uint32_t p = 0; p < CallScratch::MAX_PARTS; ++p)
-  {
-    queued2 += cnt[8 * p + 2];
-    queued1 += cnt[8 * p + 3];
-    handed += cnt[8 * p + 4];
-    direct += cnt[8 * p + 5] - std::min(cnt[8 * p + 5], cnt[8 * p + 4]); // forward tasks of the general pass that did not come through pass 1
-  }
+  uint32_t const queued2 = cnt[2], queued1 = cnt[3], handed = cnt[4];
+  uint32_t const direct = cnt[5] - std::min(cnt[5], cnt[4]); // forward tasks of the general pass that did not come through pass 1
   // forward tasks only: reverse-orientation tasks all go to the general pass
   uint32_t const hbm = std::min<uint32_t>(big[0], s->big_task_cap);
   bool const hinted = ms[0] > 0.0f;

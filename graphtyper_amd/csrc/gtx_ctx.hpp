@@ -24,16 +24,16 @@ struct CallScratch
   bool used = false;         // `done` has been recorded at least once
   uint64_t use_seq = 0;      // gtx_ctx::scratch_uses at its last release (the smallest: the one whose work was queued longest ago)
   void * done = nullptr;     // hipEvent_t recorded behind the last launch that uses this scratch
-  // per part of the batch, 8 words: [0] read / queue-1 claim counter of pass 1, [1] task counter of pass 2, [2] tasks queued
-  // for pass 2, [3] forward tasks the position-hinted pass handed to pass 1, [4] forward tasks pass 1 handed to pass 2,
-  // [5] forward tasks pass 2 did (those beyond [4] came straight from the position-hinted pass); [2] and [3] are one 64-bit
-  // word for that pass' single add per workgroup
+  // 8 words: [0] read / queue-1 claim counter of pass 1, [1] task counter of pass 2, [2] tasks queued for pass 2, [3] forward
+  // tasks the position-hinted pass handed to pass 1, [4] forward tasks pass 1 handed to pass 2, [5] forward tasks pass 2 did
+  // (those beyond [4] came straight from the position-hinted pass); [2] and [3] are one 64-bit word for that pass' single add
+  // per workgroup
   uint32_t * d_counters = nullptr;
   // TWO sets of them (round 6): a call counts in the set the call before it did not use and zeroes that one, behind its last
   // launch on its last stream, for the call after it -- the reset used to be a hipMemsetAsync in FRONT of the position-hinted pass
   // on the caller's stream: a fill kernel and the gaps around it, 25 us of an idle chip per step of 0.72 ms.  d_counters and
   // the pointers into the set (d_big_state, d_wide_state, d_exact_state, d_span) name the set of the last call.
-  static constexpr uint32_t COUNTER_WORDS = 8 * 8 + 48 + 4, COUNTER_PITCH = 128; // (8 words x MAX_PARTS; big, wide, exact x 3: 8 words each; span: 2 x 64 bits)
+  static constexpr uint32_t COUNTER_WORDS = 8 + 48 + 4, COUNTER_PITCH = 64; // (the pass counters; state of the HBM-table, wide-site, exact pass: 8 + 8 + 32 words; span: 2 x 64 bits)
   uint32_t * d_counter_sets = nullptr; // [2][COUNTER_PITCH]
   uint32_t counter_set = 0;            // the set of the last call
   bool spare_set_clean = true;         // the other one is zero (false after a call that failed on its way)
@@ -44,18 +44,13 @@ struct CallScratch
   uint64_t queue1_cap = 0;
   uint32_t * d_queue = nullptr;  // (read * 2 + orientation) tasks for pass 2 (grow-only)
   uint64_t queue_cap = 0;
-  static constexpr uint32_t MAX_PARTS = 8; // parts a large batch is cut into (their general passes overlap the next part)
-  void * side_stream = nullptr;            // hipStream_t of the general / HBM-table passes when a batch has several parts
-  void * sync_events[MAX_PARTS + 1] = {};  // hipEvent_t (no timing): part p's express pass done; [MAX_PARTS]: fork / join
   // Pass times of the calls since the last gtx_ctx_kernel_times (a ring: a host that keeps several calls in flight asks
-  // once behind them).  Per call and part 6 events: around hinted, express (caller's stream), general (side stream);
-  // [0][5] = the call's end.  Created at a slot's first use.
+  // once behind them).  Per call 6 events: [0] [1] around the position-hinted pass (caller's stream), [1] [2] around the express
+  // pass, [3] [4] around the general pass, [5] the call's end (the stream of the short queues).  Created at a slot's first use.
   static constexpr uint32_t TIME_RING = 32;
-  void * time_ring[TIME_RING][MAX_PARTS][6] = {};
-  uint32_t ring_parts[TIME_RING] = {}; // parts of the call in the slot
+  void * time_ring[TIME_RING][6] = {};
   uint32_t ring_used = 0;              // calls recorded in epoch ring_epoch (the first TIME_RING of them are kept)
   uint32_t ring_epoch = 0;             // gtx_ctx::time_epoch of the slots above
-  bool timed = false;                  // the last call was timed (its slot: ring_used - 1)
   unsigned long long * d_span = nullptr; // behind d_counters: the position-hinted pass' own clock (gtx_api.hip: GTX_HINTED_PASS), reset with the counters
   unsigned long long * h_span = nullptr; // pinned, [TIME_RING][2]: the spans of the timed calls
   uint32_t timed_reads = 0;
