@@ -2422,45 +2422,95 @@ GTX_DEV bool seed_stage(Here, GraphView const & g, IndexView const & ix, WS & ws
   // -- load the read: bit planes (graph_dev.hpp; seq4 = the read's row) -> one code per byte, four bases per lane and one
   //    4-byte store: reads up to 256 bp in one pass.  The reverse orientation is the reverse complement, and complementing
   //    an IUPAC code is reversing its 4 bits (A<->T, C<->G): the forward codes go to LDS first and are turned around there.
-  static_assert(AlignCfg::MAX_READ <= 256 && AlignCfg::MAX_READ % 4 == 0, "one pass of 64 lanes x 4 bases");
-  W::lanes([&](uint32_t l) {
-    if (4 * l < len)
-    {
-      uint32_t const * gq = reinterpret_cast<uint32_t const *>(seq4) + 4u * ((4 * l) >> 5);
-      uint32_t packed = plane_codes4(gq[0], gq[1], gq[2], gq[3], (4 * l) & 31u);
-      // bases behind the read's end count as N, and so does '=' (assigned to a seqan Iupac it becomes N,
-      // hts_parallel_reader.cpp:226-243): both are zero bytes by now
-      uint32_t const inside = len - 4 * l >= 4 ? 0xFFFFFFFFu : (1u << (8 * (len - 4 * l))) - 1u;
-      packed &= inside;
-      uint32_t const zero = ~(packed | (packed >> 1) | (packed >> 2) | (packed >> 3)) & 0x01010101u;
-      packed |= zero * 15u;
-      reinterpret_cast<uint32_t *>(ws.rd)[l] = packed;
-    }
-  });
-  if (reverse)
+  static_assert(AlignCfg::MAX_READ % 4 == 0, "four bases per lane");
+  if constexpr (AlignCfg::MAX_READ <= 256)
   {
-    W::lds_sync();
-    typename W::template PerLane<uint32_t> turned;
-    W::lanes([&](uint32_t l) {
-      uint32_t packed = 0;
-      for (uint32_t k = 0; k < 4; ++k)
-      {
-        uint32_t const i = 4 * l + k;
-        uint32_t c = 15;
-        if (i < len)
-        {
-          c = ws.rd[len - 1 - i];
-          c = ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3);
-        }
-        packed |= c << (8 * k);
-      }
-      turned[l] = packed;
-    });
-    W::lds_sync();
     W::lanes([&](uint32_t l) {
       if (4 * l < len)
-        reinterpret_cast<uint32_t *>(ws.rd)[l] = turned[l];
+      {
+        uint32_t const * gq = reinterpret_cast<uint32_t const *>(seq4) + 4u * ((4 * l) >> 5);
+        uint32_t packed = plane_codes4(gq[0], gq[1], gq[2], gq[3], (4 * l) & 31u);
+        // bases behind the read's end count as N, and so does '=' (assigned to a seqan Iupac it becomes N,
+        // hts_parallel_reader.cpp:226-243): both are zero bytes by now
+        uint32_t const inside = len - 4 * l >= 4 ? 0xFFFFFFFFu : (1u << (8 * (len - 4 * l))) - 1u;
+        packed &= inside;
+        uint32_t const zero = ~(packed | (packed >> 1) | (packed >> 2) | (packed >> 3)) & 0x01010101u;
+        packed |= zero * 15u;
+        reinterpret_cast<uint32_t *>(ws.rd)[l] = packed;
+      }
     });
+    if (reverse)
+    {
+      W::lds_sync();
+      typename W::template PerLane<uint32_t> turned;
+      W::lanes([&](uint32_t l) {
+        uint32_t packed = 0;
+        for (uint32_t k = 0; k < 4; ++k)
+        {
+          uint32_t const i = 4 * l + k;
+          uint32_t c = 15;
+          if (i < len)
+          {
+            c = ws.rd[len - 1 - i];
+            c = ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3);
+          }
+          packed |= c << (8 * k);
+        }
+        turned[l] = packed;
+      });
+      W::lds_sync();
+      W::lanes([&](uint32_t l) {
+        if (4 * l < len)
+          reinterpret_cast<uint32_t *>(ws.rd)[l] = turned[l];
+      });
+    }
+  }
+  else
+  {
+    // (long-read builds, AlignCfg::MAX_READ > 256: the same in rounds of 256 bases; the reverse orientation reads the whole
+    //  forward read before any of it is overwritten)
+    constexpr uint32_t ROUNDS = (AlignCfg::MAX_READ + 255u) / 256u;
+    for (uint32_t b = 0; b < len; b += 256)
+      W::lanes([&](uint32_t l) {
+        uint32_t const p = b + 4 * l;
+        if (p < len)
+        {
+          uint32_t const * gq = reinterpret_cast<uint32_t const *>(seq4) + 4u * (p >> 5);
+          uint32_t packed = plane_codes4(gq[0], gq[1], gq[2], gq[3], p & 31u);
+          uint32_t const inside = len - p >= 4 ? 0xFFFFFFFFu : (1u << (8 * (len - p))) - 1u;
+          packed &= inside;
+          uint32_t const zero = ~(packed | (packed >> 1) | (packed >> 2) | (packed >> 3)) & 0x01010101u;
+          packed |= zero * 15u;
+          reinterpret_cast<uint32_t *>(ws.rd)[p >> 2] = packed;
+        }
+      });
+    if (reverse)
+    {
+      W::lds_sync();
+      typename W::template PerLane<uint32_t> turned[ROUNDS];
+      for (uint32_t r = 0; r < ROUNDS; ++r)
+        W::lanes([&](uint32_t l) {
+          uint32_t packed = 0;
+          for (uint32_t k = 0; k < 4; ++k)
+          {
+            uint32_t const i = 256 * r + 4 * l + k;
+            uint32_t c = 15;
+            if (i < len)
+            {
+              c = ws.rd[len - 1 - i];
+              c = ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3);
+            }
+            packed |= c << (8 * k);
+          }
+          turned[r][l] = packed;
+        });
+      W::lds_sync();
+      for (uint32_t r = 0; r < ROUNDS; ++r)
+        W::lanes([&](uint32_t l) {
+          if (256 * r + 4 * l < len)
+            reinterpret_cast<uint32_t *>(ws.rd)[64 * r + l] = turned[r][l];
+        });
+    }
   }
   GTX_LEAD ws.read_len = len;
   W::lds_sync();
@@ -2503,62 +2553,126 @@ GTX_DEV bool seed_stage(Here, GraphView const & g, IndexView const & ix, WS & ws
   //    lanes 32 + 4i + w: key w of k-mer i when it has exactly one ambiguous base (its list has 2..4 keys)
   uint32_t const kc = n_k < AlignCfg::KC ? n_k : AlignCfg::KC;
   bool const use_halves = ix.half_bucket_cap != 0;
-  static_assert(3 * AlignCfg::MAX_KMERS <= 32 && 32 + 4 * AlignCfg::MAX_KMERS <= 64, "lane map of the lookups");
-  W::lanes([&](uint32_t l) {
-    uint32_t const i = l / 3, w = l % 3;
-    if (l >= 32)
-    {
-      uint32_t const ai = (l - 32) >> 2, aw = (l - 32) & 3u;
-      if (ai < n_k && ws.nkeys0[ai] != 1)
+  static_assert(AlignCfg::MAX_KMERS > 8 || (3 * AlignCfg::MAX_KMERS <= 32 && 32 + 4 * AlignCfg::MAX_KMERS <= 64), "lane map of the lookups");
+  if constexpr (AlignCfg::MAX_KMERS <= 8)
+  {
+    W::lanes([&](uint32_t l) {
+      uint32_t const i = l / 3, w = l % 3;
+      if (l >= 32)
       {
-        uint32_t const amb = ws.off0[ai];
-        uint32_t off = 0, cnt = aw == 0 ? 0xFFFFFFFFu : 0u; // several ambiguous bases: "unknown", left to the general loop
-        if ((amb & (amb - 1u)) == 0u)
+        uint32_t const ai = (l - 32) >> 2, aw = (l - 32) & 3u;
+        if (ai < n_k && ws.nkeys0[ai] != 1)
         {
-          // list order of to_uint64_vec: the last admissible base first, then the others ascending (see the loop below)
-          uint32_t const t0 = static_cast<uint32_t>(__builtin_ctz(amb));
-          uint32_t const code = ws.rd[(K - 1) * ai + t0] & 15u;
-          uint32_t const set = (code == 0u || code == 15u) ? 15u : code;
-          cnt = 0;
-          if (aw < static_cast<uint32_t>(__builtin_popcount(set)))
+          uint32_t const amb = ws.off0[ai];
+          uint32_t off = 0, cnt = aw == 0 ? 0xFFFFFFFFu : 0u; // several ambiguous bases: "unknown", left to the general loop
+          if ((amb & (amb - 1u)) == 0u)
           {
-            uint32_t const last = 31u - static_cast<uint32_t>(__builtin_clz(set));
-            uint32_t b = last;
-            if (aw > 0)
+            // list order of to_uint64_vec: the last admissible base first, then the others ascending (see the loop below)
+            uint32_t const t0 = static_cast<uint32_t>(__builtin_ctz(amb));
+            uint32_t const code = ws.rd[(K - 1) * ai + t0] & 15u;
+            uint32_t const set = (code == 0u || code == 15u) ? 15u : code;
+            cnt = 0;
+            if (aw < static_cast<uint32_t>(__builtin_popcount(set)))
             {
-              uint32_t rest = set & ~(1u << last);
-              for (uint32_t k = 1; k < aw; ++k)
-                rest &= rest - 1u;
-              b = static_cast<uint32_t>(__builtin_ctz(rest));
+              uint32_t const last = 31u - static_cast<uint32_t>(__builtin_clz(set));
+              uint32_t b = last;
+              if (aw > 0)
+              {
+                uint32_t rest = set & ~(1u << last);
+                for (uint32_t k = 1; k < aw; ++k)
+                  rest &= rest - 1u;
+                b = static_cast<uint32_t>(__builtin_ctz(rest));
+              }
+              uint64_t const key = ws.key0[ai] | (static_cast<uint64_t>(b & 1u) << t0) | (static_cast<uint64_t>(b >> 1) << (32u + t0));
+              bucket_find(ix.slots, ix.log2_cap, key, off, cnt);
             }
-            uint64_t const key = ws.key0[ai] | (static_cast<uint64_t>(b & 1u) << t0) | (static_cast<uint64_t>(b >> 1) << (32u + t0));
-            bucket_find(ix.slots, ix.log2_cap, key, off, cnt);
           }
+          ws.aoff[ai][aw] = off;
+          ws.acnt[ai][aw] = cnt;
         }
-        ws.aoff[ai][aw] = off;
-        ws.acnt[ai][aw] = cnt;
       }
-    }
-    else if (l < 3 * n_k && ws.nkeys0[i] == 1 && (w == 0 || (i < kc && use_halves)))
-    {
-      uint64_t const q = ws.key0[i];
-      uint32_t off, cnt;
-      IndexSlot const * hit;
-      bucket_find(w == 0 ? ix.slots : ix.hslots, w == 0 ? ix.log2_cap : ix.h_log2_cap, w == 0 ? q : half_key(q, w - 1), off, cnt,
-                  &hit);
-      uint32_t * o = w == 0 ? &ws.off0[i] : &ws.hoff[i][w - 1];
-      uint32_t * c = w == 0 ? &ws.cnt0[i] : &ws.hcnt[i][w - 1];
-      *o = off;
-      *c = cnt;
-      if (cnt == 1 && i < kc)
+      else if (l < 3 * n_k && ws.nkeys0[i] == 1 && (w == 0 || (i < kc && use_halves)))
       {
-        // a single label / a single bucket entry is inline in the slot (same cache line): no second round trip
-        uint4_t const payload = *reinterpret_cast<uint4_t const *>(hit->p);
-        static_assert(sizeof(HalfEntry) == 16 && sizeof(DevLabel) == 16, "staged entries are 16-byte words");
-        *(w == 0 ? reinterpret_cast<uint4_t *>(&ws.xl[i][0]) : reinterpret_cast<uint4_t *>(&ws.he[i][w - 1][0])) = payload;
+        uint64_t const q = ws.key0[i];
+        uint32_t off, cnt;
+        IndexSlot const * hit;
+        bucket_find(w == 0 ? ix.slots : ix.hslots, w == 0 ? ix.log2_cap : ix.h_log2_cap, w == 0 ? q : half_key(q, w - 1), off, cnt,
+                    &hit);
+        uint32_t * o = w == 0 ? &ws.off0[i] : &ws.hoff[i][w - 1];
+        uint32_t * c = w == 0 ? &ws.cnt0[i] : &ws.hcnt[i][w - 1];
+        *o = off;
+        *c = cnt;
+        if (cnt == 1 && i < kc)
+        {
+          // a single label / a single bucket entry is inline in the slot (same cache line): no second round trip
+          uint4_t const payload = *reinterpret_cast<uint4_t const *>(hit->p);
+          static_assert(sizeof(HalfEntry) == 16 && sizeof(DevLabel) == 16, "staged entries are 16-byte words");
+          *(w == 0 ? reinterpret_cast<uint4_t *>(&ws.xl[i][0]) : reinterpret_cast<uint4_t *>(&ws.he[i][w - 1][0])) = payload;
+        }
       }
-    }
-  });
+    });
+  }
+  else
+  {
+    // (long-read builds, AlignCfg::MAX_KMERS > 8: the same lane map in rounds of 8 k-mers; only k-mers below KC, all in
+    //  the first round, probe their half-key buckets and stage entries)
+    for (uint32_t k0 = 0; k0 < n_k; k0 += 8)
+    W::lanes([&](uint32_t l) {
+      uint32_t const i = k0 + l / 3, w = l % 3;
+      if (l >= 32)
+      {
+        uint32_t const ai = k0 + ((l - 32) >> 2), aw = (l - 32) & 3u;
+        if (ai < n_k && ws.nkeys0[ai] != 1)
+        {
+          uint32_t const amb = ws.off0[ai];
+          uint32_t off = 0, cnt = aw == 0 ? 0xFFFFFFFFu : 0u; // several ambiguous bases: "unknown", left to the general loop
+          if ((amb & (amb - 1u)) == 0u)
+          {
+            // list order of to_uint64_vec: the last admissible base first, then the others ascending (see the loop below)
+            uint32_t const t0 = static_cast<uint32_t>(__builtin_ctz(amb));
+            uint32_t const code = ws.rd[(K - 1) * ai + t0] & 15u;
+            uint32_t const set = (code == 0u || code == 15u) ? 15u : code;
+            cnt = 0;
+            if (aw < static_cast<uint32_t>(__builtin_popcount(set)))
+            {
+              uint32_t const last = 31u - static_cast<uint32_t>(__builtin_clz(set));
+              uint32_t b = last;
+              if (aw > 0)
+              {
+                uint32_t rest = set & ~(1u << last);
+                for (uint32_t k = 1; k < aw; ++k)
+                  rest &= rest - 1u;
+                b = static_cast<uint32_t>(__builtin_ctz(rest));
+              }
+              uint64_t const key = ws.key0[ai] | (static_cast<uint64_t>(b & 1u) << t0) | (static_cast<uint64_t>(b >> 1) << (32u + t0));
+              bucket_find(ix.slots, ix.log2_cap, key, off, cnt);
+            }
+          }
+          ws.aoff[ai][aw] = off;
+          ws.acnt[ai][aw] = cnt;
+        }
+      }
+      else if (l < 24 && i < n_k && ws.nkeys0[i] == 1 && (w == 0 || (i < kc && use_halves)))
+      {
+        uint64_t const q = ws.key0[i];
+        uint32_t off, cnt;
+        IndexSlot const * hit;
+        bucket_find(w == 0 ? ix.slots : ix.hslots, w == 0 ? ix.log2_cap : ix.h_log2_cap, w == 0 ? q : half_key(q, w - 1), off, cnt,
+                    &hit);
+        uint32_t * o = w == 0 ? &ws.off0[i] : &ws.hoff[i][w - 1];
+        uint32_t * c = w == 0 ? &ws.cnt0[i] : &ws.hcnt[i][w - 1];
+        *o = off;
+        *c = cnt;
+        if (cnt == 1 && i < kc)
+        {
+          // a single label / a single bucket entry is inline in the slot (same cache line): no second round trip
+          uint4_t const payload = *reinterpret_cast<uint4_t const *>(hit->p);
+          static_assert(sizeof(HalfEntry) == 16 && sizeof(DevLabel) == 16, "staged entries are 16-byte words");
+          *(w == 0 ? reinterpret_cast<uint4_t *>(&ws.xl[i][0]) : reinterpret_cast<uint4_t *>(&ws.he[i][w - 1][0])) = payload;
+        }
+      }
+    });
+  }
   W::lds_sync();
   // -- ... and everything those lookups point at that is small enough to be staged: bucket entries and exact labels
   W::lanes([&](uint32_t l) {

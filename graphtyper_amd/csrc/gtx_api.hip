@@ -1498,7 +1498,8 @@ static void scratch_free(CallScratch & s)
 {
   // (d_big_state lies behind d_counters in one allocation: one reset for both)
   void * ptrs[] = {s.d_counter_sets, s.d_queue1, s.d_queue, s.d_big_tasks, s.d_big_ws, s.d_score_state, s.d_score_queue,
-                   s.d_score_tables, s.d_score_work, s.d_var_masks, s.d_wide_tasks, s.d_wide_ws, s.d_planes, s.d_exact_tasks};
+                   s.d_score_tables, s.d_score_work, s.d_var_masks, s.d_wide_tasks, s.d_wide_ws, s.d_planes, s.d_exact_tasks,
+                   s.d_long_state, s.d_long_tasks, s.d_long_ws};
   for (void * p : ptrs)
     if (p)
       (void)gtx::dev_free(p);
@@ -1553,6 +1554,16 @@ static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
     }
     // the exact pass: two queues (what did not fit the tables above; what did not fit a part of the slab) and the slab
     ok = ok && dev_alloc(s->d_exact_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "exact pass queues");
+    if (ok && c.params.max_read_len > GTX_MAX_READ)
+    {
+      // the long reads' passes: tier 1's workspaces (four workgroups per CU), tier 2's queues and the state words of both
+      void * lws = nullptr;
+      s->long_blocks = static_cast<uint32_t>(c.n_cu > 0 ? c.n_cu : 256) * 4u;
+      ok = ok && hip_ok(gtx::dev_malloc(&lws, static_cast<size_t>(s->long_blocks) * long_workspace_bytes()), "long-read pass workspaces");
+      s->d_long_ws = lws;
+      ok = ok && dev_alloc(s->d_long_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "long-read exact pass queues");
+      ok = ok && dev_alloc(s->d_long_state, 8 + 32, "long-read pass state", true);
+    }
     ok = ok && dev_alloc(s->d_score_state, 8, "second-pass score state", true); // (two sets of four words; [2]: the work queue's count)
     ok = ok && dev_alloc(s->d_score_queue, gtx_ctx::SCORE_QUEUE_CAP, "second-pass score queue");
     if (c.has_wide_sites)
@@ -2302,6 +2313,21 @@ static int align_front(AlignCall & a)
   return GTX_OK;
 }
 
+// the long reads' passes of a call (the scratch has them when the context's max_read_len is above GTX_MAX_READ)
+static LongPassArgs long_args(AlignCall const & a)
+{
+  LongPassArgs l;
+  l.meta = a.r.meta;
+  l.n_reads = a.r.n_reads;
+  l.max_len = max_read_len_of(a.c->params);
+  l.force_both = a.c->params.force_align_both_orientations != 0;
+  l.blocks = a.s->long_blocks;
+  l.ws = a.s->d_long_ws;
+  l.tasks = a.s->d_long_tasks;
+  l.state = a.s->d_long_state;
+  return l;
+}
+
 // the passes behind the general one: the HBM-table pass (and the wide-site pass), then the exact pass with one of the
 // context's slabs
 static int align_hbm(AlignCall & a)
@@ -2394,6 +2420,13 @@ static int align_hbm(AlignCall & a)
     uint32_t const seen_exact = c->h_big_seen ? static_cast<uint32_t volatile *>(c->h_big_seen)[2] : 0xFFFFFFFFu;
     h.exact_grid_limit = (!adaptive || c->exact_fixed_parts || seen_exact == 0xFFFFFFFFu) ? 0u : 2u * seen_exact + 4u;
     what = launch_exact_passes(h, a.sq);
+    // the long reads (gtx_params::max_read_len > GTX_MAX_READ): tier 1 over the batch, tier 2 with the same slab, behind the above
+    if (!what && s->d_long_state)
+    {
+      if (!hip_ok(hipMemsetAsync(s->d_long_state, 0, (8 + 32) * sizeof(uint32_t), a.sq), "long-read pass state"))
+        return GTX_ERR_HIP;
+      what = launch_long_passes(h, long_args(a), a.sq);
+    }
     if (!what && c->h_big_seen)
       hipLaunchKernelGGL(gtx_seen_kernel, dim3(1), dim3(64), 0, a.sq, c->h_big_seen, s->d_big_state, s->d_exact_state);
     (void)hipEventRecord(static_cast<hipEvent_t>(slot->idle), a.sq);
@@ -2419,11 +2452,20 @@ static int align_side_bytes(AlignCall & a)
     // the dense side array for what the position-hinted pass did not settle (its queue and the general pass' queue), or --
     // without that pass -- for every task
     if (a.hinted)
+    {
       // (one-wave workgroups: behind the short queues this launch stands beside the position-hinted pass of the NEXT batch, whose
       //  workgroups of two wavefronts take every pair of slots a retiring one frees -- a workgroup of four wavefronts waited for that
       //  pass' end, 130-180 us in the trace of the staggered schedule, and the scoring of this batch with it)
       hipLaunchKernelGGL(gtx_task_flags_fixup_kernel, dim3(static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256) * 16u), dim3(64), 0, a.sq, r.records,
                          r.rec_words, r.task_flags, s->d_queue1, counters + 3, s->d_queue, counters + 2, a.var_masks);
+      // (... and the long reads, which that pass left as reads it does not align)
+      if (s->d_long_state)
+        if (char const * what = launch_long_flags(long_args(a), r.records, r.rec_words, r.task_flags, a.var_masks, a.sq))
+        {
+          (void)hip_ok(hipErrorLaunchFailure, what);
+          return GTX_ERR_HIP;
+        }
+    }
     else
     {
       hipLaunchKernelGGL(gtx_task_flags_all_kernel, dim3((2u * n + 255u) / 256u), dim3(256), 0, a.sq, r.records, r.rec_words, r.task_flags, 2u * n);
@@ -3219,6 +3261,35 @@ extern "C" int gtx_ctx_exact_pass_tasks(gtx_ctx * c, uint64_t * out)
   out[1] = st[8];
   out[2] = st[16];
   out[3] = st[24] + st[3] + st[11] + st[19]; // (+ tasks a full queue dropped)
+  return GTX_OK;
+}
+
+extern "C" int gtx_ctx_long_pass_tasks(gtx_ctx * c, uint64_t * out)
+{
+  if (!c || !out)
+    return GTX_ERR_ARG;
+  for (int k = 0; k < 5; ++k)
+    out[k] = 0;
+  if (c->device < 0)
+    return GTX_ERR_NO_DEVICE;
+  CallScratch * s = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(c->pool_mutex);
+    s = c->last_align;
+  }
+  if (!s || !s->d_long_state)
+    return GTX_OK;
+  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
+    return GTX_ERR_HIP;
+  uint32_t st[8 + 32]; // tier 1's 8 words, then tier 2's 8 per launch and what the last launch handed on (as d_exact_state)
+  if (!hip_ok(hipDeviceSynchronize(), "long-read pass state") || !hip_ok(hipMemcpy(st, s->d_long_state, sizeof(st), hipMemcpyDeviceToHost), "long-read pass state"))
+    return GTX_ERR_HIP;
+  uint32_t const * x = st + 8;
+  out[0] = st[1];
+  out[1] = x[0];
+  out[2] = x[8];
+  out[3] = x[16];
+  out[4] = x[24] + x[3] + x[11] + x[19]; // (+ tasks a full queue dropped)
   return GTX_OK;
 }
 

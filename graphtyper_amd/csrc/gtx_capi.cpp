@@ -48,6 +48,11 @@ extern "C"
       g_last_error = "gtx_ctx_create: NULL argument";
       return GTX_ERR_ARG;
     }
+    if (!gtx::max_read_len_ok(*params))
+    {
+      g_last_error = "gtx_ctx_create: max_read_len must be 0 or 257 .. 1000 (GTX_MAX_READ_LONG), and 0 with no_second_pass";
+      return GTX_ERR_ARG;
+    }
     *out = nullptr;
     bool const timing = std::getenv("GTX_TIMING") != nullptr; // stage times on stderr
     auto t_last = std::chrono::steady_clock::now();
@@ -604,6 +609,11 @@ extern "C"
   {
     if (!params || !out || n_read_groups == 0)
       return GTX_ERR_ARG;
+    if (!gtx::max_read_len_ok(*params))
+    {
+      g_last_error = "gtx_stream_create: max_read_len must be 0 or 257 .. 1000 (GTX_MAX_READ_LONG), and 0 with no_second_pass";
+      return GTX_ERR_ARG;
+    }
     auto s = std::make_unique<gtx_stream>();
     s->params = *params;
     s->parked.resize(n_read_groups);
@@ -632,9 +642,10 @@ extern "C"
         g_last_error = "gtx_stream_push: read group index out of range";
         return GTX_ERR_ARG;
       }
-      if (recs[i].l_qseq > GTX_MAX_READ)
+      if (recs[i].l_qseq > gtx::max_read_len_of(s->params))
       {
-        g_last_error = "gtx_stream_push: a read of " + std::to_string(recs[i].l_qseq) + " bases (the kernels align up to 256)";
+        g_last_error = "gtx_stream_push: a read of " + std::to_string(recs[i].l_qseq) + " bases (the stream's max_read_len is " +
+                       std::to_string(gtx::max_read_len_of(s->params)) + ")";
         return GTX_ERR_UNSUPPORTED;
       }
       if ((static_cast<uint32_t>(recs[i].l_qseq) + 1u) / 2u > seq_stride || (s->plane_stride && recs[i].l_qseq > 2u * s->plane_stride))

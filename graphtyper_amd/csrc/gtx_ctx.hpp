@@ -73,6 +73,11 @@ struct CallScratch
   static constexpr uint32_t EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64; // the launch between the small parts and the whole slab
   static constexpr uint32_t EXACT_PART_SITES = 24;       // variant sites a path has room for while a task has a small part of the slab
   static constexpr uint32_t EXACT_PART_CANDIDATES = 8256; // ... and walk candidates (128 live sequences x 64 alleles + a round's slack)
+  // the long reads' passes (gtx_params::max_read_len > GTX_MAX_READ only; gtx_hbm_passes.hpp: LongPassArgs)
+  uint32_t * d_long_state = nullptr; // 8 + 32 words, zeroed by every call: tier 1's read cursor and task count, tier 2's queue states
+  uint32_t * d_long_tasks = nullptr; // tier 2's three queues of EXACT_TASK_CAP
+  void * d_long_ws = nullptr;        // long_blocks x longr::AlignWorkspace
+  uint32_t long_blocks = 0;
   // second scoring pass (items whose reads touch more variant sites than the main pass' tables hold)
   uint32_t * d_score_state = nullptr; // two sets of 4 words, used in turn ([0] items queued, [2] the work queue's count): the triage kernel of a call zeroes the other set
   uint32_t score_set = 0;
@@ -178,6 +183,13 @@ struct gtx_ctx
 namespace gtx
 {
 extern thread_local std::string g_last_error;
+// gtx_params::max_read_len: 0 (GTX_MAX_READ) or GTX_MAX_READ + 1 .. GTX_MAX_READ_LONG -- not with no_second_pass, which leaves out
+// the passes behind the general one and the long reads' passes with them
+inline bool max_read_len_ok(gtx_params const & p)
+{
+  return p.max_read_len == 0 || (p.max_read_len > GTX_MAX_READ && p.max_read_len <= GTX_MAX_READ_LONG && !p.no_second_pass);
+}
+inline uint32_t max_read_len_of(gtx_params const & p) { return p.max_read_len ? p.max_read_len : GTX_MAX_READ; }
 // gtx_scores_alloc with the block zeroed on `stream` (no wait: for a caller whose first use of the block is on that stream)
 int scores_alloc_on(gtx_ctx * c, uint32_t n_samples, uint32_t conn_cap, gtx_score_buffers * out, uint64_t * reduced_bytes, void * stream);
 // zeroes the header word of the 2 * n_reads record slots on `stream` (slots recycled from one region to the next)

@@ -1,6 +1,8 @@
 // gtx_hbm_passes.hip -- the alignment passes behind the general one: the same algorithm (align_core.inl) over tables that
 // live in HBM.  gtx_align_big_kernel (512 paths, 2 048 labels per k-mer), gtx_align_wide_kernel (allele sets of
-// GTX_WIDE_MASK_WORDS words) and the exact pass, gtx_align_exact(_wide)_kernel, whose tables have no fixed size.
+// GTX_WIDE_MASK_WORDS words) and the exact pass, gtx_align_exact(_wide)_kernel, whose tables have no fixed size.  Behind
+// them, for contexts made with gtx_params::max_read_len > GTX_MAX_READ only, the two passes of the long reads:
+// gtx_align_long_kernel and gtx_align_exact_long(_wide)_kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +11,7 @@
 #include "gtx_ctx.hpp"
 #include "wave_hip.hpp"
 #include "align_core.hpp"
+#include "align_long.hpp"
 #include "gtx_hbm_passes.hpp"
 
 namespace gtx
@@ -191,6 +194,134 @@ GTX_EXACT_PASS_KERNEL(gtx_align_exact_wide_kernel, exactw, GTX_EXACT_PASS_ATTR)
 // position-hinted pass of the next batch to end (round 6, kernel trace of the staggered schedule).  A task that does come is done, slowly.
 GTX_EXACT_PASS_KERNEL(gtx_align_exact_light_kernel, exact, __attribute__((amdgpu_waves_per_eu(4, 4))))
 GTX_EXACT_PASS_KERNEL(gtx_align_exact_wide_light_kernel, exactw, __attribute__((amdgpu_waves_per_eu(4, 4))))
+// tier 2 of the long reads: the exact pass over what gtx_align_long_kernel refused
+GTX_EXACT_PASS_KERNEL(gtx_align_exact_long_kernel, exactl, GTX_EXACT_PASS_ATTR)
+GTX_EXACT_PASS_KERNEL(gtx_align_exact_long_wide_kernel, exactlw, GTX_EXACT_PASS_ATTR)
+
+// Tier 1 of the long reads (gtx_params::max_read_len > GTX_MAX_READ): the passes in front wrote a header with
+// GTX_ST_RECORD_OVERFLOW for every read over GTX_MAX_READ bases and queued nothing for it.  This pass finds those reads
+// itself -- a wavefront claims 64 reads of the batch at a time and takes the ones of GTX_MAX_READ + 1 .. max_len bases -- so
+// that no queue bounds how many there can be, and writes both slots of each by align_read's rules, as the position-hinted
+// pass does for a short read: the reverse orientation when needs_reverse, else an empty header (none under
+// GTX_FLAG_FORWARD_ONLY).  A task that exceeds the tables goes on to tier 2 (next_tasks), as from the HBM-table pass.
+// long_state: [0] the read cursor, [1] the tasks this pass took.
+__global__ __launch_bounds__(64) GTX_HBM_PASS_ATTR void gtx_align_long_kernel(GraphView g, IndexView ix, uint8_t const * __restrict__ seq, uint32_t seq_stride,
+                                                                             gtx_read_meta const * __restrict__ meta, uint32_t n_reads, uint32_t max_len,
+                                                                             uint32_t force_both, uint32_t * __restrict__ records, uint32_t rec_words,
+                                                                             uint32_t * long_state, longr::AlignWorkspace * workspaces,
+                                                                             uint32_t * __restrict__ arena, unsigned long long arena_words,
+                                                                             unsigned long long * arena_cursor, uint32_t * __restrict__ next_tasks,
+                                                                             uint32_t next_cap, uint32_t * next_state)
+{
+  longr::AlignWorkspace & ws = workspaces[blockIdx.x];
+  __shared__ uint32_t s_pp_keys[2][longr::AlignCfg::MAXPP];
+  __shared__ uint64_t s_pp_bits[longr::AlignCfg::MAXPP / 64 + 1];
+  ws.pp_start = s_pp_keys[0];
+  ws.pp_end = s_pp_keys[1];
+  ws.bits_pp = s_pp_bits;
+  WaveHipMem::mem_sync();
+  uint32_t const lane = threadIdx.x & 63u;
+  uint32_t n_tasks = 0;
+  // one task: the body of GTX_HBM_PASS_BODY
+  auto task_of = [&](uint32_t task, uint32_t len)
+  {
+    uint32_t const read = task >> 1, orient = task & 1u;
+    uint32_t * rec = records + static_cast<uint64_t>(task) * rec_words;
+    uint32_t np = 0, longest = 0, ext = 0;
+    uint32_t status =
+      longr::align_paths<WaveHipMem>(g, ix, ws, seq + static_cast<uint64_t>(read) * seq_stride, len, orient == 1, np, longest);
+    status = WaveHip::uni(status);
+    np = WaveHip::uni(np);
+    longest = WaveHip::uni(longest);
+    if (status && lane == 0) // a table overflowed, or an allele >= 64: tier 2
+    {
+      uint32_t const slot = atomicAdd(next_state, 1u);
+      if (slot < next_cap)
+        next_tasks[slot] = task;
+      else
+        atomicAdd(next_state + 3, 1u);
+    }
+    status &= ~GTX_ST_WIDE_ALLELE;
+    uint32_t * body = rec + 2;
+    unsigned long long off = 0;
+    if (status)
+      np = 0;
+    else
+    {
+      uint32_t const size = WaveHip::uni(longr::record_size<WaveHipMem>(longr::Here{}, ws, np));
+      if (size > rec_words)
+      {
+        off = wave_claim64(arena_cursor, size - 2);
+        if (off + (size - 2) > arena_words || off + (size - 2) > 0xFFFFFFFFull)
+        {
+          status = GTX_ST_RECORD_OVERFLOW;
+          np = 0;
+        }
+        else
+        {
+          body = arena + off;
+          ext = GTX_ST_EXTERNAL;
+        }
+      }
+    }
+    uint32_t const has_var = longr::write_record_body<WaveHipMem>(longr::Here{}, ws, np, body);
+    if (lane == 0)
+    {
+      rec[0] = np | ((status | ext) << 16);
+      rec[1] = (np == 0 ? 0 : longest) | (len << 16) | (np == 0 ? 0u : has_var);
+      if (ext)
+        rec[2] = static_cast<uint32_t>(off);
+    }
+    WaveHipMem::mem_sync();
+    ++n_tasks;
+  };
+  for (;;)
+  {
+    uint32_t const first = wave_claim(long_state, 64u);
+    if (first >= n_reads)
+      break;
+    uint32_t const len_l = first + lane < n_reads ? static_cast<uint32_t>(meta[first + lane].l_qseq) : 0u;
+    unsigned long long todo = __ballot(len_l > GTX_MAX_READ && len_l <= max_len);
+    while (todo)
+    {
+      uint32_t const read = first + static_cast<uint32_t>(__builtin_ctzll(todo));
+      todo &= todo - 1ull;
+      gtx_read_meta const m = meta[read];
+      uint32_t const len = WaveHip::uni(static_cast<uint32_t>(m.l_qseq));
+      bool const rev = WaveHip::uni(static_cast<uint32_t>(needs_reverse(m, force_both != 0))) != 0u;
+      task_of(2u * read, len);
+      if (rev)
+        task_of(2u * read + 1u, len);
+      else if ((m.flag & GTX_FLAG_FORWARD_ONLY) == 0 && lane == 0)
+      {
+        uint32_t * rec = records + (2ull * read + 1ull) * rec_words;
+        rec[0] = 0;
+        rec[1] = len << 16;
+      }
+    }
+  }
+  if (n_tasks && lane == 0)
+    atomicAdd(long_state + 1, n_tasks);
+}
+
+// The side bytes of the long reads (gtx_align_batch_*_flags / _triaged behind the position-hinted pass, which left them as
+// for a read it does not align): the final records' GTX_TASK_HAS_VARIANTS bits, and the read's bit of the variant masks
+__global__ __launch_bounds__(256) void gtx_long_flags_kernel(gtx_read_meta const * __restrict__ meta, uint32_t n_reads, uint32_t max_len,
+                                                            uint32_t force_both, uint32_t const * __restrict__ records, uint32_t rec_words,
+                                                            uint8_t * __restrict__ task_flags, unsigned long long * __restrict__ var_mask)
+{
+  for (uint32_t read = blockIdx.x * blockDim.x + threadIdx.x; read < n_reads; read += gridDim.x * blockDim.x)
+  {
+    gtx_read_meta const m = meta[read];
+    if (m.l_qseq <= GTX_MAX_READ || m.l_qseq > max_len)
+      continue;
+    uint8_t const f = static_cast<uint8_t>(records[2ull * read * rec_words + 1] >> 31);
+    task_flags[2ull * read] = f;
+    task_flags[2ull * read + 1] = needs_reverse(m, force_both != 0) ? static_cast<uint8_t>(records[(2ull * read + 1) * rec_words + 1] >> 31) : 0u;
+    if (var_mask && f != 0)
+      atomicOr(var_mask + (read >> 6), 1ull << (read & 63u));
+  }
+}
 
 
 uint64_t big_workspace_bytes() { return sizeof(big::AlignWorkspace); }
@@ -217,7 +348,11 @@ char const * launch_hbm_passes(HbmPassArgs const & a, hipStream_t stream)
   return nullptr;
 }
 
-char const * launch_exact_passes(HbmPassArgs const & a, hipStream_t stream)
+// The three launches of an exact pass over the queues q1, q1 + EXACT_TASK_CAP, q1 + 2 EXACT_TASK_CAP and the 4 x 8 state words
+// st1: the short reads' (launch_exact_passes) and the long reads' tier 2 (launch_long_passes)
+template <class Kernel>
+static char const * exact_launches(HbmPassArgs const & a, Kernel kernel, bool light, uint32_t * q1, uint32_t * st1, uint32_t max_sites, char const * what,
+                                   hipStream_t stream)
 {
   unsigned long long const arena_words = a.arena_words;
   // the exact pass: what exceeded the tables above, with a small part of the slab per task (up to exact_parts of them side by
@@ -226,12 +361,8 @@ char const * launch_exact_passes(HbmPassArgs const & a, hipStream_t stream)
   // (a small part's paths have room for EXACT_PART_SITES variant sites and its walks for exact_part_cand_cap candidates, a large
   //  part's for EXACT_LARGE_SITES, the whole slab for the proven bounds: a site per read base, 128 live sequences times the alleles
   //  of the graph's widest site)
-  uint32_t * const q1 = a.exact_tasks, * const q2 = q1 + CallScratch::EXACT_TASK_CAP, * const q3 = q2 + CallScratch::EXACT_TASK_CAP;
-  uint32_t * const st1 = a.exact_state, * const st2 = st1 + 8, * const st3 = st2 + 8, * const st4 = st3 + 8;
-  // (nothing expected -- the batch before sent no task here: the build that can be placed beside a full chip, four workgroups a launch)
-  bool const light = a.exact_grid_limit != 0 && a.exact_grid_limit <= 4u;
-  auto kernel = light ? (a.wide_sites ? gtx_align_exact_wide_light_kernel : gtx_align_exact_light_kernel)
-                      : (a.wide_sites ? gtx_align_exact_wide_kernel : gtx_align_exact_kernel);
+  uint32_t * const q2 = q1 + CallScratch::EXACT_TASK_CAP, * const q3 = q2 + CallScratch::EXACT_TASK_CAP;
+  uint32_t * const st2 = st1 + 8, * const st3 = st2 + 8, * const st4 = st3 + 8;
   uint32_t const lds_keys = light ? 256u : EXACT_LDS_KEYS;
   size_t const lds_bytes = 2u * lds_keys * sizeof(uint32_t);
   unsigned long long const slab_bytes = a.exact_slab_bytes, min_part = slab_bytes / a.exact_parts;
@@ -257,9 +388,46 @@ char const * launch_exact_passes(HbmPassArgs const & a, hipStream_t stream)
                      CallScratch::EXACT_LARGE_SITES, a.arena, arena_words, a.arena_cursor, q3, CallScratch::EXACT_TASK_CAP, st3, lds_keys);
   // (what even the whole slab cannot hold is counted in st4: a queue of capacity 0)
   hipLaunchKernelGGL(kernel, dim3(1), dim3(64), lds_bytes, stream, a.g, a.ix, a.seq, a.seq_stride, a.meta, a.records, a.rec_words, q3, CallScratch::EXACT_TASK_CAP,
-                     st3, a.exact_slab, slab_bytes, 0ull, 0u, a.exact_cand_cap, exact::AlignCfg::MAXV, a.arena, arena_words, a.arena_cursor, q3, 0u, st4, lds_keys);
+                     st3, a.exact_slab, slab_bytes, 0ull, 0u, a.exact_cand_cap, max_sites, a.arena, arena_words, a.arena_cursor, q3, 0u, st4, lds_keys);
   if (hipGetLastError() != hipSuccess)
-    return "gtx_align_exact_kernel launch";
+    return what;
   return nullptr;
+}
+
+char const * launch_exact_passes(HbmPassArgs const & a, hipStream_t stream)
+{
+  // (nothing expected -- the batch before sent no task here: the build that can be placed beside a full chip, four workgroups a launch)
+  bool const light = a.exact_grid_limit != 0 && a.exact_grid_limit <= 4u;
+  auto kernel = light ? (a.wide_sites ? gtx_align_exact_wide_light_kernel : gtx_align_exact_light_kernel)
+                      : (a.wide_sites ? gtx_align_exact_wide_kernel : gtx_align_exact_kernel);
+  return exact_launches(a, kernel, light, a.exact_tasks, a.exact_state, exact::AlignCfg::MAXV, "gtx_align_exact_kernel launch", stream);
+}
+
+uint64_t long_workspace_bytes() { return sizeof(longr::AlignWorkspace); }
+
+char const * launch_long_passes(HbmPassArgs const & a, LongPassArgs const & l, hipStream_t stream)
+{
+  uint32_t * const st1 = l.state + 8; // (the exact launches' 4 x 8 words behind the cursor's 8)
+  HbmPassArgs b = a;
+  b.exact_grid_limit = 0; // (the short reads' grid limit says nothing about the long ones)
+  hipLaunchKernelGGL(gtx_align_long_kernel, dim3(l.blocks), dim3(64), 0, stream, a.g, a.ix, a.seq, a.seq_stride, a.meta, l.n_reads, l.max_len,
+                     l.force_both ? 1u : 0u, a.records, a.rec_words, l.state, static_cast<longr::AlignWorkspace *>(l.ws), a.arena,
+                     static_cast<unsigned long long>(a.arena_words), a.arena_cursor, l.tasks, CallScratch::EXACT_TASK_CAP, st1);
+  if (hipGetLastError() != hipSuccess)
+    return "gtx_align_long_kernel launch";
+  // (wide allele sets: a path with room for all 1 000 sites of a long read is 320 KB, and the whole slab would hold too few of
+  //  them for the label lists of a site with thousands of alleles -- its paths get room for GTX_MAX_READ sites, as in exactw)
+  return a.wide_sites ? exact_launches(b, gtx_align_exact_long_wide_kernel, false, l.tasks, st1, GTX_MAX_READ,
+                                       "gtx_align_exact_long_wide_kernel launch", stream)
+                      : exact_launches(b, gtx_align_exact_long_kernel, false, l.tasks, st1, exactl::AlignCfg::MAXV,
+                                       "gtx_align_exact_long_kernel launch", stream);
+}
+
+char const * launch_long_flags(LongPassArgs const & l, uint32_t const * records, uint32_t rec_words, uint8_t * task_flags,
+                               unsigned long long * var_mask, hipStream_t stream)
+{
+  hipLaunchKernelGGL(gtx_long_flags_kernel, dim3(std::min<uint32_t>((l.n_reads + 255u) / 256u, 4096u)), dim3(256), 0, stream, l.meta, l.n_reads,
+                     l.max_len, l.force_both ? 1u : 0u, records, rec_words, task_flags, var_mask);
+  return hipGetLastError() != hipSuccess ? "gtx_long_flags_kernel launch" : nullptr;
 }
 } // namespace gtx

@@ -55,4 +55,24 @@ char const * launch_exact_passes(HbmPassArgs const & a, hipStream_t stream);
 // bytes of one workspace of the HBM-table / wide-site pass
 uint64_t big_workspace_bytes();
 uint64_t wide_workspace_bytes();
+
+// The long reads' passes (gtx_params::max_read_len > GTX_MAX_READ): tier 1, gtx_align_long_kernel, over the batch's reads of
+// GTX_MAX_READ + 1 .. max_len bases, then tier 2, the three launches of the exact pass over what tier 1 refused -- with the slab,
+// arena and graph of the HbmPassArgs, behind launch_exact_passes on the same stream
+struct LongPassArgs
+{
+  gtx_read_meta const * meta;
+  uint32_t n_reads;
+  uint32_t max_len;
+  bool force_both;
+  uint32_t blocks;  // workgroups (= workspaces) of tier 1
+  void * ws;        // blocks x longr::AlignWorkspace
+  uint32_t * tasks; // tier 2's three queues of CallScratch::EXACT_TASK_CAP
+  uint32_t * state; // 8 words (tier 1: [0] the read cursor, [1] its tasks), then tier 2's 4 x 8 (as HbmPassArgs::exact_state), zeroed
+};
+char const * launch_long_passes(HbmPassArgs const & a, LongPassArgs const & l, hipStream_t stream);
+// the side bytes (and variant masks) of the long reads from their final records, behind the position-hinted pass' own
+char const * launch_long_flags(LongPassArgs const & l, uint32_t const * records, uint32_t rec_words, uint8_t * task_flags,
+                               unsigned long long * var_mask, hipStream_t stream);
+uint64_t long_workspace_bytes();
 } // namespace gtx

@@ -22,7 +22,7 @@ ST_ERROR_MASK = 15
 # names every build of libgtx.so must export (checked by tests/test_abi.py against include/gtx.h)
 EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy", "gtx_ctx_special_positions",
            "gtx_ctx_score_layout", "gtx_ctx_haplotypes", "gtx_ctx_near_pairs", "gtx_index_stats", "gtx_index_get", "gtx_index_dump", "gtx_ctx_hint_table",
-           "gtx_align_batch", "gtx_score_batch", "gtx_calls_batch", "gtx_ctx_big_records", "gtx_ctx_big_records_rewind", "gtx_ctx_exact_pass_tasks", "gtx_graph_sv_table", "gtx_ctx_pass_times", "gtx_ctx_error_count", "gtx_ctx_profile", "gtx_ctx_profile_log", "gtx_records_failed", "gtx_vcf_sites", "gtx_vcf_records_final", "gtx_align_batch_planes_compact", "gtx_score_batch_compact", "gtx_align_batch_planes_triaged", "gtx_score_batch_queued", "gtx_scores_replay_compact", "gtx_scores_replay_log", "gtx_scores_replay_apply", "gtx_scores_finalize", "gtx_phase_flags", "gtx_stream_create",
+           "gtx_align_batch", "gtx_score_batch", "gtx_calls_batch", "gtx_ctx_big_records", "gtx_ctx_big_records_rewind", "gtx_ctx_exact_pass_tasks", "gtx_ctx_long_pass_tasks", "gtx_graph_sv_table", "gtx_ctx_pass_times", "gtx_ctx_error_count", "gtx_ctx_profile", "gtx_ctx_profile_log", "gtx_records_failed", "gtx_vcf_sites", "gtx_vcf_records_final", "gtx_align_batch_planes_compact", "gtx_score_batch_compact", "gtx_align_batch_planes_triaged", "gtx_score_batch_queued", "gtx_scores_replay_compact", "gtx_scores_replay_log", "gtx_scores_replay_apply", "gtx_scores_finalize", "gtx_phase_flags", "gtx_stream_create",
            "gtx_stream_destroy", "gtx_stream_push", "gtx_stream_set_coverage", "gtx_stream_finish", "gtx_stream_counts", "gtx_graph_build", "gtx_graph_from_files", "gtx_graph_get_view",
            "gtx_graph_destroy",
            "gtx_scores_alloc", "gtx_scores_zero", "gtx_scores_free", "gtx_scores_reduce", "gtx_comm_unique_id", "gtx_comm_init_rank",
@@ -69,7 +69,7 @@ class Params(C.Structure):
     _fields_ = [("max_index_labels", C.c_int32), ("is_sv_graph", C.c_int32), ("hq_reads", C.c_int32),
                 ("force_align_both_orientations", C.c_int32), ("is_segment_calling", C.c_int32),
                 ("sam_flag_filter", C.c_int32), ("no_second_pass", C.c_int32), ("big_record_words", C.c_uint32),
-                ("exact_pass_mb", C.c_uint32)]
+                ("exact_pass_mb", C.c_uint32), ("max_read_len", C.c_uint32)]
 
 
 class ScoreLayout(C.Structure):
@@ -161,6 +161,7 @@ def lib():
                                           C.POINTER(C.c_uint64)]
         L.gtx_ctx_big_records_rewind.argtypes = [C.c_void_p, C.c_void_p]
         L.gtx_ctx_exact_pass_tasks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.gtx_ctx_long_pass_tasks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.gtx_graph_sv_table.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_ctx_pass_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
         L.gtx_ctx_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
@@ -651,7 +652,8 @@ class Context:
     """gtx_ctx: flat graph + index (host) and, for device >= 0, their copies in HBM"""
 
     def __init__(self, graph, device=0, max_index_labels=75, is_sv_graph=False, hq_reads=False, force_both=False,
-                 is_segment_calling=False, sam_flag_filter=3840, no_second_pass=False, big_record_words=0, exact_pass_mb=0):
+                 is_segment_calling=False, sam_flag_filter=3840, no_second_pass=False, big_record_words=0, exact_pass_mb=0,
+                 max_read_len=0):
         L = lib()
         self.g = {k: np.ascontiguousarray(v) for k, v in graph.items()}
         g = self.g
@@ -661,7 +663,7 @@ class Context:
                               _p(g["var_len"]), _p(g["var_dna_off"]), _p(g["var_out_ref"]), _p(g["dna"]), len(g["dna"]),
                               _p(g["event_off"]) if has_ev else None, _p(g["event_val"]) if has_ev else None)
         self.params = Params(max_index_labels, int(is_sv_graph), int(hq_reads), int(force_both), int(is_segment_calling),
-                             sam_flag_filter, int(no_second_pass), int(big_record_words), int(exact_pass_mb))
+                             sam_flag_filter, int(no_second_pass), int(big_record_words), int(exact_pass_mb), int(max_read_len))
         h = C.c_void_p()
         check(L.gtx_ctx_create(C.byref(self.view), C.byref(self.params), device, C.byref(h)))
         self.h = h
@@ -752,6 +754,13 @@ class Context:
         out = (C.c_uint64 * 4)()
         check(lib().gtx_ctx_exact_pass_tasks(self.h, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def long_pass_tasks(self):
+        """(tasks of the last align batch that the long reads' tier 1 took, that went on to tier 2 with a small part of the exact
+        pass' slab, again with a large part, again with the whole slab, tasks that keep a table-overflow status even so)"""
+        out = (C.c_uint64 * 5)()
+        check(lib().gtx_ctx_long_pass_tasks(self.h, out))
+        return tuple(int(x) for x in out)
 
     def pass_times(self):
         """(ms of the express / general / HBM-table pass of the last align batch, tasks handed to the general pass);

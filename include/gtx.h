@@ -159,6 +159,10 @@ typedef struct gtx_params
   uint32_t exact_pass_mb;                /* MiB of HBM per slab of the exact alignment pass, of which a context makes one per batch in flight, up to four (gtx_align_batch: the
                                           * pass whose tables have no fixed size), 0 = the GTX_EXACT_PASS_MB environment
                                           * variable, else 2048 (4096 for a graph with a site of more than 64 alleles): up to 1 024 tasks of a repeat side by side */
+  uint32_t max_read_len;                 /* longest read a context aligns and a stream accepts: 0 = GTX_MAX_READ (256); GTX_MAX_READ + 1 ..
+                                          * GTX_MAX_READ_LONG turns on the long-read passes (any other value, or any non-zero one
+                                          * with no_second_pass: GTX_ERR_ARG).  Cost: every batch in flight holds 4 x (CUs) workspaces
+                                          * of ~1 MB for them (~1.1 GB on 256 CUs) and 12 MB of queues */
 } gtx_params;
 
 /* One KmerLabel (include/graphtyper/index/kmer_label.hpp:13-41) */
@@ -167,10 +171,20 @@ typedef struct gtx_label
   uint32_t start_index, end_index, variant_id;
 } gtx_label;
 
-/* Longest read the kernels align (the reference has no limit; its MAX_READ_LENGTH constant, constants.hpp.in:27, is 151).
- * A longer read gets empty records carrying GTX_ST_RECORD_OVERFLOW in every pass, and gtx_stream_push refuses a batch
- * that holds one (GTX_ERR_UNSUPPORTED) instead of letting it vanish from the accumulators. */
+/* Longest read the kernels align by default (the reference has no limit; its MAX_READ_LENGTH constant, constants.hpp.in:27,
+ * is 151).  A longer read gets empty records carrying GTX_ST_RECORD_OVERFLOW in every pass, and gtx_stream_push refuses a
+ * batch that holds one (GTX_ERR_UNSUPPORTED) instead of letting it vanish from the accumulators.  A context or stream made
+ * with gtx_params::max_read_len above GTX_MAX_READ aligns reads up to that length instead: every align entry point runs two
+ * further passes over the batch's reads of GTX_MAX_READ + 1 .. max_read_len bases behind the exact pass (an HBM-table pass
+ * that takes them straight from the batch, then an exact pass for what it refuses), and those reads get the records
+ * gtx_align_batch gives any read -- never compact ones (gtx_align_batch_planes_compact).  Reads longer than max_read_len
+ * keep GTX_ST_RECORD_OVERFLOW.  The first pass takes any number of long reads; its hand-over to the exact pass holds 1 Mi
+ * tasks per batch (CallScratch::EXACT_TASK_CAP, as for short reads): a batch with more long tasks than that which exceed the
+ * first pass' tables leaves the rest with a table-overflow status (counted in gtx_ctx_long_pass_tasks' out[4]).  gtx_pipeline_run (80-byte plane rows: reads up to 160 bases) and gtx_regions_run make no
+ * promise for long reads. */
 #define GTX_MAX_READ 256
+/* Largest gtx_params::max_read_len: 1 + (1000 - 32) / 31 = 32 k-mers per read, plane rows of 1 024 bases (512 bytes) */
+#define GTX_MAX_READ_LONG 1000
 
 /* Per read fields of bam1_t the path looks at (src/typer/alignment.cpp:331-363) */
 typedef struct gtx_read_meta
@@ -454,6 +468,13 @@ int gtx_ctx_big_records(gtx_ctx *, const uint32_t ** d_words, uint64_t * capacit
  * again with a large part, out[2] again with the whole slab, out[3] = tasks that keep a table-overflow status even so
  * (synchronises with the device) */
 int gtx_ctx_exact_pass_tasks(gtx_ctx *, uint64_t * out /* [4] */);
+
+/* The long reads' passes of the last align call of a context made with gtx_params::max_read_len > GTX_MAX_READ: out[0] =
+ * (read, orientation) tasks of tier 1 (the HBM-table pass over the batch's reads of GTX_MAX_READ + 1 .. max_read_len bases),
+ * out[1] = tasks tier 1 handed to tier 2 (the exact pass, a small part of the slab), out[2] again with a large part, out[3]
+ * again with the whole slab, out[4] = tasks that keep a table-overflow status even so.  All zero for any other context
+ * (synchronises with the device). */
+int gtx_ctx_long_pass_tasks(gtx_ctx *, uint64_t * out /* [5] */);
 
 /* Durations (ms, HIP events on the launch stream) of the passes of gtx_align_batch -- everything in front of the general
  * pass (position-hinted + express), general, HBM tables -- and the number of tasks handed to the general pass.  The
