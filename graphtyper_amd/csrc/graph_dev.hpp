@@ -124,6 +124,46 @@ GTX_HDI void planes_from_nibbles(uint8_t const * nib, uint32_t nib_bytes, uint32
   }
 }
 
+// ---- packed 2-bit rows with an exception list (gtx.h: gtx_pack_2bit).  A row of S bytes (S a multiple of 8) is S / 8 groups
+// of 32 bases, two words per group: word 2g the low and word 2g + 1 the high bit of the 2-bit codes (A0 C1 G2 T3) of bases
+// 32g .. 32g+31, base 32g + j at bit j.  Every base whose BAM code is not exactly A, C, G or T holds 00 there and has an entry
+// (base index | code << 12) in the read's sorted run of the exception list.
+constexpr uint32_t PACKED_GROUP_BYTES = 8;
+constexpr uint32_t PACKED_EXC_INDEX_BITS = 12;
+
+// the run of read `read`'s entries in d_exc: [*b, *e), offsets from exc_start[0], each clamped to n_exc; a decreasing run is
+// empty.  No index it gives can leave an exception list of n_exc entries.
+GTX_HDI void packed_exc_run(uint32_t const * exc_start, uint32_t read, uint32_t n_exc, uint32_t * b, uint32_t * e)
+{
+  uint32_t const base = exc_start[0];
+  uint32_t lo = exc_start[read] - base, hi = exc_start[read + 1] - base;
+  lo = lo < n_exc ? lo : n_exc;
+  hi = hi < n_exc ? hi : n_exc;
+  *b = lo;
+  *e = hi > lo ? hi : lo;
+}
+
+// one group of a packed row (lo, hi: its two words) and the read's exception run exc[b .. e) -> the four plane words of the
+// group; entries of other groups are skipped
+GTX_HDI void planes_from_packed(uint32_t lo, uint32_t hi, uint16_t const * exc, uint32_t b, uint32_t e, uint32_t grp, uint32_t (&out)[4])
+{
+  out[0] = ~lo & ~hi;
+  out[1] = lo & ~hi;
+  out[2] = ~lo & hi;
+  out[3] = lo & hi;
+  for (uint32_t k = b; k < e; ++k)
+  {
+    uint32_t const x = exc[k], at = x & ((1u << PACKED_EXC_INDEX_BITS) - 1u), code = x >> PACKED_EXC_INDEX_BITS;
+    if ((at >> 5) != grp)
+      continue;
+    uint32_t const bit = 1u << (at & 31u);
+    out[0] = (out[0] & ~bit) | ((code & 1u) ? bit : 0u);
+    out[1] = (out[1] & ~bit) | ((code & 2u) ? bit : 0u);
+    out[2] = (out[2] & ~bit) | ((code & 4u) ? bit : 0u);
+    out[3] = (out[3] & ~bit) | ((code & 8u) ? bit : 0u);
+  }
+}
+
 // internal status bit (never stored in a record): the task met an allele number beyond the allele sets of the pass it was
 // in; together with GTX_ST_PATH_OVERFLOW it sends the task on, in the end to the pass with GTX_WIDE_MASK_WORDS-word sets
 constexpr uint32_t GTX_ST_WIDE_ALLELE = 32u;

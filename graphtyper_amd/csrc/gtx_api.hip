@@ -1034,6 +1034,29 @@ __global__ __launch_bounds__(256) void gtx_planes_kernel(uint8_t const * __restr
   reinterpret_cast<uint4_t *>(planes)[t] = uint4_t{o[0], o[1], o[2], o[3]};
 }
 
+// Packed 2-bit rows + exception list -> plane rows (graph_dev.hpp: planes_from_packed), one thread per (read, group of 32
+// bases): adjacent threads load adjacent 8-byte words and store 16-byte plane groups.  A thread walks its own read's run of the
+// exception list and applies the entries of its group.  Every index into exc is clamped to n_exc (packed_exc_run), so a
+// malformed list yields wrong bases, never an access outside it.  Plane groups behind the packed row are written as zeros.
+__global__ __launch_bounds__(256) void gtx_packed_kernel(uint8_t const * __restrict__ packed, uint32_t packed_stride, uint32_t const * __restrict__ exc_start,
+                                                         uint16_t const * __restrict__ exc, uint32_t n_exc, uint32_t n_reads,
+                                                         uint32_t * __restrict__ planes, uint32_t groups)
+{
+  uint64_t const t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= static_cast<uint64_t>(n_reads) * groups)
+    return;
+  uint32_t const read = static_cast<uint32_t>(t / groups), grp = static_cast<uint32_t>(t % groups);
+  uint32_t o[4] = {0, 0, 0, 0};
+  if (PACKED_GROUP_BYTES * (grp + 1) <= packed_stride)
+  {
+    uint2 const v = reinterpret_cast<uint2 const *>(packed + static_cast<uint64_t>(read) * packed_stride)[grp];
+    uint32_t b, e;
+    packed_exc_run(exc_start, read, n_exc, &b, &e);
+    planes_from_packed(v.x, v.y, exc, b, e, grp, o);
+  }
+  reinterpret_cast<uint4_t *>(planes)[t] = uint4_t{o[0], o[1], o[2], o[3]};
+}
+
 // Scoring, stage 1 (triage): one thread per item reads the record header(s) and decides whether the item can add
 // anything; 85 % of the cfg2 items cannot and end here.  No per-thread tables, so this kernel runs at full occupancy.
 // The others are appended to a work queue, one atomic per wavefront.
@@ -2037,6 +2060,60 @@ extern "C" int gtx_reads_to_planes(gtx_ctx * c, const uint8_t * d_seq, uint32_t 
   return launch_planes_kernel(d_seq, seq_stride, n_reads, d_planes, plane_stride, static_cast<hipStream_t>(stream));
 }
 
+static int launch_packed_kernel(const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start, const uint16_t * d_exc,
+                                uint32_t n_exc, uint32_t n_reads, uint8_t * d_planes, uint32_t plane_stride, hipStream_t st)
+{
+  uint32_t const groups = plane_stride / PLANE_GROUP_BYTES;
+  uint64_t const threads = static_cast<uint64_t>(n_reads) * groups;
+  if (threads == 0)
+    return GTX_OK;
+  if (threads > 0xFFFFFFFFull * 256ull)
+  {
+    g_last_error = "gtx_packed_to_planes: batch too large";
+    return GTX_ERR_ARG;
+  }
+  hipLaunchKernelGGL(gtx_packed_kernel, dim3(static_cast<uint32_t>((threads + 255u) / 256u)), dim3(256), 0, st, d_packed, packed_stride, d_exc_start,
+                     d_exc, n_exc, n_reads, reinterpret_cast<uint32_t *>(d_planes), groups);
+  return hip_ok(hipGetLastError(), "gtx_packed_kernel launch") ? GTX_OK : GTX_ERR_HIP;
+}
+
+// the argument checks of every entry point over packed rows (the exception list: n_reads + 1 starts, n_exc entries)
+static bool packed_args_ok(const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start, const uint16_t * d_exc,
+                           uint32_t n_exc, uint32_t n_reads)
+{
+  if (packed_stride == 0 || (packed_stride % PACKED_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(d_packed) & 7u) != 0 ||
+      (n_exc != 0 && !d_exc) || (reinterpret_cast<uintptr_t>(d_exc_start) & 3u) != 0 || (reinterpret_cast<uintptr_t>(d_exc) & 1u) != 0 ||
+      (n_reads != 0 && (!d_packed || !d_exc_start)))
+  {
+    g_last_error = "packed rows: bad argument (rows are 8-byte groups at an 8-byte aligned address; exc_start holds n_reads + 1 offsets; "
+                   "exc may be NULL only when n_exc is 0)";
+    return false;
+  }
+  return true;
+}
+
+extern "C" int gtx_packed_to_planes(gtx_ctx * c, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start,
+                                    const uint16_t * d_exc, uint32_t n_exc, uint32_t n_reads, uint8_t * d_planes, uint32_t plane_stride,
+                                    void * stream)
+{
+  if (!c || plane_stride == 0 || (plane_stride % PLANE_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(d_planes) & 15u) != 0 ||
+      (n_reads != 0 && !d_planes))
+  {
+    g_last_error = "gtx_packed_to_planes: bad argument (plane rows are 16-byte groups at a 16-byte aligned address)";
+    return GTX_ERR_ARG;
+  }
+  if (!packed_args_ok(d_packed, packed_stride, d_exc_start, d_exc, n_exc, n_reads))
+    return GTX_ERR_ARG;
+  if (c->device < 0)
+  {
+    g_last_error = "context was created without a device (libgtx has no CPU path)";
+    return GTX_ERR_NO_DEVICE;
+  }
+  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
+    return GTX_ERR_HIP;
+  return launch_packed_kernel(d_packed, packed_stride, d_exc_start, d_exc, n_exc, n_reads, d_planes, plane_stride, static_cast<hipStream_t>(stream));
+}
+
 // the slab a call's exact launches use (gtx_ctx::exact_slot); c.exact_mutex is held by the caller.  *wait: the call's stream has
 // to wait for the slab's event first (every slab is busy)
 // The slab a call of `n_reads` reads gets.  A large batch (a whole region's reads of a sample: HBM_SMALL_BATCH and more) gets the
@@ -2098,10 +2175,18 @@ struct TriageRequest
   bool items_are_reads; // GTX_TRIAGE_ITEMS_ARE_READS: item i is read i, alone and aligned forward only
 };
 
-// One align call as the six align entry points hand it on, after their argument checks (align_call)
+// the exception list that goes with packed rows (gtx_align_batch_packed)
+struct PackedInput
+{
+  uint32_t const * exc_start; // n_reads + 1 offsets from exc_start[0]
+  uint16_t const * exc;
+  uint32_t n_exc;
+};
+
+// One align call as the eight align entry points hand it on, after their argument checks (align_call)
 struct AlignRequest
 {
-  uint8_t const * seq; // plane rows -- or, with `nibbles`, BAM nibble rows (seq_stride: their pitch)
+  uint8_t const * seq; // plane rows -- or, with `nibbles`, BAM nibble rows, or with `packed`, packed rows (seq_stride: their pitch)
   uint32_t seq_stride;
   gtx_read_meta const * meta;
   uint32_t n_reads;
@@ -2115,6 +2200,7 @@ struct AlignRequest
   uint32_t * compact = nullptr;
   TriageRequest const * triage = nullptr;
   bool nibbles = false; // gtx_align_batch[_flags]: repacked into plane rows in the call's scratch first
+  PackedInput const * packed = nullptr; // gtx_align_batch_packed[_staged]: unpacked into plane rows in the call's scratch first
 };
 
 // What the steps of one align call share; they run in launch order: align_setup, align_front, align_hbm, align_side_bytes,
@@ -2518,7 +2604,7 @@ static void align_end(AlignCall & a)
     ++s->ring_used;
 }
 
-// The one way into the alignment passes, behind the argument checks of the six align entry points
+// The one way into the alignment passes, behind the argument checks of the eight align entry points
 static int align_call(gtx_ctx * c, AlignRequest r)
 {
   if (c->device < 0)
@@ -2557,6 +2643,18 @@ static int align_call(gtx_ctx * c, AlignRequest r)
     if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(r.n_reads) * plane_stride, "plane rows"))
       return GTX_ERR_HIP;
     if (int const rc = launch_planes_kernel(r.seq, r.seq_stride, r.n_reads, s->d_planes, plane_stride, r.stream))
+      return rc;
+    r.seq = s->d_planes;
+    r.seq_stride = plane_stride;
+  }
+  else if (r.packed)
+  {
+    // (2 x packed_stride: a plane row of the same number of bases -- the kernels see the row the plane entry points would)
+    uint32_t const plane_stride = (2u * r.seq_stride + PLANE_GROUP_BYTES - 1u) / PLANE_GROUP_BYTES * PLANE_GROUP_BYTES;
+    if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(r.n_reads) * plane_stride, "plane rows"))
+      return GTX_ERR_HIP;
+    if (int const rc = launch_packed_kernel(r.seq, r.seq_stride, r.packed->exc_start, r.packed->exc, r.packed->n_exc, r.n_reads, s->d_planes,
+                                            plane_stride, r.stream))
       return rc;
     r.seq = s->d_planes;
     r.seq_stride = plane_stride;
@@ -2622,6 +2720,39 @@ extern "C" int gtx_align_batch_planes_staged(gtx_ctx * c, const uint8_t * d_plan
     return GTX_ERR_ARG;
   return align_call(c, {d_planes, plane_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream),
                         static_cast<hipEvent_t>(front_event), static_cast<hipStream_t>(tail_stream), static_cast<hipEvent_t>(done_event)});
+}
+
+extern "C" int gtx_align_batch_packed(gtx_ctx * c, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start,
+                                      const uint16_t * d_exc, uint32_t n_exc, const gtx_read_meta * d_meta, uint32_t n_reads, uint32_t * d_records,
+                                      uint32_t rec_words, uint8_t * d_task_flags, void * stream)
+{
+  return gtx_align_batch_packed_staged(c, d_packed, packed_stride, d_exc_start, d_exc, n_exc, d_meta, n_reads, d_records, rec_words, d_task_flags,
+                                       stream, nullptr, nullptr, nullptr);
+}
+
+// packed rows + exception list: unpacked into plane rows in the call's scratch, then the calls of gtx_align_batch_planes_staged
+extern "C" int gtx_align_batch_packed_staged(gtx_ctx * c, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start,
+                                             const uint16_t * d_exc, uint32_t n_exc, const gtx_read_meta * d_meta, uint32_t n_reads,
+                                             uint32_t * d_records, uint32_t rec_words, uint8_t * d_task_flags, void * stream, void * front_event,
+                                             void * tail_stream, void * done_event)
+{
+  if (!c || rec_words < 8 || (n_reads != 0 && (!d_meta || !d_records)))
+  {
+    g_last_error = "gtx_align_batch_packed: bad argument";
+    return GTX_ERR_ARG;
+  }
+  if (!packed_args_ok(d_packed, packed_stride, d_exc_start, d_exc, n_exc, n_reads))
+    return GTX_ERR_ARG;
+  if (packed_stride > 0x7FFFFFFFu / 2u)
+  {
+    g_last_error = "gtx_align_batch_packed: packed_stride too large";
+    return GTX_ERR_ARG;
+  }
+  PackedInput const p{d_exc_start, d_exc, n_exc};
+  AlignRequest r{d_packed, packed_stride, d_meta, n_reads, d_records, rec_words, d_task_flags, static_cast<hipStream_t>(stream),
+                 static_cast<hipEvent_t>(front_event), static_cast<hipStream_t>(tail_stream), static_cast<hipEvent_t>(done_event)};
+  r.packed = &p;
+  return align_call(c, r);
 }
 
 extern "C" int gtx_align_batch_planes_compact(gtx_ctx * c, const uint8_t * d_planes, uint32_t plane_stride, const gtx_read_meta * d_meta,

@@ -535,6 +535,109 @@ extern "C" int gtx_pack_planes(const uint8_t * seq, uint32_t seq_stride, uint32_
   return GTX_OK;
 }
 
+// ---- BAM nibble rows -> packed 2-bit rows + exception list (graph_dev.hpp: planes_from_packed is the way back)
+namespace
+{
+constexpr uint32_t PACKED_MAX_BASES = (1u << gtx::PACKED_EXC_INDEX_BITS) - 1u; // 4 095: what an entry's index can name
+
+// non-ACGT nibbles per BAM byte: what a read of these bytes adds to the exception list at most
+struct ExcPerByte
+{
+  uint8_t n[256];
+  ExcPerByte()
+  {
+    auto acgt = [](uint32_t c) { return c == 1u || c == 2u || c == 4u || c == 8u; };
+    for (uint32_t b = 0; b < 256; ++b)
+      n[b] = static_cast<uint8_t>(!acgt(b >> 4) + !acgt(b & 15u));
+  }
+};
+
+uint32_t exc_bound(uint8_t const * nib, uint32_t l_qseq)
+{
+  static ExcPerByte const t;
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < l_qseq / 2u; ++i)
+    k += t.n[nib[i]];
+  if (l_qseq & 1u)
+    k += t.n[(nib[l_qseq / 2u] & 0xF0u) | 1u]; // (the low nibble lies behind the read: counted as an A)
+  return k;
+}
+
+// One read: its packed row (`groups` groups; behind the read 00) and its exceptions, appended to exc from entry `at` on while
+// they fit in exc_cap.  Returns the entries the read has.  Planes first (planes_row: PEXT where the CPU has it), then per group
+// the bases with exactly one bit set are the 2-bit bases and all others are exceptions.
+uint32_t pack_2bit_row(uint8_t const * nib, uint32_t l_qseq, uint32_t * out, uint32_t groups, uint16_t * exc, uint64_t at, uint64_t exc_cap)
+{
+  constexpr uint32_t MAX_GROUPS = (PACKED_MAX_BASES + 32u) / 32u;
+  uint32_t pl[4 * MAX_GROUPS];
+  uint32_t const read_groups = (l_qseq + 31u) / 32u;
+  planes_row(nib, (l_qseq + 1u) / 2u, pl, read_groups);
+  uint32_t k = 0;
+  for (uint32_t g = 0; g < groups; ++g)
+  {
+    uint32_t lo = 0, hi = 0;
+    if (g < read_groups)
+    {
+      uint32_t const p0 = pl[4 * g], p1 = pl[4 * g + 1], p2 = pl[4 * g + 2], p3 = pl[4 * g + 3];
+      uint32_t const in_read = l_qseq - 32u * g >= 32u ? 0xFFFFFFFFu : (1u << (l_qseq - 32u * g)) - 1u;
+      uint32_t const two = (p0 & p1) | (p0 & p2) | (p0 & p3) | (p1 & p2) | (p1 & p3) | (p2 & p3);
+      uint32_t const one = (p0 ^ p1 ^ p2 ^ p3) & ~two & in_read;
+      lo = (p1 | p3) & one;
+      hi = (p2 | p3) & one;
+      for (uint32_t m = ~one & in_read; m; m &= m - 1u)
+      {
+        uint32_t const j = static_cast<uint32_t>(__builtin_ctz(m));
+        uint32_t const code = ((p0 >> j) & 1u) | (((p1 >> j) & 1u) << 1) | (((p2 >> j) & 1u) << 2) | (((p3 >> j) & 1u) << 3);
+        if (at + k < exc_cap)
+          exc[at + k] = static_cast<uint16_t>((32u * g + j) | (code << gtx::PACKED_EXC_INDEX_BITS));
+        ++k;
+      }
+    }
+    out[2 * g] = lo;
+    out[2 * g + 1] = hi;
+  }
+  return k;
+}
+} // namespace
+
+extern "C" int gtx_pack_2bit(const uint8_t * seq, uint32_t seq_stride, const uint32_t * l_qseq, uint32_t n, uint8_t * packed, uint32_t packed_stride,
+                             uint32_t * exc_start, uint16_t * exc, uint32_t exc_cap, uint32_t * n_exc)
+{
+  if (!exc_start || !n_exc || (n != 0 && (!seq || !l_qseq || !packed)) || (exc_cap != 0 && !exc) || packed_stride == 0 ||
+      (packed_stride % gtx::PACKED_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(packed) & 3u) != 0)
+  {
+    gtx::g_last_error = "gtx_pack_2bit: bad argument (packed rows are 8-byte groups of 32-bit words; exc_start holds n + 1 entries)";
+    return GTX_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (l_qseq[i] > PACKED_MAX_BASES || l_qseq[i] > 4ull * packed_stride || (l_qseq[i] + 1ull) / 2u > seq_stride)
+    {
+      gtx::g_last_error = "gtx_pack_2bit: read " + std::to_string(i) + " of " + std::to_string(l_qseq[i]) +
+                          " bases is longer than its nibble row, its packed row or 4 095 bases";
+      return GTX_ERR_ARG;
+    }
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; ++i)
+  {
+    exc_start[i] = static_cast<uint32_t>(total);
+    total += pack_2bit_row(seq + static_cast<uint64_t>(i) * seq_stride, l_qseq[i], reinterpret_cast<uint32_t *>(packed + static_cast<uint64_t>(i) * packed_stride),
+                           packed_stride / gtx::PACKED_GROUP_BYTES, exc, total, exc_cap);
+    if (total > 0xFFFFFFFFull)
+    {
+      gtx::g_last_error = "gtx_pack_2bit: more than 2^32 - 1 exceptions";
+      return GTX_ERR_CAPACITY;
+    }
+  }
+  exc_start[n] = static_cast<uint32_t>(total);
+  *n_exc = static_cast<uint32_t>(total);
+  if (total > exc_cap)
+  {
+    gtx::g_last_error = "gtx_pack_2bit: " + std::to_string(total) + " exceptions, exc_cap is " + std::to_string(exc_cap);
+    return GTX_ERR_CAPACITY;
+  }
+  return GTX_OK;
+}
+
 struct gtx_stream
 {
   gtx_params params{};
@@ -603,6 +706,198 @@ struct gtx_stream
   uint64_t n_records = 0, n_duplicated = 0;
 };
 
+namespace
+{
+// gtx_stream_push: copies of the BAM bytes, or plane rows after gtx_stream_set_planes
+struct NibbleOrPlaneRows
+{
+  uint8_t * align_seq;
+  uint32_t seq_stride, plane_stride;
+  uint32_t row_bases() const { return 2u * plane_stride; }
+  std::string too_long_message() const { return "gtx_stream_push: a record is longer than seq_stride (or than the plane rows of gtx_stream_set_planes)"; }
+  int fits(gtx_stream_record const *, uint8_t const *, uint32_t, uint32_t) const { return GTX_OK; }
+  void put(uint32_t task, uint8_t const * rseq, uint32_t nbytes, uint32_t)
+  {
+    if (plane_stride)
+      planes_row(rseq, nbytes, reinterpret_cast<uint32_t *>(align_seq + static_cast<uint64_t>(task) * plane_stride), plane_stride / gtx::PLANE_GROUP_BYTES);
+    else
+      std::memcpy(align_seq + static_cast<uint64_t>(task) * seq_stride, rseq, nbytes);
+  }
+  void end(uint32_t) {}
+};
+
+// gtx_stream_push_packed: packed rows and the exception list (exc_start: one offset per task and one behind the last)
+struct PackedRows
+{
+  uint8_t * packed;
+  uint32_t packed_stride;
+  uint32_t * exc_start;
+  uint16_t * exc;
+  uint32_t exc_cap;
+  uint32_t * n_exc;
+  uint32_t used = 0;
+  uint32_t row_bases() const { return std::min<uint32_t>(4u * packed_stride, PACKED_MAX_BASES); }
+  std::string too_long_message() const { return "gtx_stream_push_packed: a record is longer than seq_stride (or than the packed rows)"; }
+  // every record's exceptions, whether it becomes a task or not: a bound the call never exceeds, checked before the stream moves
+  int fits(gtx_stream_record const * recs, uint8_t const * seq, uint32_t seq_stride, uint32_t n) const
+  {
+    uint64_t need = 0;
+    for (uint32_t i = 0; i < n; ++i)
+      need += exc_bound(seq + static_cast<uint64_t>(i) * seq_stride, recs[i].l_qseq);
+    if (need <= exc_cap)
+      return GTX_OK;
+    *n_exc = static_cast<uint32_t>(std::min<uint64_t>(need, 0xFFFFFFFFull));
+    g_last_error = "gtx_stream_push_packed: exc_cap has to hold the exceptions of every pushed record (" + std::to_string(need) + ")";
+    return GTX_ERR_CAPACITY;
+  }
+  void put(uint32_t task, uint8_t const * rseq, uint32_t, uint32_t l_qseq)
+  {
+    exc_start[task] = used;
+    used += pack_2bit_row(rseq, l_qseq, reinterpret_cast<uint32_t *>(packed + static_cast<uint64_t>(task) * packed_stride),
+                          packed_stride / gtx::PACKED_GROUP_BYTES, exc, used, exc_cap);
+  }
+  void end(uint32_t tasks)
+  {
+    exc_start[tasks] = used;
+    *n_exc = used;
+  }
+};
+
+// The per-record decisions of gtx_stream_push and gtx_stream_push_packed: `rows` receives the alignment tasks' bases --
+// rows.row_bases() (0: no limit but seq_stride) is the longest read a row holds, rows.fits() the sink's own check of the
+// whole batch behind the common ones, rows.put(task, bases, bytes, l_qseq) writes one task's row, rows.end(tasks) closes.
+template <class Rows>
+int stream_push(gtx_stream * s, const gtx_stream_record * recs, const uint8_t * seq, uint32_t seq_stride, uint32_t n, Rows & rows,
+                gtx_read_meta * align_meta, uint32_t align_cap, uint32_t * n_align, gtx_score_item * items, uint32_t item_cap, uint32_t * n_items)
+{
+  if (!s || !recs || !seq || !align_meta || !n_align || !items || !n_items)
+    return GTX_ERR_ARG;
+  // everything that can fail is checked before the stream's state is touched: a failing call consumes nothing
+  if (n > align_cap || n > item_cap)
+  {
+    g_last_error = "gtx_stream_push: align_cap and item_cap have to hold one entry per pushed record";
+    return GTX_ERR_CAPACITY;
+  }
+  for (uint32_t i = 0; i < n; ++i)
+  {
+    if (recs[i].rg >= s->parked.size())
+    {
+      g_last_error = "gtx_stream_push: read group index out of range";
+      return GTX_ERR_ARG;
+    }
+    if (recs[i].l_qseq > gtx::max_read_len_of(s->params))
+    {
+      g_last_error = "gtx_stream_push: a read of " + std::to_string(recs[i].l_qseq) + " bases (the stream's max_read_len is " +
+                     std::to_string(gtx::max_read_len_of(s->params)) + ")";
+      return GTX_ERR_UNSUPPORTED;
+    }
+    if ((static_cast<uint32_t>(recs[i].l_qseq) + 1u) / 2u > seq_stride || (rows.row_bases() && recs[i].l_qseq > rows.row_bases()))
+    {
+      g_last_error = rows.too_long_message();
+      return GTX_ERR_ARG;
+    }
+  }
+  if (int const rc = rows.fits(recs, seq, seq_stride, n))
+    return rc;
+  uint32_t na = 0, ni = 0;
+  for (uint32_t i = 0; i < n; ++i)
+  {
+    gtx_stream_record const & r = recs[i];
+    if ((r.flag & s->params.sam_flag_filter) != 0 || (s->params.is_sv_graph && !gtx_stream::is_good_read(r))) // :658-663
+      continue;
+    if (r.rg >= s->parked.size())
+    {
+      g_last_error = "gtx_stream_push: read group index out of range";
+      return GTX_ERR_ARG;
+    }
+    ++s->n_records;
+    uint8_t const * rseq = seq + static_cast<uint64_t>(i) * seq_stride;
+    uint32_t const nbytes = (static_cast<uint32_t>(r.l_qseq) + 1u) / 2u;
+    if (nbytes > seq_stride)
+      return GTX_ERR_ARG;
+    // equal_pos_seq (include/graphtyper/utilities/hts_utils.hpp:110-128): same tid, pos, length and packed bytes
+    bool const dup = s->have_prev && r.tid == s->prev_tid && r.pos == s->prev_pos && r.l_qseq == s->prev_len &&
+                     std::memcmp(rseq, s->prev_seq.data(), nbytes) == 0;
+    uint32_t align_index;
+    if (!s->have_prev)
+      s->first_pos = r.pos; // the first record that passes the filters anchors the coverage bins (:594)
+    if (dup)
+    {
+      (void)s->update_bin_count(r);
+      ++s->n_duplicated;
+      align_index = s->prev_align_index; // prev_paths are reused as they are (hts_parallel_reader.cpp:666-684)
+    }
+    else
+    {
+      if (!s->update_bin_count(r) && s->have_prev) // too many reads in this bin: the record is skipped (:685-690)
+      {
+        --s->n_records;
+        continue;
+      }
+      if (na >= align_cap)
+        return GTX_ERR_CAPACITY;
+      rows.put(na, rseq, nbytes, r.l_qseq);
+      // position hint of the alignment: where read base 0 lies when the mapper was right (leading soft clip removed)
+      int32_t const clip = (r.n_cigar != 0 && (r.cigar_front & 15u) == 4u) ? static_cast<int32_t>(r.cigar_front >> 4) : 0;
+      // align_read (alignment.cpp:341-352): forward only for unpaired reads and concordant pairs
+      bool const one_orientation = (r.flag & 1u) == 0u || (r.tid == r.mtid && r.isize > -1200 && r.isize < 1200 &&
+                                                            (((r.flag & 16u) != 0u) != ((r.flag & 32u) != 0u)));
+      s->prev_forward_only = one_orientation && !s->params.force_align_both_orientations;
+      // (every item made of this task carries GTX_FLAG_FORWARD_ONLY then: the task's reverse record is never read, and the
+      //  same bit in the read's flag word lets the alignment skip writing its empty header)
+      align_meta[na] = gtx_read_meta{r.l_qseq, static_cast<uint16_t>(r.flag | (s->prev_forward_only ? GTX_FLAG_FORWARD_ONLY : 0u)), r.tid, r.mtid,
+                                     r.isize, r.pos - clip};
+      align_index = s->next_align_index++;
+      ++na;
+      s->have_prev = true;
+      s->prev_tid = r.tid;
+      s->prev_pos = r.pos;
+      s->prev_len = r.l_qseq;
+      s->prev_seq.assign(rseq, rseq + nbytes);
+      s->prev_align_index = align_index;
+    }
+    gtx_rec_meta const me{align_index, static_cast<uint16_t>(r.flag | (s->prev_forward_only ? GTX_FLAG_FORWARD_ONLY : 0u)), r.mapq,
+                          r.score_diff, r.pos, r.isize};
+    auto & map = s->parked[r.rg];
+    auto it = map.find(r.name_id);
+    if (it == map.end())
+    {
+      if (r.flag & 1u) // IS_PAIRED: wait for the mate (hts_parallel_reader.cpp:283-290)
+      {
+        map.emplace(r.name_id, gtx_stream::Parked{me, r.sample});
+        continue;
+      }
+      if (ni >= item_cap)
+        return GTX_ERR_CAPACITY;
+      gtx_score_item item{};
+      item.first = me;
+      item.second.align_index = GTX_INVALID_ID;
+      item.sample = r.sample;
+      items[ni++] = item;
+      continue;
+    }
+    if ((it->second.meta.flag & 64u) == (r.flag & 64u)) // both mates claim the same IS_FIRST_IN_PAIR: the reference exits (:306-315)
+    {
+      g_last_error = "gtx_stream_push: two reads with one name have the same IS_FIRST_IN_PAIR";
+      return GTX_ERR_ARG;
+    }
+    if (ni >= item_cap)
+      return GTX_ERR_CAPACITY;
+    gtx_score_item item{};
+    item.first = it->second.meta;
+    item.second = me;
+    item.sample = r.sample;
+    items[ni++] = item;
+    map.erase(it);
+  }
+  *n_align = na;
+  *n_items = ni;
+  rows.end(na);
+  return GTX_OK;
+}
+
+} // namespace
+
 extern "C"
 {
   int gtx_stream_create(const gtx_params * params, uint32_t n_read_groups, gtx_stream ** out)
@@ -627,131 +922,25 @@ extern "C"
                       uint8_t * align_seq, gtx_read_meta * align_meta, uint32_t align_cap, uint32_t * n_align,
                       gtx_score_item * items, uint32_t item_cap, uint32_t * n_items)
   {
-    if (!s || !recs || !seq || !align_seq || !align_meta || !n_align || !items || !n_items)
+    if (!s || !align_seq)
       return GTX_ERR_ARG;
-    // everything that can fail is checked before the stream's state is touched: a failing call consumes nothing
-    if (n > align_cap || n > item_cap)
+    NibbleOrPlaneRows rows{align_seq, seq_stride, s->plane_stride};
+    return stream_push(s, recs, seq, seq_stride, n, rows, align_meta, align_cap, n_align, items, item_cap, n_items);
+  }
+
+  int gtx_stream_push_packed(gtx_stream * s, const gtx_stream_record * recs, const uint8_t * seq, uint32_t seq_stride, uint32_t n,
+                             uint8_t * packed, uint32_t packed_stride, uint32_t * exc_start, uint16_t * exc, uint32_t exc_cap, uint32_t * n_exc,
+                             gtx_read_meta * align_meta, uint32_t align_cap, uint32_t * n_align, gtx_score_item * items, uint32_t item_cap,
+                             uint32_t * n_items)
+  {
+    if (!s || !packed || !exc_start || !n_exc || (exc_cap != 0 && !exc) || packed_stride == 0 || (packed_stride % gtx::PACKED_GROUP_BYTES) != 0 ||
+        (reinterpret_cast<uintptr_t>(packed) & 3u) != 0)
     {
-      g_last_error = "gtx_stream_push: align_cap and item_cap have to hold one entry per pushed record";
-      return GTX_ERR_CAPACITY;
+      g_last_error = "gtx_stream_push_packed: bad argument (packed rows are 8-byte groups of 32-bit words; exc_start holds align_cap + 1 entries)";
+      return GTX_ERR_ARG;
     }
-    for (uint32_t i = 0; i < n; ++i)
-    {
-      if (recs[i].rg >= s->parked.size())
-      {
-        g_last_error = "gtx_stream_push: read group index out of range";
-        return GTX_ERR_ARG;
-      }
-      if (recs[i].l_qseq > gtx::max_read_len_of(s->params))
-      {
-        g_last_error = "gtx_stream_push: a read of " + std::to_string(recs[i].l_qseq) + " bases (the stream's max_read_len is " +
-                       std::to_string(gtx::max_read_len_of(s->params)) + ")";
-        return GTX_ERR_UNSUPPORTED;
-      }
-      if ((static_cast<uint32_t>(recs[i].l_qseq) + 1u) / 2u > seq_stride || (s->plane_stride && recs[i].l_qseq > 2u * s->plane_stride))
-      {
-        g_last_error = "gtx_stream_push: a record is longer than seq_stride (or than the plane rows of gtx_stream_set_planes)";
-        return GTX_ERR_ARG;
-      }
-    }
-    uint32_t na = 0, ni = 0;
-    for (uint32_t i = 0; i < n; ++i)
-    {
-      gtx_stream_record const & r = recs[i];
-      if ((r.flag & s->params.sam_flag_filter) != 0 || (s->params.is_sv_graph && !gtx_stream::is_good_read(r))) // :658-663
-        continue;
-      if (r.rg >= s->parked.size())
-      {
-        g_last_error = "gtx_stream_push: read group index out of range";
-        return GTX_ERR_ARG;
-      }
-      ++s->n_records;
-      uint8_t const * rseq = seq + static_cast<uint64_t>(i) * seq_stride;
-      uint32_t const nbytes = (static_cast<uint32_t>(r.l_qseq) + 1u) / 2u;
-      if (nbytes > seq_stride)
-        return GTX_ERR_ARG;
-      // equal_pos_seq (include/graphtyper/utilities/hts_utils.hpp:110-128): same tid, pos, length and packed bytes
-      bool const dup = s->have_prev && r.tid == s->prev_tid && r.pos == s->prev_pos && r.l_qseq == s->prev_len &&
-                       std::memcmp(rseq, s->prev_seq.data(), nbytes) == 0;
-      uint32_t align_index;
-      if (!s->have_prev)
-        s->first_pos = r.pos; // the first record that passes the filters anchors the coverage bins (:594)
-      if (dup)
-      {
-        (void)s->update_bin_count(r);
-        ++s->n_duplicated;
-        align_index = s->prev_align_index; // prev_paths are reused as they are (hts_parallel_reader.cpp:666-684)
-      }
-      else
-      {
-        if (!s->update_bin_count(r) && s->have_prev) // too many reads in this bin: the record is skipped (:685-690)
-        {
-          --s->n_records;
-          continue;
-        }
-        if (na >= align_cap)
-          return GTX_ERR_CAPACITY;
-        if (s->plane_stride)
-          planes_row(rseq, nbytes, reinterpret_cast<uint32_t *>(align_seq + static_cast<uint64_t>(na) * s->plane_stride),
-                     s->plane_stride / gtx::PLANE_GROUP_BYTES);
-        else
-          std::memcpy(align_seq + static_cast<uint64_t>(na) * seq_stride, rseq, nbytes);
-        // position hint of the alignment: where read base 0 lies when the mapper was right (leading soft clip removed)
-        int32_t const clip = (r.n_cigar != 0 && (r.cigar_front & 15u) == 4u) ? static_cast<int32_t>(r.cigar_front >> 4) : 0;
-        // align_read (alignment.cpp:341-352): forward only for unpaired reads and concordant pairs
-        bool const one_orientation = (r.flag & 1u) == 0u || (r.tid == r.mtid && r.isize > -1200 && r.isize < 1200 &&
-                                                              (((r.flag & 16u) != 0u) != ((r.flag & 32u) != 0u)));
-        s->prev_forward_only = one_orientation && !s->params.force_align_both_orientations;
-        // (every item made of this task carries GTX_FLAG_FORWARD_ONLY then: the task's reverse record is never read, and the
-        //  same bit in the read's flag word lets the alignment skip writing its empty header)
-        align_meta[na] = gtx_read_meta{r.l_qseq, static_cast<uint16_t>(r.flag | (s->prev_forward_only ? GTX_FLAG_FORWARD_ONLY : 0u)), r.tid, r.mtid,
-                                       r.isize, r.pos - clip};
-        align_index = s->next_align_index++;
-        ++na;
-        s->have_prev = true;
-        s->prev_tid = r.tid;
-        s->prev_pos = r.pos;
-        s->prev_len = r.l_qseq;
-        s->prev_seq.assign(rseq, rseq + nbytes);
-        s->prev_align_index = align_index;
-      }
-      gtx_rec_meta const me{align_index, static_cast<uint16_t>(r.flag | (s->prev_forward_only ? GTX_FLAG_FORWARD_ONLY : 0u)), r.mapq,
-                            r.score_diff, r.pos, r.isize};
-      auto & map = s->parked[r.rg];
-      auto it = map.find(r.name_id);
-      if (it == map.end())
-      {
-        if (r.flag & 1u) // IS_PAIRED: wait for the mate (hts_parallel_reader.cpp:283-290)
-        {
-          map.emplace(r.name_id, gtx_stream::Parked{me, r.sample});
-          continue;
-        }
-        if (ni >= item_cap)
-          return GTX_ERR_CAPACITY;
-        gtx_score_item item{};
-        item.first = me;
-        item.second.align_index = GTX_INVALID_ID;
-        item.sample = r.sample;
-        items[ni++] = item;
-        continue;
-      }
-      if ((it->second.meta.flag & 64u) == (r.flag & 64u)) // both mates claim the same IS_FIRST_IN_PAIR: the reference exits (:306-315)
-      {
-        g_last_error = "gtx_stream_push: two reads with one name have the same IS_FIRST_IN_PAIR";
-        return GTX_ERR_ARG;
-      }
-      if (ni >= item_cap)
-        return GTX_ERR_CAPACITY;
-      gtx_score_item item{};
-      item.first = it->second.meta;
-      item.second = me;
-      item.sample = r.sample;
-      items[ni++] = item;
-      map.erase(it);
-    }
-    *n_align = na;
-    *n_items = ni;
-    return GTX_OK;
+    PackedRows rows{packed, packed_stride, exc_start, exc, exc_cap, n_exc};
+    return stream_push(s, recs, seq, seq_stride, n, rows, align_meta, align_cap, n_align, items, item_cap, n_items);
   }
 
   int gtx_stream_set_planes(gtx_stream * s, uint32_t plane_stride)

@@ -30,7 +30,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_reads_sample_name", "gtx_reads_next", "gtx_reads_close", "gtx_align_batch_flags", "gtx_score_batch_flags", "gtx_score_batch_words", "gtx_item_words",
            "gtx_pack_planes", "gtx_reads_to_planes", "gtx_align_batch_planes", "gtx_align_batch_planes_staged", "gtx_stream_set_planes", "gtx_device_cache_release",
            "gtx_disc_create", "gtx_disc_destroy", "gtx_disc_events_batch", "gtx_disc_first_pass", "gtx_vcf_header", "gtx_bgzf_compress",
-           "gtx_shrink_params_default", "gtx_bam_shrink", "gtx_inflate_raw", "gtx_tabix_build", "gtx_tabix_start", "gtx_pipeline_run", "gtx_regions_run", "gtx_regions_free", "gtx_bam_shrink_multi", "gtx_disc_first_pass_haplotypes", "gtx_disc_merge"]
+           "gtx_shrink_params_default", "gtx_bam_shrink", "gtx_inflate_raw", "gtx_tabix_build", "gtx_tabix_start", "gtx_pipeline_run", "gtx_regions_run", "gtx_regions_free", "gtx_bam_shrink_multi", "gtx_disc_first_pass_haplotypes", "gtx_disc_merge",
+           "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged"]
 
 
 class GraphView(C.Structure):
@@ -214,6 +215,17 @@ def lib():
         L.gtx_align_batch_planes_staged.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]
         L.gtx_stream_set_planes.argtypes = [C.c_void_p, C.c_uint32]
+        L.gtx_pack_2bit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                    C.POINTER(C.c_uint32)]
+        L.gtx_stream_push_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32,
+                                             C.POINTER(C.c_uint32)]
+        L.gtx_packed_to_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                           C.c_void_p]
+        L.gtx_align_batch_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_uint32, C.c_void_p, C.c_void_p]
+        L.gtx_align_batch_packed_staged.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                    C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gtx_score_batch_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(ScoreBuffers), C.c_void_p]
         L.gtx_reads_open.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.POINTER(C.c_void_p)]
         L.gtx_reads_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -481,6 +493,48 @@ def planes_reference(codes, plane_stride):
         bits = ((padded >> b) & 1).reshape(n, groups, 32).astype(np.uint32)
         out[:, :, b] = (bits << np.arange(32, dtype=np.uint32)).sum(axis=2, dtype=np.uint64).astype(np.uint32)
     return out.reshape(n, groups * 4).view(np.uint8).reshape(n, plane_stride)
+
+
+def pack_2bit(seq, l_qseq, packed_stride=None):
+    """gtx_pack_2bit: [n, stride] BAM nibble rows of l_qseq[i] bases -> (rows [n, packed_stride] uint8, exc_start [n + 1] uint32,
+    exc uint16) (include/gtx.h: packed 2-bit rows with an exception list)"""
+    seq = np.ascontiguousarray(seq, np.uint8)
+    n, stride = seq.shape
+    l_qseq = np.ascontiguousarray(l_qseq, np.uint32)
+    assert len(l_qseq) == n
+    packed_stride = packed_stride or max(8, (stride // 2 + 7) // 8 * 8)  # (a row for every base of the nibble row)
+    rows = np.zeros((n, packed_stride), np.uint8)
+    exc_start = np.zeros(n + 1, np.uint32)
+    n_exc = C.c_uint32()
+    L = lib()
+    rc = L.gtx_pack_2bit(_p(seq), stride, _p(l_qseq), n, _p(rows), packed_stride, _p(exc_start), None, 0, C.byref(n_exc))
+    if rc not in (0, 5):  # (5: GTX_ERR_CAPACITY -- the first call only counts)
+        check(rc)
+    exc = np.zeros(max(n_exc.value, 1), np.uint16)
+    check(L.gtx_pack_2bit(_p(seq), stride, _p(l_qseq), n, _p(rows), packed_stride, _p(exc_start), _p(exc), len(exc), C.byref(n_exc)))
+    return rows, exc_start, exc[:n_exc.value]
+
+
+def packed_reference(codes, packed_stride, lengths=None):
+    """the packed layout restated in numpy (tests): [n, L] codes, read i being codes[i, :lengths[i]] (default: all L) ->
+    (rows [n, packed_stride] uint8, exc_start [n + 1] uint32, exc uint16)"""
+    codes = np.asarray(codes, np.uint8)
+    n, L = codes.shape
+    groups = packed_stride // 8
+    inside = np.arange(L)[None, :] < (np.full(n, L) if lengths is None else np.asarray(lengths))[:, None]
+    two = np.select([codes == 1, codes == 2, codes == 4, codes == 8], [0, 1, 2, 3], default=0).astype(np.uint8) * inside
+    is_exc = ~np.isin(codes, (1, 2, 4, 8)) & inside
+    padded = np.zeros((n, groups * 32), np.uint8)
+    padded[:, :L] = two
+    out = np.zeros((n, groups, 2), np.uint32)
+    for b in range(2):
+        bits = ((padded >> b) & 1).reshape(n, groups, 32).astype(np.uint64)
+        out[:, :, b] = (bits << np.arange(32, dtype=np.uint64)).sum(axis=2, dtype=np.uint64).astype(np.uint32)
+    r, j = np.nonzero(is_exc)  # (row-major: sorted by read, then by base index)
+    exc = (j.astype(np.uint32) | (codes[r, j].astype(np.uint32) << 12)).astype(np.uint16)
+    exc_start = np.zeros(n + 1, np.uint32)
+    exc_start[1:] = np.cumsum(np.bincount(r, minlength=n))
+    return out.reshape(n, groups * 2).view(np.uint8).reshape(n, packed_stride), exc_start, exc
 
 
 class Reads:
@@ -888,6 +942,22 @@ class Stream:
         check(lib().gtx_stream_push(self.h, _p(recs), _p(seq), stride, n, _p(a_seq), _p(a_meta), n, C.byref(na), _p(items), n,
                                     C.byref(ni)))
         return a_seq[:na.value], a_meta[:na.value], items[:ni.value]
+
+    def push_packed(self, recs, seq, packed_stride):
+        """push() with the tasks' bases as packed rows: recs, seq: [n, stride] packed bases -> (rows, exc_start, exc, align_meta,
+        items), exc_start with one entry per row and one behind the last"""
+        recs = np.ascontiguousarray(recs, STREAM_RECORD)
+        seq = np.ascontiguousarray(seq, np.uint8)
+        n, stride = seq.shape
+        rows = np.zeros((n, packed_stride), np.uint8)
+        exc_start = np.zeros(n + 1, np.uint32)
+        exc = np.zeros(max(1, n * min(4 * packed_stride, 2 * stride)), np.uint16)  # (room for every base of every record)
+        a_meta = np.zeros(n, READ_META)
+        items = np.zeros(n, SCORE_ITEM)
+        ne, na, ni = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().gtx_stream_push_packed(self.h, _p(recs), _p(seq), stride, n, _p(rows), packed_stride, _p(exc_start), _p(exc), len(exc),
+                                           C.byref(ne), _p(a_meta), n, C.byref(na), _p(items), n, C.byref(ni)))
+        return rows[:na.value], exc_start[:na.value + 1], exc[:ne.value], a_meta[:na.value], items[:ni.value]
 
     def set_coverage(self, avg_cov_by_readlen):
         a = np.ascontiguousarray(avg_cov_by_readlen, np.float64)

@@ -372,6 +372,42 @@ int gtx_align_batch_planes_compact(gtx_ctx *, const uint8_t * d_planes, uint32_t
                                    uint32_t * d_records, uint32_t rec_words, uint32_t * d_compact, uint8_t * d_task_flags, void * stream,
                                    void * front_event, void * tail_stream, void * done_event);
 
+/* ---- reads as packed 2-bit rows with an exception list: half the bytes of a plane row, for hosts that copy reads to the
+ * device per batch (the copy, not the device, sets such a host's rate).  A packed row of packed_stride bytes (a multiple of 8)
+ * is packed_stride / 8 groups of 32 bases, two little-endian 32-bit words per group: word 2g holds the low bit and word 2g + 1
+ * the high bit of the 2-bit codes (A0 C1 G2 T3) of bases 32g .. 32g+31, base 32g + j at bit j.  For a read without ambiguous
+ * bases these are the plane row's words 4g+1 | 4g+3 and 4g+2 | 4g+3: 40 bytes for 150 bases, 256 for GTX_MAX_READ_LONG.
+ * EXCEPTIONS: every base whose BAM code is not exactly A=1, C=2, G=4 or T=8 (N=15, the other IUPAC sets, '='=0) holds 00 in
+ * the row -- as do the bases behind the read's end -- and has an entry (uint16_t) base index | code << 12 in the exception
+ * list.  A read's entries are sorted by base index and are exc[exc_start[i] - exc_start[0] .. exc_start[i+1] - exc_start[0]):
+ * exc_start holds n + 1 OFFSETS FROM exc_start[0], so a slice of a batch (exc_start + k with the matching part of exc) needs
+ * no rebasing.  Reads of up to 4 095 bases (12 index bits).  At one N per thousand bases a 150-base read costs 40 + 4 + 0.3
+ * bytes instead of 80.
+ *   gtx_pack_2bit           host: n BAM nibble rows (l_qseq[i] bases each) -> n packed rows + the list.  *n_exc = entries the
+ *                           batch has; more than exc_cap: GTX_ERR_CAPACITY (rows and exc_start are written all the same).  A
+ *                           read longer than its nibble row, 4 x packed_stride or 4 095 bases: GTX_ERR_ARG (nothing written).
+ *   gtx_stream_push_packed  gtx_stream_push (the same decisions, meta and items) writing the tasks' bases as packed rows
+ *                           (align_cap of them) and the list (exc_start: align_cap + 1 entries; exc: exc_cap, which has to hold
+ *                           the exceptions of all n records -- else GTX_ERR_CAPACITY with *n_exc = that number, and the stream
+ *                           is untouched)
+ *   gtx_packed_to_planes    device: packed rows + list -> plane rows (plane_stride 2 x packed_stride keeps every base), for
+ *                           any plane entry point (_compact, _triaged, ...).  d_packed 8-byte aligned.  Every index into d_exc
+ *                           is clamped to n_exc and a decreasing run is empty: a malformed list gives wrong bases, never an
+ *                           access outside it.  d_exc may be NULL when n_exc is 0.
+ *   gtx_align_batch_packed  gtx_align_batch_planes over packed rows: unpacked into plane rows of 2 x packed_stride bytes in the
+ *                           call's scratch, then the same passes -- the same records and side bytes as gtx_align_batch_planes
+ *                           over those plane rows; _staged as gtx_align_batch_planes_staged. */
+int gtx_pack_2bit(const uint8_t * seq, uint32_t seq_stride, const uint32_t * l_qseq, uint32_t n, uint8_t * packed, uint32_t packed_stride,
+                  uint32_t * exc_start, uint16_t * exc, uint32_t exc_cap, uint32_t * n_exc);
+int gtx_packed_to_planes(gtx_ctx *, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start, const uint16_t * d_exc,
+                         uint32_t n_exc, uint32_t n_reads, uint8_t * d_planes, uint32_t plane_stride, void * stream);
+int gtx_align_batch_packed(gtx_ctx *, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start, const uint16_t * d_exc,
+                           uint32_t n_exc, const gtx_read_meta * d_meta, uint32_t n_reads, uint32_t * d_records, uint32_t rec_words,
+                           uint8_t * d_task_flags, void * stream);
+int gtx_align_batch_packed_staged(gtx_ctx *, const uint8_t * d_packed, uint32_t packed_stride, const uint32_t * d_exc_start, const uint16_t * d_exc,
+                                  uint32_t n_exc, const gtx_read_meta * d_meta, uint32_t n_reads, uint32_t * d_records, uint32_t rec_words,
+                                  uint8_t * d_task_flags, void * stream, void * front_event, void * tail_stream, void * done_event);
+
 /* Score accumulators (all uint32 / uint64, zero-initialised by the caller; sample-major):
  *   d_log_score [n_samples * total_tri]      HapSample::log_score
  *   d_gt_cov    [n_samples * total_allele]   HapSample::gt_coverage
@@ -764,6 +800,11 @@ int gtx_stream_push(gtx_stream *, const gtx_stream_record * recs, const uint8_t 
                     gtx_score_item * items, uint32_t item_cap, uint32_t * n_items);
 /* plane_stride != 0: align_seq receives plane rows of that pitch (see gtx_pack_planes) instead of copies of the BAM bytes */
 int gtx_stream_set_planes(gtx_stream *, uint32_t plane_stride);
+/* gtx_stream_push with the tasks' bases as packed rows and their exception list (see gtx_pack_2bit) */
+int gtx_stream_push_packed(gtx_stream *, const gtx_stream_record * recs, const uint8_t * seq, uint32_t seq_stride, uint32_t n,
+                           uint8_t * packed, uint32_t packed_stride, uint32_t * exc_start, uint16_t * exc, uint32_t exc_cap, uint32_t * n_exc,
+                           gtx_read_meta * align_meta, uint32_t align_cap, uint32_t * n_align, gtx_score_item * items, uint32_t item_cap,
+                           uint32_t * n_items);
 /* SV calling only, optional: the (extreme) coverage filter (hts_parallel_reader.cpp:594-633) drops a record once its
  * sample has more than avg_cov_by_readlen[sample] * 150 accepted records in the record's 50 bp bin.  Without this call
  * (or with a value <= 0 for a sample) nothing is dropped -- Options::no_filter_on_coverage. */
