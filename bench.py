@@ -13,9 +13,11 @@ Launch: `python bench.py --gpus N` starts N ranks itself (torch.distributed.run 
 already set WORLD_SIZE (the driver's `python -m torch.distributed.run ... bench.py --gpus N`) it is one of the ranks and
 WORLD_SIZE must equal --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline` objects; at N=1 the
-line also carries `config.extra`: the cfg3-like workload (30 samples, merged multi-allelic SNP+indel graph) measured in
-the same run.
+Prints ONE JSON line on rank 0 (contract in the task description) with a `roofline` object priced on the timed steps' own
+events.  A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full runs the rest
+as well: the `cpu_baseline` object, the checks of the results (the VCF digest against the pinned one, overflow counts, at
+N > 1 the summed block against one GPU), and at N=1 `config.extra`: the other workloads (cfg3-like, cfg4's share, long
+reads, repeats, SV graph, ...) and schedules, each measured in the same process.
 """
 import argparse
 import ctypes as C
@@ -73,11 +75,14 @@ def parse_args(argv=None):
     ap.add_argument("--err", type=float, default=0.005, help="experiments only; the reported workload uses 0.005")
     ap.add_argument("--nrate", type=float, default=0.001, help="experiments only; the reported workload uses 0.001")
     ap.add_argument("--region-len", type=int, default=REGION_LEN, help="experiments only; the reported workload is 1 Mb")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the checks of the results, the extra workloads and schedules, and the whole record "
+                         "as a file (a plain run only sets up, warms up, times the steps, dumps the outputs and prints the line)")
     ap.add_argument("--cpu-sample", type=int, default=300_000, help="reads timed through the CPU oracle on one core (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU baseline (0 = all host hardware threads, max 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the cfg3-like extra workload")
-    ap.add_argument("--no-reduce-check", action="store_true", help="N > 1: skip the check of the summed block against one GPU (rank 0 redoes every rank's reads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra workloads and schedules")
+    ap.add_argument("--no-reduce-check", action="store_true", help="--full, N > 1: skip the check of the summed block against one GPU (rank 0 redoes every rank's reads)")
     ap.add_argument("--lanes", type=int, default=4, help="steps in flight (each with its own records and accumulators); 1 = one after the other.  "
                     "Staggered schedule with four and more lanes: the last lane is the host's slack (Workload.steps_staggered)")
     ap.add_argument("--schedule", choices=["staggered", "lanes"], default="staggered",
@@ -1756,10 +1761,12 @@ def main(argv=None):
     t0 = time.time()
     ctx = gtx.Context(gtx.graph_from_records(ref_str, records, region_begin=REGION_BEGIN), device=local_rank)
     t_ctx = time.time() - t0
-    t0 = time.time()
-    ctx2 = gtx.Context(gtx.graph_from_records(ref_str, records, region_begin=REGION_BEGIN), device=local_rank)
-    t_ctx_warm = time.time() - t0  # (the first context of a process also pays the HIP module load)
-    ctx2.close()
+    t_ctx_warm = None
+    if args.full:
+        t0 = time.time()
+        ctx2 = gtx.Context(gtx.graph_from_records(ref_str, records, region_begin=REGION_BEGIN), device=local_rank)
+        t_ctx_warm = time.time() - t0  # (the first context of a process also pays the HIP module load)
+        ctx2.close()
     n_keys, n_labels = ctx.index_stats()
 
     # ---- reads, resident in HBM before the timed region ----
@@ -1787,7 +1794,7 @@ def main(argv=None):
     pass_ms, n_pass2 = ctx.pass_times()  # last step: express / general / HBM-table kernels
     kern = ctx.kernel_times() if hasattr(ctx, "kernel_times") else None
     step_alone_ms = None
-    if len(w.lanes) > 1 and dist is None:  # (N = 1 only: with an exchange step every rank would have to take part)
+    if args.full and len(w.lanes) > 1 and dist is None:  # (N = 1 only: with an exchange step every rank would have to take part)
         # (behind the timed region and the queries above: one step at a time on one stream -- a step's latency, where the
         #  timed region measures the throughput of steps in flight on several streams)
         torch.cuda.synchronize()
@@ -1796,7 +1803,7 @@ def main(argv=None):
             w.step(0)
         torch.cuda.synchronize()
         step_alone_ms = 1000.0 * (time.perf_counter() - t0) / 4
-    facts = w.result_facts()
+    facts = w.result_facts() if args.full else {}
     n_gpus = dist.get_world_size() if dist is not None else 1
     per_rank_ms = gather_floats(dist, 1000.0 * w.local_s / args.steps, device)
     reduce_ms = gather_floats(dist, w.reduce_ms, device)
@@ -1806,7 +1813,7 @@ def main(argv=None):
     # into ONE block without an exchange, and the two blocks must be the same bytes: the first run on real xGMI says itself
     # whether gtx_scores_reduce summed what one GPU computes.
     reduce_check = None
-    if dist is not None and not args.no_reduce_check:
+    if args.full and dist is not None and not args.no_reduce_check:
         w.steps_done = 0
         w.step(0)
         summed = w.block_digest(0)
@@ -1910,12 +1917,12 @@ def main(argv=None):
                 "accumulators of all samples, one packed sum over the ranks per step" %
                 (n_samples, sum(per_rank), READ_LEN, n_gpus, "%d per GPU" % n if len(set(per_rank)) == 1 else "%s per GPU" % per_rank, args.scaling))
     cfg = {"workload": what + ", chr20:1000001-2000000 (1 Mb), SNP-only graph (1 SNP / %d bp), unpaired, 0.5%% substitutions, 0.1%% N; "
-                       "result = SampleCall (GT, PL, GQ, depths) per site and sample; gtx_vcf_records writes the region's VCF records from them on "
-                       "the host after the timed steps (config.vcf_text, config.calls_checksum: the digest the full-size GPU test reproduces "
-                       "from the oracle over all reads)" % args.snp_every,
+                       "result = SampleCall (GT, PL, GQ, depths) per site and sample; with --full gtx_vcf_records writes the region's VCF records "
+                       "from them on the host after the timed steps (config.vcf_text, config.calls_checksum: the digest the full-size GPU test "
+                       "reproduces from the oracle over all reads)" % args.snp_every,
            "samples": n_samples, "reads_per_rank": per_rank,
            "reads_per_gpu": n, "index_keys": n_keys, "index_labels": n_labels, "haplotypes": ctx.n_hap,
-           "ctx_create_s": round(t_ctx_warm, 3), "ctx_create_first_s": round(t_ctx, 3),
+           "ctx_create_s": round(t_ctx_warm, 3) if t_ctx_warm is not None else None, "ctx_create_first_s": round(t_ctx, 3),
            "position_hint": not args.no_hint, "task_flags_side_array": USE_TASK_FLAGS, "dense_records": USE_COMPACT,
            "read_layout": "bit planes (gtx_align_batch_planes; repacked once from BAM nibbles by gtx_reads_to_planes before the timed region)" if PLANE_INPUT else "BAM nibbles (gtx_align_batch_flags repacks them inside every call)", "resident_read_sets": len(w.sets),
            "streams": {"steps_in_flight": w.used_lanes, "schedule": ("staggered" if w.staggered else "lanes") if w.used_lanes > 1 else "one step at a time",
@@ -1931,7 +1938,7 @@ def main(argv=None):
            "reduce_ms": max(reduce_ms) if n_gpus > 1 else 0.0, "reduce_ms_per_rank": reduce_ms, "per_rank_ms_per_step": per_rank_ms,
            "reduce_check": reduce_check}
     cfg.update(facts)
-    if n_gpus == 1 and n_samples == 1:
+    if args.full and n_gpus == 1 and n_samples == 1:
         try:
             cfg["calls_checksum"] = w.calls_checksum(0)
             cfg["calls_checksum"]["reads_seed"] = CFG2_READ_SEED
@@ -1944,12 +1951,13 @@ def main(argv=None):
            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling if n_gpus > 1 else "weak", "vs_baseline": None,
            "dtype": "u64/u32 integer (2-bit k-mer keys, byte compares, u32 atomics)", "data": "synthetic", "config": cfg,
            "roofline": roof}
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         m = min(args.cpu_sample, n)
         out["cpu_baseline"] = cpu_baseline(args, ref_str, records, unpack_nibbles(d_seq[:m].cpu().numpy(), READ_LEN), d_pos[:m].cpu().numpy())
     else:
         out["cpu_baseline"] = None
-    if n_gpus == 1 and n_samples == 1 and not args.no_extra:
+    legs = args.full and not args.no_extra
+    if n_gpus == 1 and n_samples == 1 and legs:
         try:  # the same schedule over 500 steps: a timed window of 15 ms cannot tell a 2 % effect from noise
             calib, stag = w.calibration, w.staggered
             dt_long, _ = w.run(500, 2, None)
@@ -2000,13 +2008,13 @@ def main(argv=None):
             del w4
         except Exception as e:
             cfg.setdefault("extra", {})["cfg4_one_gpu"] = {"error": repr(e)}
-    if n_gpus == 1 and not args.no_extra:
+    if n_gpus == 1 and legs:
         try:
             cfg.setdefault("extra", {})["pcie_fed"] = extra_pcie_fed(w, torch, gtx)
         except Exception as e:  # the extra line must never cost the main one
             cfg.setdefault("extra", {})["pcie_fed"] = {"error": repr(e)}
     w.close()
-    if n_gpus == 1 and n_samples == 1 and not args.no_extra:
+    if n_gpus == 1 and n_samples == 1 and legs:
         try:
             cfg.setdefault("extra", {})["pipeline"] = extra_pipeline(args, torch, gtx, synth, device, ctx, ref, records)
             # the same leg with four times the host threads (and reads): where the host side stops scaling
@@ -2020,12 +2028,12 @@ def main(argv=None):
             cfg.setdefault("extra", {})["shrink"] = extra_shrink(args, torch, gtx, synth, device, ref, records)
         except Exception as e:
             cfg.setdefault("extra", {})["shrink"] = {"error": repr(e)}
-    if n_gpus == 1 and n_samples == 1 and not args.no_extra:
+    if n_gpus == 1 and n_samples == 1 and legs:
         try:
             cfg.setdefault("extra", {})["regions"] = extra_regions(args, torch, gtx, synth, device, ref)
         except Exception as e:  # the extra line must never cost the main one
             cfg.setdefault("extra", {})["regions"] = {"error": repr(e)}
-    if n_gpus == 1 and not args.no_extra:
+    if n_gpus == 1 and legs:
         del d_seq, w
         torch.cuda.empty_cache()
         try:
@@ -2049,7 +2057,7 @@ def main(argv=None):
             cfg.setdefault("extra", {})["cfg5"] = extra_cfg5(args, torch, gtx, synth, device)
         except Exception as e:
             cfg.setdefault("extra", {})["cfg5"] = {"error": repr(e)}
-    emit_line(out)
+    emit_line(out, record=args.full)
     if dist is not None:
         dist.destroy_process_group()
     return 0
@@ -2109,8 +2117,8 @@ def compact_line(out):
     return line
 
 
-def emit_line(out):
-    full = json.dumps(out)
+def write_full_record(full):
+    """the whole record (every leg whole) beside the line"""
     try:
         d = os.path.join(ROOT, "gpurun_out")
         os.makedirs(d, exist_ok=True)
@@ -2118,9 +2126,22 @@ def emit_line(out):
             f.write(full + "\n")
     except OSError:
         pass
+
+
+def emit_line(out, record):
+    """record=False (a plain run): the line only -- no file is written, and the line names none"""
+    full = json.dumps(out)
+    if record:
+        write_full_record(full)
     # (NOT to stderr: the driver's record of a run is a bounded tail of stdout AND stderr together -- round 4's 17 KB line was
     #  parsed, round 5's 24 KB line was not -- so nothing long may follow the line either)
-    line = full if os.environ.get("GTX_BENCH_FULL_LINE") else json.dumps(compact_line(out))
+    if os.environ.get("GTX_BENCH_FULL_LINE"):
+        line = full
+    else:
+        small = compact_line(out)
+        if not record:
+            del small["config"]["full_record"]
+        line = json.dumps(small)
     sys.stdout.write(line + "\n")
     sys.stdout.flush()
 

@@ -100,3 +100,19 @@ def test_dump_outputs_writes_exact_floats_under_the_cap(tmp_path):
             assert np.array_equal(x, a.astype(x.dtype)) and x.astype(a.dtype).tolist() == a.tolist()
     x = np.load(str(tmp_path / "a" / "big.npy"))
     assert x.nbytes == bench.DUMP_ARRAY_BYTES and (np.diff(x) > 0).all() and np.isin(x, big).all()
+
+
+def test_a_plain_run_prints_the_line_and_writes_nothing(tmp_path, monkeypatch, capsys):
+    """Without --full the bench runs only what the headline needs: its line names no record file, and it writes none
+    (the CPU baseline, the checks and the extra legs are --full's, off by default)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    out = json.load(open(os.path.join(ROOT, "profiles", "r05_bench.json")))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    monkeypatch.delenv("GTX_BENCH_FULL_LINE", raising=False)
+    bench.emit_line(out, record=False)
+    lines = capsys.readouterr().out.splitlines()
+    assert len(lines) == 1 and list(tmp_path.iterdir()) == []
+    line = json.loads(lines[0])
+    assert "full_record" not in line["config"] and line["value"] == out["value"] and line["ms_per_step"] == out["ms_per_step"]

@@ -20,6 +20,7 @@ mkdir -p gpurun_out
 for round in $(seq 1 $rounds); do
 for v in "$@"; do
   case "$v" in *" -- "*) e="${v%% -- *}"; b="${v#* -- }" ;; "-- "*) e=""; b="${v#-- }" ;; *) e="$v"; b="" ;; esac
+  b="--full $b"  # (the line's VCF digest and, with --extra, the cfg3 leg are bench.py's --full)
   if [ -n "$leg" ]; then
     out=$(env $e python tools/run_extra_leg.py $leg --no-cpu-baseline $b 2>gpurun_out/ab.err | python -c "
 import sys, json
