@@ -1969,6 +1969,19 @@ int ctx_upload(gtx_ctx & c, int device)
   return GTX_OK;
 }
 
+void ctx_release_scratch(gtx_ctx & c)
+{
+  std::lock_guard<std::mutex> lock(c.pool_mutex);
+  for (auto & s : c.pool)
+  {
+    if (s->used) // (behind the last launch that used it, whichever stream that was on)
+      (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
+    scratch_free(*s);
+  }
+  c.pool.clear();
+  c.last_align = nullptr;
+}
+
 void ctx_release_device(gtx_ctx & c)
 {
   if (c.device >= 0)

@@ -895,6 +895,7 @@ struct gtx_reads
   // merge front: one record per file that still has some
   std::vector<std::pair<Rec, uint32_t>> front;
   std::string error;
+  uint32_t refused_len = 0; // bases of the read the last gtx_reads_next stopped at for want of seq_stride (0: none)
 };
 
 namespace
@@ -1054,6 +1055,7 @@ extern "C" int gtx_reads_next(gtx_reads * r, gtx_stream_record * recs, uint8_t *
   if (!r || !recs || !seq || !n)
     return GTX_ERR_ARG;
   *n = 0;
+  r->refused_len = 0;
   while (*n < cap && !r->front.empty())
   {
     // the smallest record; equal keys: the file that was opened first
@@ -1064,6 +1066,7 @@ extern "C" int gtx_reads_next(gtx_reads * r, gtx_stream_record * recs, uint8_t *
     Rec & rec = r->front[best].first;
     if (rec.seq.size() > seq_stride)
     {
+      r->refused_len = rec.r.l_qseq;
       gtx::g_last_error = "gtx_reads_next: a read does not fit in seq_stride";
       return GTX_ERR_ARG;
     }
@@ -1086,6 +1089,8 @@ extern "C" int gtx_reads_next(gtx_reads * r, gtx_stream_record * recs, uint8_t *
   }
   return GTX_OK;
 }
+
+uint32_t gtx::reads_refused_len(gtx_reads const * r) { return r ? r->refused_len : 0; }
 
 extern "C" void gtx_reads_close(gtx_reads * r)
 {

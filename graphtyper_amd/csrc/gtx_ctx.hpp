@@ -190,6 +190,8 @@ inline bool max_read_len_ok(gtx_params const & p)
   return p.max_read_len == 0 || (p.max_read_len > GTX_MAX_READ && p.max_read_len <= GTX_MAX_READ_LONG && !p.no_second_pass);
 }
 inline uint32_t max_read_len_of(gtx_params const & p) { return p.max_read_len ? p.max_read_len : GTX_MAX_READ; }
+// the length of the read the last gtx_reads_next refused with GTX_ERR_ARG because its seq_stride was too small, else 0 (gtx_bam.cpp)
+uint32_t reads_refused_len(gtx_reads const * r);
 // gtx_scores_alloc with the block zeroed on `stream` (no wait: for a caller whose first use of the block is on that stream)
 int scores_alloc_on(gtx_ctx * c, uint32_t n_samples, uint32_t conn_cap, gtx_score_buffers * out, uint64_t * reduced_bytes, void * stream);
 // zeroes the header word of the 2 * n_reads record slots on `stream` (slots recycled from one region to the next)
@@ -198,6 +200,9 @@ int records_clear_enqueue(gtx_ctx * c, uint32_t * d_records, uint32_t rec_words,
 int records_failed_enqueue(gtx_ctx * c, const uint32_t * d_records, uint32_t rec_words, uint64_t n_reads, void * stream, unsigned long long * d_count);
 int ctx_upload(gtx_ctx & c, int device); // graph tables + per-call scratch (no index)
 void ctx_release_device(gtx_ctx & c);
+// gives the context's per-call scratch back to the device cache (a later call makes a new one); only when nothing of the
+// context runs any more (gtx_regions_run: between a long-read region's device stage and its text)
+void ctx_release_scratch(gtx_ctx & c);
 int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<EmitRun> const & runs); // gtx_index_dev.hip
 int download_index(gtx_ctx & c);
 int download_hint_table(gtx_ctx const & c, int which, void * out, uint64_t cap_bytes, uint64_t * bytes); // gtx_index_dev.hip

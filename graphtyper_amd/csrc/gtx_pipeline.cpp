@@ -10,6 +10,11 @@
 // the block does not depend on which thread scored a read).  Two staging sets per thread: while the device works on one
 // batch the thread decodes the next.  What a host language has to add is what follows the loop: gtx_calls_batch,
 // gtx_vcf_records.
+// Reads of up to the context's max_read_len: the BAM nibbles are decoded into rows that hold the longest of them, and each batch
+// is staged as plane rows of the pitch its own longest read needs (80 bytes for reads of up to 160 bases, as before long reads
+// were taken).  A staging set is made for 80-byte rows and grows the first time a batch needs more.  What the stream keeps
+// across batches (the previous read's bases for duplicate reuse, parked mates) is nibbles and task numbers: the pitch may
+// change from one batch to the next.
 #include "gtx_ctx.hpp"
 #include "gtx_devmem.hpp"
 
@@ -30,6 +35,9 @@ double seconds_since(std::chrono::steady_clock::time_point t0)
 {
   return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
+
+constexpr uint32_t MIN_PITCH = 80;   // plane rows of reads of up to 160 bases: every batch gets at least these
+constexpr uint32_t GROUP_BYTES = 16; // a plane row's group of 32 bases (gtx.h, gtx_pack_planes)
 
 struct Worker
 {
@@ -140,7 +148,11 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
     gtx_score_item * pin_items[2] = {nullptr, nullptr};
     void *dev_seq[2] = {nullptr, nullptr}, *dev_meta[2] = {nullptr, nullptr}, *dev_items[2] = {nullptr, nullptr}, *d_rec = nullptr, *d_fl = nullptr;
     gtx_stream * push = nullptr;
-    uint32_t const stride = 80; // plane rows of reads of up to 160 bases
+    uint32_t const max_len = gtx::max_read_len_of(c->params);
+    uint32_t const nibble_stride = (max_len + 1) / 2;  // gtx_reads_next's rows: the context's longest read
+    uint32_t cap_pitch[2] = {MIN_PITCH, MIN_PITCH};    // plane rows the staging sets hold
+    uint32_t set_pitch[2] = {MIN_PITCH, MIN_PITCH};    // the pitch of the batch a set holds
+    uint32_t stream_pitch = MIN_PITCH;                 // what gtx_stream_push writes
     {
       std::lock_guard<std::mutex> lock(c->pipeline_mutex);
       if (!c->pipeline_streams_idle.empty())
@@ -158,10 +170,10 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
     }
     for (int b = 0; b < 2 && ok; ++b)
       ok = hipEventCreateWithFlags(&done[b], hipEventDisableTiming) == hipSuccess &&
-           hipHostMalloc(reinterpret_cast<void **>(&pin_seq[b]), static_cast<size_t>(chunk) * stride) == hipSuccess &&
+           hipHostMalloc(reinterpret_cast<void **>(&pin_seq[b]), static_cast<size_t>(chunk) * MIN_PITCH) == hipSuccess &&
            hipHostMalloc(reinterpret_cast<void **>(&pin_meta[b]), static_cast<size_t>(chunk) * sizeof(gtx_read_meta)) == hipSuccess &&
            hipHostMalloc(reinterpret_cast<void **>(&pin_items[b]), static_cast<size_t>(chunk) * sizeof(gtx_score_item)) == hipSuccess &&
-           gtx::dev_malloc(&dev_seq[b], static_cast<size_t>(chunk) * stride) == hipSuccess &&
+           gtx::dev_malloc(&dev_seq[b], static_cast<size_t>(chunk) * MIN_PITCH) == hipSuccess &&
            gtx::dev_malloc(&dev_meta[b], static_cast<size_t>(chunk) * sizeof(gtx_read_meta)) == hipSuccess &&
            gtx::dev_malloc(&dev_items[b], static_cast<size_t>(chunk) * sizeof(gtx_score_item)) == hipSuccess;
     size_t const rec_bytes = static_cast<size_t>(record_slots_per_thread) * 2 * rec_words * 4, fl_bytes = static_cast<size_t>(record_slots_per_thread) * 2;
@@ -177,9 +189,9 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
       fail(GTX_ERR_ARG, gtx_last_error());
     }
     if (ok)
-      gtx_stream_set_planes(push, stride);
+      gtx_stream_set_planes(push, stream_pitch);
     std::vector<gtx_stream_record> recs(chunk);
-    std::vector<uint8_t> seq(static_cast<size_t>(chunk) * stride);
+    std::vector<uint8_t> seq(static_cast<size_t>(chunk) * nibble_stride);
     if (st)
       (void)hipStreamSynchronize(st);
     // every thread has its buffers: the loop's clock starts when the last one gets here
@@ -190,7 +202,7 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
     uint64_t at = 0; // tasks of this thread so far: the stream numbers them over all its records
     auto submit = [&](int b, uint32_t na, uint32_t ni) -> bool
     {
-      if ((na && (hipMemcpyAsync(dev_seq[b], pin_seq[b], static_cast<size_t>(na) * stride, hipMemcpyHostToDevice, st) != hipSuccess ||
+      if ((na && (hipMemcpyAsync(dev_seq[b], pin_seq[b], static_cast<size_t>(na) * set_pitch[b], hipMemcpyHostToDevice, st) != hipSuccess ||
                   hipMemcpyAsync(dev_meta[b], pin_meta[b], static_cast<size_t>(na) * sizeof(gtx_read_meta), hipMemcpyHostToDevice, st) != hipSuccess)) ||
           (ni && hipMemcpyAsync(dev_items[b], pin_items[b], static_cast<size_t>(ni) * sizeof(gtx_score_item), hipMemcpyHostToDevice, st) != hipSuccess))
       {
@@ -199,7 +211,7 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
       }
       int rc = GTX_OK;
       if (na)
-        rc = gtx_align_batch_planes(c, static_cast<uint8_t const *>(dev_seq[b]), stride, static_cast<gtx_read_meta const *>(dev_meta[b]), na,
+        rc = gtx_align_batch_planes(c, static_cast<uint8_t const *>(dev_seq[b]), set_pitch[b], static_cast<gtx_read_meta const *>(dev_meta[b]), na,
                                     static_cast<uint32_t *>(d_rec) + at * 2 * rec_words, rec_words, static_cast<uint8_t *>(d_fl) + at * 2, st);
       if (rc == GTX_OK && ni)
         rc = gtx_score_batch_flags(c, static_cast<gtx_score_item const *>(dev_items[b]), ni, static_cast<uint32_t const *>(d_rec), rec_words,
@@ -220,8 +232,18 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
     {
       auto t0 = std::chrono::steady_clock::now();
       uint32_t n = 0;
-      int rc = gtx_reads_next(w.reads, recs.data(), seq.data(), stride, chunk, &n);
+      int rc = gtx_reads_next(w.reads, recs.data(), seq.data(), nibble_stride, chunk, &n);
       w.decode += seconds_since(t0);
+      uint32_t longest = 0;
+      for (uint32_t i = 0; rc == GTX_OK && i < n; ++i)
+        longest = std::max<uint32_t>(longest, recs[i].l_qseq);
+      if (rc == GTX_ERR_ARG && gtx::reads_refused_len(w.reads)) // (a read longer than the nibble rows: longer than the context takes)
+        longest = gtx::reads_refused_len(w.reads);
+      if (longest > max_len)
+      {
+        fail(GTX_ERR_UNSUPPORTED, "gtx_pipeline_run: a read of " + std::to_string(longest) + " bases (the context's max_read_len is " + std::to_string(max_len) + ")");
+        break;
+      }
       if (rc != GTX_OK)
       {
         fail(rc, gtx_last_error());
@@ -235,8 +257,30 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
       t0 = std::chrono::steady_clock::now();
       if (used[b])
         (void)hipEventSynchronize(done[b]); // the staging set is free again
+      // the batch's plane rows: as wide as its longest read needs (16 bytes per 32 bases), never narrower than 80 bytes
+      uint32_t const pitch = std::max(MIN_PITCH, (longest + 31) / 32 * GROUP_BYTES);
+      if (pitch > cap_pitch[b])
+      {
+        (void)hipHostFree(pin_seq[b]);
+        (void)gtx::dev_free(dev_seq[b]);
+        pin_seq[b] = nullptr;
+        dev_seq[b] = nullptr;
+        if (hipHostMalloc(reinterpret_cast<void **>(&pin_seq[b]), static_cast<size_t>(chunk) * pitch) != hipSuccess ||
+            gtx::dev_malloc(&dev_seq[b], static_cast<size_t>(chunk) * pitch) != hipSuccess)
+        {
+          fail(GTX_ERR_HIP, "gtx_pipeline_run: could not grow a thread's staging buffers to plane rows of " + std::to_string(pitch) + " bytes");
+          break;
+        }
+        cap_pitch[b] = pitch;
+      }
+      if (pitch != stream_pitch)
+      {
+        gtx_stream_set_planes(push, pitch);
+        stream_pitch = pitch;
+      }
+      set_pitch[b] = pitch;
       uint32_t na = 0, ni = 0;
-      rc = gtx_stream_push(push, recs.data(), seq.data(), stride, n, pin_seq[b], pin_meta[b], chunk, &na, pin_items[b], chunk, &ni);
+      rc = gtx_stream_push(push, recs.data(), seq.data(), nibble_stride, n, pin_seq[b], pin_meta[b], chunk, &na, pin_items[b], chunk, &ni);
       w.push += seconds_since(t0);
       if (rc != GTX_OK)
       {

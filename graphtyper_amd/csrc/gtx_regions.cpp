@@ -11,6 +11,12 @@
 // a millisecond and what the host does around it three times that, so the stages of DIFFERENT regions overlap instead: each
 // region is a job that goes through the three stages on whichever thread of the stage is free.  Every job's text depends on that
 // job's inputs only (tests/test_regions_run.py: the same bytes as the stages called one by one).
+// Long reads (params->max_read_len > GTX_MAX_READ): every context's call scratch holds the long reads' workspaces, 4 x CUs of
+// about 1 MB (1.1 GB on 256 CUs) from the moment it is made.  Of the contexts alive at once -- a builder's, those queued for a
+// device thread, the device threads', those queued for and held by the text threads -- up to 4 + 8 + 2 + 6 + 3 of a default run,
+// so such a run has at most two builders and one built context waiting, and a context gives its scratch back to the device
+// cache as soon as its device thread is done with it (the text stage does not touch the device): at most five scratches are
+// alive ("Long reads": 9.5 GB at the peak of an 8-region run, the exact pass' slabs included).
 #include "gtx_ctx.hpp"
 #include "gtx_devmem.hpp"
 
@@ -34,6 +40,8 @@ double seconds_since(std::chrono::steady_clock::time_point t0)
 {
   return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
+
+constexpr uint32_t LONG_READ_BUILDERS = 2; // builder threads of a run with params->max_read_len > GTX_MAX_READ, at most
 
 // what a job carries from one stage to the next
 struct Built
@@ -138,7 +146,10 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
     return GTX_ERR_NO_DEVICE;
   }
   auto const t_all = std::chrono::steady_clock::now();
+  bool const long_reads = params->max_read_len > GTX_MAX_READ;
   n_builders = std::max(1u, std::min(n_builders ? n_builders : 4u, std::max(1u, n_jobs)));
+  if (long_reads)
+    n_builders = std::min(n_builders, LONG_READ_BUILDERS);
   n_device_threads = std::max(1u, std::min(n_device_threads ? n_device_threads : 2u, std::max(1u, n_jobs)));
   n_text_threads = std::max(1u, std::min(n_text_threads ? n_text_threads : 3u, std::max(1u, n_jobs)));
   uint64_t max_reads = 0;
@@ -160,7 +171,7 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
   std::string first_error;
   int first_status = GTX_OK;
   std::atomic<uint32_t> next_job{0};
-  Channel<Built> built(2 * n_builders);
+  Channel<Built> built(long_reads ? 1 : 2 * n_builders);
   Channel<Scored> scored(2 * n_text_threads);
   std::mutex stat_m;
   gtx_regions_stats s{};
@@ -340,6 +351,8 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
       }
       if (st)
         (void)hipStreamSynchronize(st); // (nothing of this region may still run when its blocks go back to the cache)
+      if (long_reads)
+        gtx::ctx_release_scratch(*c);
       (void)gtx::dev_free(d_phred);
       (void)gtx::dev_free(d_calls);
       (void)gtx::dev_free(acc.d_stat_u64);

@@ -180,8 +180,9 @@ typedef struct gtx_label
  * gtx_align_batch gives any read -- never compact ones (gtx_align_batch_planes_compact).  Reads longer than max_read_len
  * keep GTX_ST_RECORD_OVERFLOW.  The first pass takes any number of long reads; its hand-over to the exact pass holds 1 Mi
  * tasks per batch (CallScratch::EXACT_TASK_CAP, as for short reads): a batch with more long tasks than that which exceed the
- * first pass' tables leaves the rest with a table-overflow status (counted in gtx_ctx_long_pass_tasks' out[4]).  gtx_pipeline_run (80-byte plane rows: reads up to 160 bases) and gtx_regions_run make no
- * promise for long reads. */
+ * first pass' tables leaves the rest with a table-overflow status (counted in gtx_ctx_long_pass_tasks' out[4]).  gtx_pipeline_run
+ * takes every read its context aligns (GTX_MAX_READ, or max_read_len), and gtx_regions_run every read of a job whose plane rows
+ * hold it. */
 #define GTX_MAX_READ 256
 /* Largest gtx_params::max_read_len: 1 + (1000 - 32) / 31 = 32 k-mers per read, plane rows of 1 024 bases (512 bytes) */
 #define GTX_MAX_READ_LONG 1000
@@ -847,7 +848,12 @@ void gtx_reads_close(gtx_reads *);
  * context (made by gtx_scores_alloc for at least the files' samples; samples are numbered by name in the order the groups
  * bring them: position-sliced files of one sample are one sample).  chunk: records per batch; rec_words: words of a record slot; record_slots_per_thread: how many reads a thread's
  * files may hold at most (their records stay on the device for the run: a mate's item names a task of batches ago).
- * What follows is the caller's: gtx_calls_batch, gtx_vcf_records.  Reads of more than 160 bases are not taken by this loop. */
+ * What follows is the caller's: gtx_calls_batch, gtx_vcf_records.
+ * Reads of up to the context's longest (GTX_MAX_READ, or gtx_params::max_read_len): the files are decoded into nibble rows of
+ * (longest + 1) / 2 bytes, and each batch goes to the device as plane rows of max(80, 16 x ceil(L / 32)) bytes, L the longest
+ * read of that batch's records -- 80 bytes (as for reads of up to 160 bases) until a batch needs more.  A thread's staging
+ * buffers are made for 80-byte rows and grow the first time a batch needs wider ones.  A read longer than the context takes
+ * fails the run with GTX_ERR_UNSUPPORTED (the message names its length). */
 typedef struct gtx_pipeline_stats
 {
   uint64_t records, tasks, items;           /* records read; alignment tasks and score items made of them */
@@ -880,7 +886,11 @@ int gtx_pipeline_run(gtx_ctx *, const char * const * bam_paths, uint32_t n_paths
  * malloc'ed by the library, released by gtx_regions_free), text_len, status.
  * rec_words: words of a record slot (>= 8); conn_cap: as for gtx_scores_alloc.  A job whose records, score items or connections
  * ran into a capacity limit fails with GTX_ERR_CAPACITY (no text); the call returns the first failing job's status and goes
- * on with the others.  Small-variant graphs (params->is_sv_graph = 0). */
+ * on with the others.  Small-variant graphs (params->is_sv_graph = 0).
+ * Long reads: a job's plane_stride has to hold its longest read (16 bytes per 32 bases), and params->max_read_len applies to
+ * every region's context -- reads of up to GTX_MAX_READ bases by default, up to max_read_len with the long reads' passes.
+ * With max_read_len > GTX_MAX_READ every context holds ~1.1 GB of their workspaces (256 CUs) from its creation to the end of its
+ * device stage: the call then runs at most two builders with one context waiting between them and the device threads. */
 typedef struct gtx_region_job
 {
   const char * reference;            /* [reference_len] the region's bases, reference[0] at contig position region_begin */
