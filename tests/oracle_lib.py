@@ -329,6 +329,16 @@ class OracleGenotyper:
         return dict(records=int(c[0]), duplicated=int(c[1]), parked=int(c[2]))
 
 
+def default_threads():
+    """host threads a sharded oracle run may take: OMP_NUM_THREADS where it is set (a job's share of the host), else the CPUs
+    this process may run on -- not os.cpu_count(), which counts the whole host"""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", ""))
+    except ValueError:
+        n = 0
+    return n if n > 0 else len(os.sched_getaffinity(0))
+
+
 def sharded_genotyper(oracle, codes, pos, n_samples=1, samples=None, threads=None, mapq=None):
     """All reads of a large UNPAIRED, position-sorted read set through the oracle on several host threads: contiguous
     shards, one Genotyper each (the C++ calls release the GIL), summed into the first (Genotyper::merge_from).  codes:
@@ -336,7 +346,7 @@ def sharded_genotyper(oracle, codes, pos, n_samples=1, samples=None, threads=Non
     which is an optimisation of the reference, not part of the result."""
     import threading
     n, L = codes.shape
-    threads = max(1, min(threads or (os.cpu_count() or 1), 256, (n + 9999) // 10000))
+    threads = max(1, min(threads or default_threads(), 256, (n + 9999) // 10000))
     cuts = [n * k // threads for k in range(threads + 1)]
     genos = [oracle.genotyper(n_samples, 1) for _ in range(threads)]
     errors = []
