@@ -17,8 +17,10 @@
 // so such a run has at most two builders and one built context waiting, and a context gives its scratch back to the device
 // cache as soon as its device thread is done with it (the text stage does not touch the device): at most five scratches are
 // alive ("Long reads": 9.5 GB at the peak of an 8-region run, the exact pass' slabs included).
+// What a job carries from one stage to the next owns its context: a context is destroyed by whichever stage holds it when the job
+// ends or fails.  Buffers, streams and graphs are held by owners (gtx_host_loops.hpp); a stage's catch block only reports.
 #include "gtx_ctx.hpp"
-#include "gtx_devmem.hpp"
+#include "gtx_host_loops.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -36,10 +38,7 @@
 
 namespace
 {
-double seconds_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
+using gtx::seconds_since;
 
 constexpr uint32_t LONG_READ_BUILDERS = 2; // builder threads of a run with params->max_read_len > GTX_MAX_READ, at most
 
@@ -47,13 +46,13 @@ constexpr uint32_t LONG_READ_BUILDERS = 2; // builder threads of a run with para
 struct Built
 {
   uint32_t job = 0;
-  gtx_ctx * ctx = nullptr;
+  gtx::Ctx ctx;
 };
 
 struct Scored
 {
   uint32_t job = 0;
-  gtx_ctx * ctx = nullptr;
+  gtx::Ctx ctx;
   std::vector<uint32_t> gt_cov, stat_u32;
   std::vector<uint64_t> stat_u64;
   std::vector<uint8_t> phred;
@@ -185,37 +184,32 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
       if (k >= n_jobs)
         break;
       gtx_region_job & j = jobs[k];
-      gtx_ctx * c = nullptr;
       try
       {
-      auto t0 = std::chrono::steady_clock::now();
-      gtx_graph * g = nullptr;
-      int rc = gtx_graph_build(j.reference, j.reference_len, j.region_begin, j.region_end, j.records, j.n_records, j.add_all_variants, params->is_sv_graph, 0, &g);
-      gtx_graph_view view{};
-      if (rc == GTX_OK)
-        rc = gtx_graph_get_view(g, &view);
-      t_graph += seconds_since(t0);
-      t0 = std::chrono::steady_clock::now();
-      if (rc == GTX_OK)
-        rc = gtx_ctx_create(&view, params, device, &c);
-      if (g)
-        gtx_graph_destroy(g); // (the context holds its own flat copy)
-      t_ctx += seconds_since(t0);
-      if (rc != GTX_OK)
-      {
-        fail(j, rc, "gtx_regions_run: job " + std::to_string(k) + ": " + gtx_last_error(), err_m, first_error, first_status);
-        continue;
-      }
-      Built b;
-      b.job = k;
-      b.ctx = c;
-      built.put(std::move(b));
-      c = nullptr; // (the device stage's from here on)
+        auto t0 = std::chrono::steady_clock::now();
+        gtx_graph * raw_g = nullptr;
+        int rc = gtx_graph_build(j.reference, j.reference_len, j.region_begin, j.region_end, j.records, j.n_records, j.add_all_variants, params->is_sv_graph, 0, &raw_g);
+        gtx::Graph g(raw_g);
+        gtx_graph_view view{};
+        if (rc == GTX_OK)
+          rc = gtx_graph_get_view(g.get(), &view);
+        t_graph += seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        gtx_ctx * raw_c = nullptr;
+        if (rc == GTX_OK)
+          rc = gtx_ctx_create(&view, params, device, &raw_c);
+        Built b{k, gtx::Ctx(raw_c)};
+        g.reset(); // (the context holds its own flat copy)
+        t_ctx += seconds_since(t0);
+        if (rc != GTX_OK)
+        {
+          fail(j, rc, "gtx_regions_run: job " + std::to_string(k) + ": " + gtx_last_error(), err_m, first_error, first_status);
+          continue;
+        }
+        built.put(std::move(b)); // (the device stage's from here on)
       }
       catch (...)
       {
-        if (c)
-          gtx_ctx_destroy(c);
         fail_thrown(j, err_m, first_error, first_status);
       }
     }
@@ -228,171 +222,146 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
   {
     double t_dev = 0;
     uint64_t failed_total = 0, refused_total = 0, dropped_total = 0;
-    hipStream_t st = nullptr;
-    void *d_rec = nullptr, *d_fl = nullptr;
     size_t const rec_bytes = static_cast<size_t>(std::max<uint64_t>(max_reads, 1)) * 2 * rec_words * 4, fl_bytes = static_cast<size_t>(std::max<uint64_t>(max_reads, 1)) * 2;
-    void * d_failed_v = nullptr;
-    uint8_t * pinned = nullptr;
+    gtx::DevPtr<uint32_t> d_rec;
+    gtx::DevPtr<uint8_t> d_fl;
+    gtx::DevPtr<unsigned long long> d_failed;
+    gtx::PinnedPtr<uint8_t> pinned;
     size_t pinned_cap = 0;
+    // No device block may go back to the cache while the stream may still use it: the stream is declared behind the thread's
+    // blocks and each region's StreamWait behind that region's, so that on every way out of a scope, an exception's included, the
+    // stream is waited for before the blocks are freed.
+    gtx::Stream st;
     // (the record slots are recycled from region to region: a call writes the record and the flag byte of every task it is
     //  given and a region's items name that region's tasks only -- but the reverse slot of a GTX_FLAG_FORWARD_ONLY read is no task,
     //  and the count of failed records looks at every slot: the header words are zeroed on the stream in front of every region,
     //  so that a table-overflow status one region's read left there is not counted against the regions behind it)
-    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-              gtx::dev_malloc(&d_rec, rec_bytes) == hipSuccess && gtx::dev_malloc(&d_fl, fl_bytes) == hipSuccess &&
-              gtx::dev_malloc(&d_failed_v, 8) == hipSuccess && hipMemsetAsync(d_rec, 0, rec_bytes, st) == hipSuccess &&
-              hipMemsetAsync(d_fl, 0, fl_bytes, st) == hipSuccess;
-    unsigned long long * const d_failed = static_cast<unsigned long long *>(d_failed_v);
+    hipStream_t raw_st = nullptr;
+    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&raw_st, hipStreamNonBlocking) == hipSuccess;
+    st.reset(raw_st);
+    ok = ok && gtx::alloc(d_rec, rec_bytes) && gtx::alloc(d_fl, fl_bytes) && gtx::alloc(d_failed, 8) && hipMemsetAsync(d_rec.get(), 0, rec_bytes, st.get()) == hipSuccess &&
+         hipMemsetAsync(d_fl.get(), 0, fl_bytes, st.get()) == hipSuccess;
     Built b;
     while (built.get(b))
     {
       gtx_region_job & j = jobs[b.job];
-      gtx_ctx * c = b.ctx;
-      void *d_phred = nullptr, *d_calls = nullptr;
-      gtx_score_buffers acc{};
-      bool blocks_held = true; // (d_phred, d_calls and the accumulator block are this iteration's until they went back to the cache)
       try
       {
-      auto const t0 = std::chrono::steady_clock::now();
-      Scored out;
-      out.job = b.job;
-      out.ctx = c;
-      int rc = ok ? GTX_OK : GTX_ERR_HIP;
-      std::string what = ok ? "" : "gtx_regions_run: a device thread could not get its stream / record slots";
-      gtx_score_layout lay{};
-      if (rc == GTX_OK)
-        rc = gtx_ctx_score_layout(c, &lay);
-      uint64_t const n_phred = static_cast<uint64_t>(n_samples) * lay.total_tri, n_calls = static_cast<uint64_t>(n_samples) * lay.n_hap;
-      // Everything of a region is queued on the thread's stream and waited for ONCE: the accumulator block zeroed on the stream, the
-      // three launches' work, the count of records that are a table-overflow status, and the results -- into one pinned buffer (a copy
-      // into pageable memory waits for the device before it returns: six of them, the overflow count's own wait and the error flag's
-      // were eight round trips per region; a device thread spent 1.2 ms on a region whose kernels take 0.3).
-      if (rc == GTX_OK && (rc = gtx::scores_alloc_on(c, n_samples, conn_cap, &acc, nullptr, st)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK && (gtx::dev_malloc(&d_phred, std::max<uint64_t>(n_phred, 1)) != hipSuccess ||
-                           gtx::dev_malloc(&d_calls, std::max<uint64_t>(n_calls, 1) * sizeof(gtx_sample_call)) != hipSuccess))
-      {
-        rc = GTX_ERR_HIP;
-        what = "gtx_regions_run: device memory for the calls";
-      }
-      if (rc == GTX_OK && j.n_reads && hipMemsetAsync(d_fl, 0, static_cast<size_t>(j.n_reads) * 2, st) != hipSuccess) // (the side bytes: two per read, all of them looked at)
-      {
-        rc = GTX_ERR_HIP;
-        what = "gtx_regions_run: hipMemsetAsync";
-      }
-      if (rc == GTX_OK && j.n_reads && (rc = gtx::records_clear_enqueue(c, static_cast<uint32_t *>(d_rec), rec_words, j.n_reads, st)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK && j.n_reads &&
-          (rc = gtx_align_batch_planes(c, j.d_planes, j.plane_stride, j.d_meta, static_cast<uint32_t>(j.n_reads), static_cast<uint32_t *>(d_rec), rec_words,
-                                       static_cast<uint8_t *>(d_fl), st)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK && j.n_items &&
-          (rc = gtx_score_batch_flags(c, j.d_items, static_cast<uint32_t>(j.n_items), static_cast<uint32_t const *>(d_rec), rec_words, static_cast<uint8_t const *>(d_fl), &acc,
-                                      st)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK && (rc = gtx_calls_batch(c, &acc, static_cast<uint8_t *>(d_phred), static_cast<gtx_sample_call *>(d_calls), st)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK && j.n_reads && (rc = gtx::records_failed_enqueue(c, static_cast<uint32_t const *>(d_rec), rec_words, j.n_reads, st, d_failed)) != GTX_OK)
-        what = gtx_last_error();
-      if (rc == GTX_OK)
-      {
-        size_t const b_cov = static_cast<size_t>(n_samples) * lay.total_allele * 4, b_u64 = (static_cast<size_t>(lay.n_hap) + 2ull * lay.total_allele) * 8,
-                     b_u32 = (static_cast<size_t>(lay.n_hap) + 6ull * lay.total_allele) * 4, b_phred = n_phred, b_calls = n_calls * sizeof(gtx_sample_call);
-        auto up = [](size_t x) { return (x + 63) & ~static_cast<size_t>(63); };
-        size_t const o_cov = 64, o_u64 = o_cov + up(b_cov), o_u32 = o_u64 + up(b_u64), o_phred = o_u32 + up(b_u32), o_calls = o_phred + up(b_phred),
-                     total = o_calls + up(b_calls);
-        if (total > pinned_cap)
+        auto const t0 = std::chrono::steady_clock::now();
+        Scored out;
+        out.job = b.job;
+        out.ctx = std::move(b.ctx); // (destroyed when this iteration ends, unless it goes on to the text stage)
+        gtx_ctx * const c = out.ctx.get();
+        int rc = ok ? GTX_OK : GTX_ERR_HIP;
+        std::string what = ok ? "" : "gtx_regions_run: a device thread could not get its stream / record slots";
+        gtx_score_layout lay{};
+        if (rc == GTX_OK)
+          rc = gtx_ctx_score_layout(c, &lay);
+        uint64_t const n_phred = static_cast<uint64_t>(n_samples) * lay.total_tri, n_calls = static_cast<uint64_t>(n_samples) * lay.n_hap;
         {
-          if (pinned)
-            (void)hipHostFree(pinned);
-          pinned = nullptr;
-          pinned_cap = 0;
-          if (hipHostMalloc(reinterpret_cast<void **>(&pinned), 2 * total) == hipSuccess)
-            pinned_cap = 2 * total;
-        }
-        // ([0..1] connections appended / dropped, [2] the context's error flag, [4..5] the failed-record count)
-        auto down = [&](size_t at, void const * src, size_t bytes) { return bytes == 0 || hipMemcpyAsync(pinned + at, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess; };
-        if (!pinned || !down(0, acc.d_conn_count, 8) || !down(8, c->d_error_flag, 4) || !(j.n_reads == 0 || down(16, d_failed, 8)) || !down(o_cov, acc.d_gt_cov, b_cov) ||
-            !down(o_u64, acc.d_stat_u64, b_u64) || !down(o_u32, acc.d_stat_u32, b_u32) || !down(o_phred, d_phred, b_phred) || !down(o_calls, d_calls, b_calls) ||
-            hipStreamSynchronize(st) != hipSuccess)
-        {
-          rc = GTX_ERR_HIP;
-          what = "gtx_regions_run: device to host copy";
-        }
-        else
-        {
-          out.gt_cov.resize(b_cov / 4);
-          out.stat_u64.resize(b_u64 / 8);
-          out.stat_u32.resize(b_u32 / 4);
-          out.phred.resize(b_phred);
-          out.calls.resize(n_calls);
-          std::memcpy(out.gt_cov.data(), pinned + o_cov, b_cov);
-          std::memcpy(out.stat_u64.data(), pinned + o_u64, b_u64);
-          std::memcpy(out.stat_u32.data(), pinned + o_u32, b_u32);
-          std::memcpy(out.phred.data(), pinned + o_phred, b_phred);
-          std::memcpy(out.calls.data(), pinned + o_calls, b_calls);
-          // what a capacity limit dropped makes the text a wrong result: the job fails instead
-          uint32_t conn[2], refused = 0;
-          uint64_t failed = 0;
-          std::memcpy(conn, pinned, 8);
-          std::memcpy(&refused, pinned + 8, 4);
-          if (j.n_reads)
-            std::memcpy(&failed, pinned + 16, 8);
-          if (failed || refused || conn[1])
+          gtx::DevPtr<uint8_t> d_phred;
+          gtx::DevPtr<gtx_sample_call> d_calls;
+          gtx::DevPtr<> acc_block; // (acc's pointers are into this one block)
+          gtx::StreamWait region_done(st.get());
+          gtx_score_buffers acc{};
+          // Everything of a region is queued on the thread's stream and waited for ONCE: the accumulator block zeroed on the stream, the
+          // three launches' work, the count of records that are a table-overflow status, and the results -- into one pinned buffer (a copy
+          // into pageable memory waits for the device before it returns: six of them, the overflow count's own wait and the error flag's
+          // were eight round trips per region; a device thread spent 1.2 ms on a region whose kernels take 0.3).
+          if (rc == GTX_OK)
           {
-            rc = GTX_ERR_CAPACITY;
-            what = "gtx_regions_run: job " + std::to_string(b.job) + " is incomplete -- " + std::to_string(failed) + " records with a table-overflow status, " +
-                   std::to_string(refused) + " score items refused, " + std::to_string(conn[1]) + " connections beyond the log";
-            failed_total += failed;
-            refused_total += refused;
-            dropped_total += conn[1];
+            rc = gtx::scores_alloc_on(c, n_samples, conn_cap, &acc, nullptr, st.get());
+            acc_block.reset(acc.d_stat_u64);
+            if (rc != GTX_OK)
+              what = gtx_last_error();
           }
+          if (rc == GTX_OK &&
+              (!gtx::alloc(d_phred, std::max<uint64_t>(n_phred, 1)) || !gtx::alloc(d_calls, std::max<uint64_t>(n_calls, 1) * sizeof(gtx_sample_call))))
+          {
+            rc = GTX_ERR_HIP;
+            what = "gtx_regions_run: device memory for the calls";
+          }
+          if (rc == GTX_OK && j.n_reads && hipMemsetAsync(d_fl.get(), 0, static_cast<size_t>(j.n_reads) * 2, st.get()) != hipSuccess) // (the side bytes: two per read, all of them looked at)
+          {
+            rc = GTX_ERR_HIP;
+            what = "gtx_regions_run: hipMemsetAsync";
+          }
+          if (rc == GTX_OK && j.n_reads && (rc = gtx::records_clear_enqueue(c, d_rec.get(), rec_words, j.n_reads, st.get())) != GTX_OK)
+            what = gtx_last_error();
+          if (rc == GTX_OK && j.n_reads &&
+              (rc = gtx_align_batch_planes(c, j.d_planes, j.plane_stride, j.d_meta, static_cast<uint32_t>(j.n_reads), d_rec.get(), rec_words, d_fl.get(), st.get())) != GTX_OK)
+            what = gtx_last_error();
+          if (rc == GTX_OK && j.n_items && (rc = gtx_score_batch_flags(c, j.d_items, static_cast<uint32_t>(j.n_items), d_rec.get(), rec_words, d_fl.get(), &acc, st.get())) != GTX_OK)
+            what = gtx_last_error();
+          if (rc == GTX_OK && (rc = gtx_calls_batch(c, &acc, d_phred.get(), d_calls.get(), st.get())) != GTX_OK)
+            what = gtx_last_error();
+          if (rc == GTX_OK && j.n_reads && (rc = gtx::records_failed_enqueue(c, d_rec.get(), rec_words, j.n_reads, st.get(), d_failed.get())) != GTX_OK)
+            what = gtx_last_error();
+          if (rc == GTX_OK)
+          {
+            size_t const b_cov = static_cast<size_t>(n_samples) * lay.total_allele * 4, b_u64 = (static_cast<size_t>(lay.n_hap) + 2ull * lay.total_allele) * 8,
+                         b_u32 = (static_cast<size_t>(lay.n_hap) + 6ull * lay.total_allele) * 4, b_phred = n_phred, b_calls = n_calls * sizeof(gtx_sample_call);
+            auto up = [](size_t x) { return (x + 63) & ~static_cast<size_t>(63); };
+            size_t const o_cov = 64, o_u64 = o_cov + up(b_cov), o_u32 = o_u64 + up(b_u64), o_phred = o_u32 + up(b_u32), o_calls = o_phred + up(b_phred),
+                         total = o_calls + up(b_calls);
+            if (total > pinned_cap)
+              pinned_cap = gtx::alloc(pinned, 2 * total) ? 2 * total : 0;
+            // ([0..1] connections appended / dropped, [2] the context's error flag, [4..5] the failed-record count)
+            auto down = [&](size_t at, void const * src, size_t bytes)
+            { return bytes == 0 || hipMemcpyAsync(pinned.get() + at, src, bytes, hipMemcpyDeviceToHost, st.get()) == hipSuccess; };
+            if (!pinned || !down(0, acc.d_conn_count, 8) || !down(8, c->d_error_flag, 4) || !(j.n_reads == 0 || down(16, d_failed.get(), 8)) ||
+                !down(o_cov, acc.d_gt_cov, b_cov) || !down(o_u64, acc.d_stat_u64, b_u64) || !down(o_u32, acc.d_stat_u32, b_u32) ||
+                !down(o_phred, d_phred.get(), b_phred) || !down(o_calls, d_calls.get(), b_calls) || hipStreamSynchronize(st.get()) != hipSuccess)
+            {
+              rc = GTX_ERR_HIP;
+              what = "gtx_regions_run: device to host copy";
+            }
+            else
+            {
+              out.gt_cov.resize(b_cov / 4);
+              out.stat_u64.resize(b_u64 / 8);
+              out.stat_u32.resize(b_u32 / 4);
+              out.phred.resize(b_phred);
+              out.calls.resize(n_calls);
+              std::memcpy(out.gt_cov.data(), pinned.get() + o_cov, b_cov);
+              std::memcpy(out.stat_u64.data(), pinned.get() + o_u64, b_u64);
+              std::memcpy(out.stat_u32.data(), pinned.get() + o_u32, b_u32);
+              std::memcpy(out.phred.data(), pinned.get() + o_phred, b_phred);
+              std::memcpy(out.calls.data(), pinned.get() + o_calls, b_calls);
+              // what a capacity limit dropped makes the text a wrong result: the job fails instead
+              uint32_t conn[2], refused = 0;
+              uint64_t failed = 0;
+              std::memcpy(conn, pinned.get(), 8);
+              std::memcpy(&refused, pinned.get() + 8, 4);
+              if (j.n_reads)
+                std::memcpy(&failed, pinned.get() + 16, 8);
+              if (failed || refused || conn[1])
+              {
+                rc = GTX_ERR_CAPACITY;
+                what = "gtx_regions_run: job " + std::to_string(b.job) + " is incomplete -- " + gtx::incomplete_counts(failed, refused, conn[1]);
+                failed_total += failed;
+                refused_total += refused;
+                dropped_total += conn[1];
+              }
+            }
+          }
+          region_done.reset(); // (waits for the stream: nothing of this region runs any more)
+          if (long_reads)
+            gtx::ctx_release_scratch(*c);
+        } // (this region's blocks go back to the cache)
+        t_dev += seconds_since(t0);
+        if (rc != GTX_OK)
+        {
+          fail(j, rc, what, err_m, first_error, first_status);
+          continue;
         }
-      }
-      if (st)
-        (void)hipStreamSynchronize(st); // (nothing of this region may still run when its blocks go back to the cache)
-      if (long_reads)
-        gtx::ctx_release_scratch(*c);
-      (void)gtx::dev_free(d_phred);
-      (void)gtx::dev_free(d_calls);
-      (void)gtx::dev_free(acc.d_stat_u64);
-      blocks_held = false;
-      t_dev += seconds_since(t0);
-      if (rc != GTX_OK)
-      {
-        gtx_ctx_destroy(c);
-        c = nullptr;
-        fail(j, rc, what, err_m, first_error, first_status);
-        continue;
-      }
-      scored.put(std::move(out));
-      c = nullptr; // (the text stage's from here on)
+        scored.put(std::move(out)); // (the text stage's from here on)
       }
       catch (...)
       {
-        if (st)
-          (void)hipStreamSynchronize(st);
-        if (blocks_held)
-        {
-          (void)gtx::dev_free(d_phred);
-          (void)gtx::dev_free(d_calls);
-          (void)gtx::dev_free(acc.d_stat_u64);
-        }
-        if (c)
-          gtx_ctx_destroy(c);
         fail_thrown(j, err_m, first_error, first_status);
       }
     }
-    if (st)
-    {
-      (void)hipStreamSynchronize(st);
-      (void)hipStreamDestroy(st);
-    }
-    (void)gtx::dev_free(d_rec);
-    (void)gtx::dev_free(d_fl);
-    (void)gtx::dev_free(d_failed_v);
-    if (pinned)
-      (void)hipHostFree(pinned);
     std::lock_guard<std::mutex> lock(stat_m);
     s.device_s += t_dev;
     s.records_failed += failed_total;
@@ -403,63 +372,52 @@ extern "C" int gtx_regions_run(gtx_region_job * jobs, uint32_t n_jobs, const gtx
   auto texter = [&]
   {
     double t_text = 0;
-    (void)hipSetDevice(device); // (gtx_ctx_destroy gives the context's device memory back)
+    (void)hipSetDevice(device); // (a context that ends here gives its device memory back)
     Scored sc;
     while (scored.get(sc))
     {
       gtx_region_job & j = jobs[sc.job];
-      char * text = nullptr;
-      bool ctx_held = true;
       try
       {
-      auto const t0 = std::chrono::steady_clock::now();
-      gtx_vcf_request rq{};
-      rq.contig = contig;
-      rq.sample_names = sample_names;
-      rq.n_samples = n_samples;
-      rq.region_begin = j.vcf_begin;
-      rq.region_end = j.vcf_end;
-      rq.filter_zero_qual = j.filter_zero_qual;
-      rq.gt_cov = sc.gt_cov.data();
-      rq.stat_u64 = sc.stat_u64.data();
-      rq.stat_u32 = sc.stat_u32.data();
-      rq.phred = sc.phred.data();
-      rq.calls = sc.calls.data();
-      gtx_score_layout lay{};
-      (void)gtx_ctx_score_layout(sc.ctx, &lay);
-      uint64_t cap = 4096 + static_cast<uint64_t>(lay.n_hap) * (600 + 40ull * n_samples), len = 0;
-      text = static_cast<char *>(std::malloc(cap));
-      int rc = text ? gtx_vcf_records(sc.ctx, &rq, text, cap, &len) : GTX_ERR_CAPACITY;
-      if (rc == GTX_OK && len > cap) // (the estimate was short: once more with what it takes)
-      {
-        std::free(text);
-        cap = len;
-        text = static_cast<char *>(std::malloc(cap));
-        rc = text ? gtx_vcf_records(sc.ctx, &rq, text, cap, &len) : GTX_ERR_CAPACITY;
-      }
-      sc.ctx->quiet = true; // (its device thread waited for the stream the region ran on)
-      gtx_ctx_destroy(sc.ctx);
-      ctx_held = false;
-      t_text += seconds_since(t0);
-      if (rc != GTX_OK)
-      {
-        bool const had_text = text != nullptr;
-        std::free(text);
-        text = nullptr;
-        fail(j, rc, "gtx_regions_run: job " + std::to_string(sc.job) + ": " + (had_text ? gtx_last_error() : "out of memory"), err_m, first_error, first_status);
-        continue;
-      }
-      j.text = text;
-      j.text_len = len;
+        auto const t0 = std::chrono::steady_clock::now();
+        gtx::Ctx c = std::move(sc.ctx);
+        c->quiet = true; // (its device thread waited for the stream the region ran on)
+        gtx_vcf_request rq{};
+        rq.contig = contig;
+        rq.sample_names = sample_names;
+        rq.n_samples = n_samples;
+        rq.region_begin = j.vcf_begin;
+        rq.region_end = j.vcf_end;
+        rq.filter_zero_qual = j.filter_zero_qual;
+        rq.gt_cov = sc.gt_cov.data();
+        rq.stat_u64 = sc.stat_u64.data();
+        rq.stat_u32 = sc.stat_u32.data();
+        rq.phred = sc.phred.data();
+        rq.calls = sc.calls.data();
+        gtx_score_layout lay{};
+        (void)gtx_ctx_score_layout(c.get(), &lay);
+        uint64_t cap = 4096 + static_cast<uint64_t>(lay.n_hap) * (600 + 40ull * n_samples), len = 0;
+        std::unique_ptr<char, gtx::Free<std::free>> text(static_cast<char *>(std::malloc(cap)));
+        int rc = text ? gtx_vcf_records(c.get(), &rq, text.get(), cap, &len) : GTX_ERR_CAPACITY;
+        if (rc == GTX_OK && len > cap) // (the estimate was short: once more with what it takes)
+        {
+          text.reset();
+          cap = len;
+          text.reset(static_cast<char *>(std::malloc(cap)));
+          rc = text ? gtx_vcf_records(c.get(), &rq, text.get(), cap, &len) : GTX_ERR_CAPACITY;
+        }
+        c.reset();
+        t_text += seconds_since(t0);
+        if (rc != GTX_OK)
+        {
+          fail(j, rc, "gtx_regions_run: job " + std::to_string(sc.job) + ": " + (text ? gtx_last_error() : "out of memory"), err_m, first_error, first_status);
+          continue;
+        }
+        j.text = text.release();
+        j.text_len = len;
       }
       catch (...)
       {
-        std::free(text);
-        if (ctx_held)
-        {
-          sc.ctx->quiet = true;
-          gtx_ctx_destroy(sc.ctx);
-        }
         fail_thrown(j, err_m, first_error, first_status);
       }
     }
