@@ -15,6 +15,7 @@
 // CRAM (needs htslib's codecs).
 #include "gtx_ctx.hpp"
 #include "gtx_inflate.hpp"
+#include "gtx_inflate_host.hpp"
 
 #include <zlib.h>
 
@@ -33,6 +34,16 @@
 #include <thread>
 #include <unordered_map>
 #include <vector>
+
+gtx::InflateDeviceOps const * gtx::inflate_device_ops = nullptr;
+
+namespace
+{
+// what became of the members of readers that asked for the device (process-wide, gtx_reads_inflate_counts)
+std::atomic<uint64_t> g_members_device{0};   // inflated by the device, status ok
+std::atomic<uint64_t> g_members_fallback{0}; // taken by the device's team and then inflated on the host: a status but ok, or a launch that failed
+std::atomic<uint64_t> g_members_reader{0};   // inflated by their reader before the team had started on them
+} // namespace
 
 namespace
 {
@@ -235,6 +246,184 @@ private:
   std::atomic<bool> stop_flag_{false};
 };
 
+// The device's team: ONE thread per process that takes what the readers that asked for the device (Bgzf::use_device) have
+// queued -- everything that is there, a launch wants thousands of members --, gathers the compressed members into a pinned block,
+// has them inflated in one launch (gtx_inflate_dev.hip) and hands the bytes out.  A member the device does not give "ok" goes
+// through inflate_member on this thread: the host's verdict is the one that counts, so a damaged file fails as it does without
+// the device.  As with the host's team, a reader that needs a member nobody has started on inflates it itself.
+class DeviceInflateTeam
+{
+public:
+  static constexpr size_t MAX_BATCH = 16384; // members per launch (1 GB of output at most)
+  // 0, or the status and message (gtx_last_error) of what failed; a team on another device is alive: GTX_ERR_UNSUPPORTED
+  static int acquire(int device)
+  {
+    std::lock_guard<std::mutex> lock(gate());
+    if (users() > 0)
+    {
+      if (self()->device_ != device)
+      {
+        gtx::g_last_error = "gtx_reads_set_inflate_device: readers of this process inflate on device " + std::to_string(self()->device_) + " already";
+        return GTX_ERR_UNSUPPORTED;
+      }
+      ++users();
+      return GTX_OK;
+    }
+    if (!gtx::inflate_device_ops)
+    {
+      gtx::g_last_error = "gtx_reads_set_inflate_device: this build holds no device inflater";
+      return GTX_ERR_NO_DEVICE;
+    }
+    gtx_inflate * h = nullptr;
+    int const rc = gtx::inflate_device_ops->create(device, &h);
+    if (rc != GTX_OK)
+      return rc;
+    self() = new DeviceInflateTeam(device, h);
+    users() = 1;
+    return GTX_OK;
+  }
+  static void release()
+  {
+    DeviceInflateTeam * gone = nullptr;
+    {
+      std::lock_guard<std::mutex> lock(gate());
+      if (--users() == 0)
+      {
+        gone = self();
+        self() = nullptr;
+      }
+    }
+    delete gone;
+  }
+  static void submit(InflateJob * const * jobs, size_t n)
+  {
+    DeviceInflateTeam * t = self();
+    if (!t || n == 0)
+      return;
+    {
+      std::lock_guard<std::mutex> lock(t->m_);
+      t->queue_.insert(t->queue_.end(), jobs, jobs + n);
+    }
+    t->cv_.notify_one();
+  }
+  static void forget(InflateJob const * first, InflateJob const * last)
+  {
+    DeviceInflateTeam * t = self();
+    if (!t)
+      return;
+    std::lock_guard<std::mutex> lock(t->m_);
+    t->queue_.erase(std::remove_if(t->queue_.begin(), t->queue_.end(), [&](InflateJob * j) { return j >= first && j < last; }), t->queue_.end());
+  }
+
+private:
+  DeviceInflateTeam(int device, gtx_inflate * h) : device_(device), h_(h), worker_([this] { run(); }) {}
+  ~DeviceInflateTeam()
+  {
+    {
+      std::lock_guard<std::mutex> lock(m_);
+      stop_ = true;
+    }
+    cv_.notify_all();
+    worker_.join();
+    gtx::inflate_device_ops->destroy(h_);
+  }
+  void run()
+  {
+    static bool const check_crc = !(std::getenv("GTX_BGZF_CRC") && std::getenv("GTX_BGZF_CRC")[0] == '0');
+    gtx::InflateDeviceOps const & ops = *gtx::inflate_device_ops;
+    using Pinned = std::unique_ptr<uint8_t, void (*)(void *)>;
+    Pinned pin_in(nullptr, ops.pinned_free), pin_out(nullptr, ops.pinned_free);
+    auto grow = [&](Pinned & p, size_t & cap, uint64_t want) {
+      if (want <= cap)
+        return true;
+      p.reset();
+      p.reset(static_cast<uint8_t *>(ops.pinned_alloc(h_, want + want / 4)));
+      cap = p ? want + want / 4 : 0;
+      return cap != 0;
+    };
+    size_t in_cap = 0, out_cap = 0;
+    std::vector<InflateJob *> batch;
+    std::vector<gtx_inflate_member> members;
+    std::vector<uint32_t> status;
+    for (;;)
+    {
+      batch.clear();
+      {
+        std::unique_lock<std::mutex> lock(m_);
+        cv_.wait(lock, [this] { return stop_ || !queue_.empty(); });
+        if (stop_)
+          return;
+        while (!queue_.empty() && batch.size() < MAX_BATCH)
+        {
+          InflateJob * j = queue_.front();
+          queue_.pop_front();
+          int expect = 0;
+          if (j->state.compare_exchange_strong(expect, 1)) // (else its reader got there first)
+            batch.push_back(j);
+        }
+      }
+      if (batch.empty())
+        continue;
+      members.resize(batch.size());
+      status.assign(batch.size(), GTX_INFLATE_BAD_MEMBER);
+      uint64_t in_size = 0, out_size = 0;
+      for (size_t i = 0; i < batch.size(); ++i)
+      {
+        members[i] = gtx_inflate_member{in_size, out_size, static_cast<uint32_t>(batch[i]->clen), static_cast<uint32_t>(batch[i]->data.size()), 0, 0};
+        std::memcpy(&members[i].crc32, batch[i]->comp.data() + batch[i]->clen, 4);
+        in_size += static_cast<uint64_t>(batch[i]->clen);
+        out_size += batch[i]->data.size();
+      }
+      bool ok = grow(pin_in, in_cap, in_size) && grow(pin_out, out_cap, out_size);
+      if (ok)
+      {
+        for (size_t i = 0; i < batch.size(); ++i)
+          std::memcpy(pin_in.get() + members[i].in_off, batch[i]->comp.data(), members[i].in_len);
+        ok = ops.batch(h_, pin_in.get(), in_size, members.data(), static_cast<uint32_t>(batch.size()), pin_out.get(), out_size, status.data(),
+                                     check_crc) == GTX_OK;
+      }
+      for (size_t i = 0; i < batch.size(); ++i)
+      {
+        InflateJob & j = *batch[i];
+        if (!ok || status[i] != GTX_INFLATE_OK)
+        {
+          g_members_fallback.fetch_add(1, std::memory_order_relaxed);
+          inflate_member(j); // (the host's decoders, and their verdict)
+          continue;
+        }
+        std::memcpy(j.data.data(), pin_out.get() + members[i].out_off, members[i].out_len);
+        g_members_device.fetch_add(1, std::memory_order_relaxed);
+        j.ok = true;
+        std::lock_guard<std::mutex> lock(j.m);
+        j.state.store(2);
+        j.cv.notify_all();
+      }
+    }
+  }
+  static std::mutex & gate()
+  {
+    static std::mutex m;
+    return m;
+  }
+  static int & users()
+  {
+    static int n = 0;
+    return n;
+  }
+  static DeviceInflateTeam *& self()
+  {
+    static DeviceInflateTeam * t = nullptr;
+    return t;
+  }
+  int device_;
+  gtx_inflate * h_;
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::deque<InflateJob *> queue_;
+  bool stop_ = false;
+  std::thread worker_; // (last: it runs as soon as it is made)
+};
+
 class Bgzf
 {
 public:
@@ -245,7 +434,8 @@ public:
     if (fp_)
     {
       InflateTeam::acquire();
-      ring_.reset(new InflateJob[RING]);
+      ring_n_ = RING;
+      ring_.reset(new InflateJob[ring_n_]);
     }
     return fp_ != nullptr;
   }
@@ -256,6 +446,9 @@ public:
       drain();
       ring_.reset();
       InflateTeam::release();
+      if (on_device_)
+        DeviceInflateTeam::release();
+      on_device_ = false;
       std::fclose(fp_);
     }
     fp_ = nullptr;
@@ -289,6 +482,38 @@ public:
       return false;
     at_ = voffset & 0xFFFFu;
     return true;
+  }
+  // From here on the members go to the device's team, and the reader keeps more of them in flight: a launch wants thousands of
+  // members from all readers together, not 32 from each.  What has been read ahead stays, in order.  0 or a gtx status.
+  int use_device(int device)
+  {
+    if (!fp_ || on_device_)
+      return fp_ ? GTX_OK : GTX_ERR_ARG;
+    int const rc = DeviceInflateTeam::acquire(device);
+    if (rc != GTX_OK)
+      return rc;
+    unsigned deep = 256;
+    if (char const * e = std::getenv("GTX_BGZF_DEVICE_RING"))
+      deep = static_cast<unsigned>(std::min(65536, std::max<int>(RING, std::atoi(e))));
+    std::unique_ptr<InflateJob[]> ring(new InflateJob[deep]);
+    // the members in flight are finished where they are and move to the front of the deeper ring
+    uint64_t n = 0;
+    for (uint64_t k = head_; k < tail_ && n < deep; ++k, ++n)
+    {
+      InflateJob & j = ring_[k % ring_n_];
+      finish(j);
+      ring[n].comp.swap(j.comp);
+      ring[n].data.swap(j.data);
+      ring[n].clen = j.clen;
+      ring[n].ok = j.ok;
+    }
+    InflateTeam::forget(ring_.get(), ring_.get() + ring_n_);
+    ring_.swap(ring);
+    ring_n_ = deep;
+    head_ = 0;
+    tail_ = n;
+    on_device_ = true;
+    return GTX_OK;
   }
 
 private:
@@ -342,13 +567,14 @@ private:
   // reads members ahead until the ring is full or the file ends / breaks (which is reported when the caller gets there)
   void fill()
   {
-    if (tail_ - head_ > RING / 2) // (refilled by halves: the members go to the team in one hand-over)
+    if (tail_ - head_ > ring_n_ / 2) // (refilled by halves: the members go to the team in one hand-over)
       return;
-    InflateJob * fresh[RING];
+    fresh_.resize(ring_n_);
+    InflateJob ** const fresh = fresh_.data();
     size_t n = 0;
-    while (ahead_ == MORE && tail_ - head_ < RING)
+    while (ahead_ == MORE && tail_ - head_ < ring_n_)
     {
-      InflateJob & j = ring_[tail_ % RING];
+      InflateJob & j = ring_[tail_ % ring_n_];
       Ahead const a = read_member(j);
       if (a != MORE)
       {
@@ -359,7 +585,10 @@ private:
       ++tail_;
       fresh[n++] = &j;
     }
-    InflateTeam::submit(fresh, n);
+    if (on_device_)
+      DeviceInflateTeam::submit(fresh, n);
+    else
+      InflateTeam::submit(fresh, n);
   }
   bool next_block()
   {
@@ -370,21 +599,30 @@ private:
         return fail();
       return false; // end of the file
     }
-    InflateJob & j = ring_[head_ % RING];
-    int expect = 0;
-    if (j.state.compare_exchange_strong(expect, 1))
-      inflate_member(j); // (nobody has started on it: this thread does)
-    else
-    {
-      std::unique_lock<std::mutex> lock(j.m);
-      j.cv.wait(lock, [&] { return j.state.load() == 2; });
-    }
+    InflateJob & j = ring_[head_ % ring_n_];
+    finish(j);
     ++head_;
     if (!j.ok)
       return fail();
     data_.swap(j.data);
     at_ = 0;
     return true;
+  }
+  // the member is inflated when this returns: by this thread when nobody has started on it
+  void finish(InflateJob & j) const
+  {
+    int expect = 0;
+    if (j.state.compare_exchange_strong(expect, 1))
+    {
+      if (on_device_)
+        g_members_reader.fetch_add(1, std::memory_order_relaxed);
+      inflate_member(j);
+    }
+    else
+    {
+      std::unique_lock<std::mutex> lock(j.m);
+      j.cv.wait(lock, [&] { return j.state.load() == 2; });
+    }
   }
   // nothing of this reader is in flight or queued afterwards
   void drain()
@@ -393,14 +631,17 @@ private:
       return;
     for (; head_ < tail_; ++head_)
     {
-      InflateJob & j = ring_[head_ % RING];
+      InflateJob & j = ring_[head_ % ring_n_];
       int expect = 0;
       if (j.state.compare_exchange_strong(expect, 2))
         continue; // (never started)
       std::unique_lock<std::mutex> lock(j.m);
       j.cv.wait(lock, [&] { return j.state.load() == 2; });
     }
-    InflateTeam::forget(ring_.get(), ring_.get() + RING);
+    if (on_device_)
+      DeviceInflateTeam::forget(ring_.get(), ring_.get() + ring_n_);
+    else
+      InflateTeam::forget(ring_.get(), ring_.get() + ring_n_);
     head_ = tail_ = 0;
     ahead_ = MORE;
   }
@@ -411,6 +652,9 @@ private:
   }
   std::FILE * fp_ = nullptr;
   std::unique_ptr<InflateJob[]> ring_;
+  uint64_t ring_n_ = RING;       // RING, or what use_device chose
+  bool on_device_ = false;       // the members go to the device's team
+  std::vector<InflateJob *> fresh_;
   uint64_t head_ = 0, tail_ = 0; // members taken / read ahead
   Ahead ahead_ = MORE;
   std::vector<uint8_t> data_;
@@ -1031,6 +1275,33 @@ extern "C" int gtx_reads_open(const char * const * bam_paths, uint32_t n_paths, 
     }
   }
   *out = r;
+  return GTX_OK;
+}
+
+extern "C" int gtx_reads_set_inflate_device(gtx_reads * r, int device)
+{
+  if (!r)
+  {
+    gtx::g_last_error = "gtx_reads_set_inflate_device: bad argument";
+    return GTX_ERR_ARG;
+  }
+  for (auto & f : r->files)
+  {
+    int const rc = f->fp.use_device(device);
+    if (rc != GTX_OK)
+      return rc; // (the files before this one stay with the device, the others with the host: every one of them reads on)
+  }
+  return GTX_OK;
+}
+
+extern "C" int gtx_reads_inflate_counts(uint64_t * by_device, uint64_t * fell_back, uint64_t * by_reader)
+{
+  if (by_device)
+    *by_device = g_members_device.load();
+  if (fell_back)
+    *fell_back = g_members_fallback.load();
+  if (by_reader)
+    *by_reader = g_members_reader.load();
   return GTX_OK;
 }
 

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -331,11 +332,15 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
   std::vector<Worker> team(n_threads);
   for (uint32_t f = 0; f < n_paths; ++f)
     team[f % n_threads].paths.push_back(bam_paths[f] ? bam_paths[f] : "");
+  // GTX_BGZF_DEVICE=1: the readers' BGZF members are inflated by the context's device (gtx_reads_set_inflate_device)
+  char const * const env_dev = std::getenv("GTX_BGZF_DEVICE");
+  bool const bgzf_on_device = env_dev && env_dev[0] != '\0' && std::strcmp(env_dev, "0") != 0;
+  int const device = c->device;
   // the files are opened first (one thread each): the samples' numbers need every group's names
   {
     std::vector<std::thread> openers;
     for (Worker & w : team)
-      openers.emplace_back([&w, region]
+      openers.emplace_back([&w, region, bgzf_on_device, device]
       {
         std::vector<char const *> p;
         for (auto const & s : w.paths)
@@ -343,6 +348,8 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
         gtx_reads * raw = nullptr;
         w.status = gtx_reads_open(p.data(), static_cast<uint32_t>(p.size()), region, &raw);
         w.reads.reset(raw);
+        if (w.status == GTX_OK && bgzf_on_device)
+          w.status = gtx_reads_set_inflate_device(raw, device);
         if (w.status != GTX_OK)
           w.error = gtx_last_error();
         else

@@ -31,7 +31,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_pack_planes", "gtx_reads_to_planes", "gtx_align_batch_planes", "gtx_align_batch_planes_staged", "gtx_stream_set_planes", "gtx_device_cache_release",
            "gtx_disc_create", "gtx_disc_destroy", "gtx_disc_events_batch", "gtx_disc_first_pass", "gtx_vcf_header", "gtx_bgzf_compress",
            "gtx_shrink_params_default", "gtx_bam_shrink", "gtx_inflate_raw", "gtx_tabix_build", "gtx_tabix_start", "gtx_pipeline_run", "gtx_regions_run", "gtx_regions_free", "gtx_bam_shrink_multi", "gtx_disc_first_pass_haplotypes", "gtx_disc_merge",
-           "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged"]
+           "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged",
+           "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts"]
 
 
 class GraphView(C.Structure):
@@ -236,6 +237,14 @@ def lib():
         L.gtx_reads_close.restype = None
         L.gtx_bam_shrink_multi.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(ShrinkParams), C.c_char_p, C.POINTER(ShrinkStats)]
         L.gtx_inflate_raw.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        if hasattr(L, "gtx_inflate_create"):  # (GTX_LIB= a build of an earlier commit, for A/B runs, has no device inflater; build() insists on EXPORTS)
+            L.gtx_inflate_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+            L.gtx_inflate_destroy.argtypes = [C.c_void_p]
+            L.gtx_inflate_destroy.restype = None
+            L.gtx_inflate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
+            L.gtx_inflate_bgzf.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
+            L.gtx_reads_set_inflate_device.argtypes = [C.c_void_p, C.c_int]
+            L.gtx_reads_inflate_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gtx_regions_run.argtypes = [C.POINTER(RegionJob), C.c_uint32, C.POINTER(Params), C.c_int, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RegionsStats)]
         L.gtx_regions_free.argtypes = [C.POINTER(RegionJob), C.c_uint32]
@@ -558,6 +567,10 @@ class Reads:
         check(lib().gtx_reads_next(self.h, _p(recs), _p(seq), seq_stride, cap, C.byref(n)))
         return recs[:n.value], seq[:n.value]
 
+    def set_inflate_device(self, device=0):
+        """the files' BGZF members are inflated by the device from here on (gtx_reads_set_inflate_device)"""
+        check(lib().gtx_reads_set_inflate_device(self.h, device))
+
     def close(self):
         if getattr(self, "h", None):
             lib().gtx_reads_close(self.h)
@@ -605,6 +618,50 @@ def inflate_raw(data, out_len):
     out = C.create_string_buffer(max(out_len, 1))
     check(lib().gtx_inflate_raw(data, len(data), out, out_len))
     return out.raw[:out_len]
+
+
+INFLATE_MEMBER = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("in_len", np.uint32), ("out_len", np.uint32), ("crc32", np.uint32),
+                           ("reserved", np.uint32)], align=True)
+assert INFLATE_MEMBER.itemsize == 32
+INFLATE_OK, INFLATE_BAD_STREAM, INFLATE_SHORT, INFLATE_LONG, INFLATE_CRC, INFLATE_BAD_MEMBER = range(6)
+
+
+def reads_inflate_counts():
+    """(by the device, fell back to the host on a status, by the reader itself): members of readers on the device path, process-wide"""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().gtx_reads_inflate_counts(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+class Inflater:
+    """DEFLATE on the device (gtx_inflate_*): BGZF members, one wavefront each"""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        check(lib().gtx_inflate_create(device, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gtx_inflate_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def batch(self, d_in, in_size, d_members, n, d_out, out_size, d_status, check_crc=True, stream=None):
+        """device pointers (ints); asynchronous on `stream`"""
+        check(lib().gtx_inflate_batch(self.h, d_in, in_size, d_members, n, d_out, out_size, d_status, int(check_crc), stream))
+
+    def bgzf(self, data, check_crc=True):
+        """the inflated bytes of a BGZF buffer (the inverse of bgzf_compress)"""
+        n = C.c_uint64(0)
+        check(lib().gtx_inflate_bgzf(self.h, data, len(data), None, 0, C.byref(n), int(check_crc)))
+        out = np.zeros(max(1, n.value), np.uint8)
+        check(lib().gtx_inflate_bgzf(self.h, data, len(data), _p(out), n.value, C.byref(n), int(check_crc)))
+        return out[:n.value].tobytes()
 
 
 def pipeline_run(ctx, paths, n_threads, buf, rec_words, record_slots_per_thread, chunk=65536, region=None):

@@ -649,6 +649,54 @@ int gtx_bgzf_compress(const void * in, uint64_t in_len, int level, int with_eof,
  * bgzf.c, which calls libdeflate or zlib).  GTX_ERR_IO: not a valid stream of that size. */
 int gtx_inflate_raw(const void * in, uint64_t in_len, void * out, uint64_t out_len);
 
+/* DEFLATE on the device: BGZF members are independent streams of at most 64 KB, and a file holds thousands of them -- one
+ * wavefront inflates one member (graphtyper_amd/csrc/gtx_inflate_dev.hpp: stored, fixed and dynamic blocks, every complete code
+ * of RFC 1951 in fixed LDS tables, the output's CRC-32 computed by the wavefront as well).
+ *   gtx_inflate_create     an inflater on `device` (device -1 or no such HIP device: GTX_ERR_NO_DEVICE -- no CPU compute path;
+ *                          gtx_inflate_raw is the host's decoder).  Its device blocks come from the library's cache.
+ *   gtx_inflate_batch      device: n members in one launch, asynchronous on `stream`.  d_in holds in_size bytes of streams,
+ *                          d_members the n descriptors, d_out has out_size bytes, d_status receives one GTX_INFLATE_* per member.
+ *                          A member is the stream d_in[in_off, in_off + in_len) and its output d_out[out_off, out_off + out_len),
+ *                          out_len <= 65536; nothing outside those ranges is loaded or stored whatever the stream holds, a
+ *                          descriptor that leaves the buffers gets GTX_INFLATE_BAD_MEMBER.  check_crc 0: crc32 is not compared.
+ *   gtx_inflate_bgzf       host: the inverse of gtx_bgzf_compress -- the BGZF members of `in` (a .bam, a .vcf.gz) are parsed on the
+ *                          host and inflated by the device into `out` one behind the other.  *out_len: the inflated size (out may
+ *                          be NULL with cap 0 to ask for it; cap too small: GTX_ERR_CAPACITY).  GTX_ERR_IO: not BGZF, or the
+ *                          device refused a member (gtx_last_error names the member and its status).
+ *   gtx_reads_set_inflate_device   the members of an open gtx_reads go to a team of the device instead of the host's threads:
+ *                          the compressed members of all readers that asked are gathered, copied up, inflated in one launch and
+ *                          copied back; the reader takes them in file order as before.  A member the device gives any status
+ *                          but GTX_INFLATE_OK is inflated on the host as without this call, so a damaged file fails as it does
+ *                          there.  One device per process at a time (another while such readers are open: GTX_ERR_UNSUPPORTED).
+ *                          GTX_BGZF_DEVICE_RING: members a reader keeps in flight on this path (default 256).
+ *                          gtx_pipeline_run calls it for its readers with the context's device when GTX_BGZF_DEVICE=1.
+ *   gtx_reads_inflate_counts   what became of the members of such readers, counted over the process since it began: inflated by
+ *                          the device; taken by the team and then inflated on the host (a status but ok, or a launch that
+ *                          failed); inflated by their reader before the team had started on them.  Any pointer may be NULL.
+ * One gtx_inflate serves one thread at a time: gtx_inflate_bgzf stages through blocks and a stream that belong to the object. */
+enum
+{
+  GTX_INFLATE_OK = 0,
+  GTX_INFLATE_BAD_STREAM = 1, /* not a valid DEFLATE stream (or it ends behind its input) */
+  GTX_INFLATE_SHORT = 2,      /* the stream ends before out_len bytes */
+  GTX_INFLATE_LONG = 3,       /* the stream holds more than out_len bytes */
+  GTX_INFLATE_CRC = 4,        /* out_len bytes whose CRC-32 is not the member's */
+  GTX_INFLATE_BAD_MEMBER = 5  /* the descriptor reaches outside the batch's buffers, or out_len > 65536 */
+};
+typedef struct gtx_inflate_member
+{
+  uint64_t in_off, out_off;
+  uint32_t in_len, out_len;
+  uint32_t crc32;
+  uint32_t reserved;
+} gtx_inflate_member;
+typedef struct gtx_inflate gtx_inflate;
+int gtx_inflate_create(int device, gtx_inflate ** out);
+void gtx_inflate_destroy(gtx_inflate *);
+int gtx_inflate_batch(gtx_inflate *, const void * d_in, uint64_t in_size, const gtx_inflate_member * d_members, uint32_t n, void * d_out,
+                      uint64_t out_size, uint32_t * d_status, int check_crc, void * stream);
+int gtx_inflate_bgzf(gtx_inflate *, const void * in, uint64_t in_len, void * out, uint64_t cap, uint64_t * out_len, int check_crc);
+
 /* Coordinate index of a bgzip-compressed VCF file.  gtx_tabix_build replaces Vcf::write_tbi_index (src/typer/vcf.cpp:1308-1321:
  * htslib's tbx_index_build with the VCF preset): min_shift 0 writes <vcf>.tbi (bins of 16 kb .. 512 Mb and the linear index),
  * min_shift > 0 a .csi of that geometry (the reference's --csi uses 14) -- to index_path when given.  The file has to be
@@ -838,6 +886,8 @@ int gtx_reads_open(const char * const * bam_paths, uint32_t n_paths, const char 
 int gtx_reads_info(const gtx_reads *, uint32_t * n_samples, uint32_t * n_read_groups);
 const char * gtx_reads_sample_name(const gtx_reads *, uint32_t i);
 int gtx_reads_next(gtx_reads *, gtx_stream_record * recs, uint8_t * seq, uint32_t seq_stride, uint32_t cap, uint32_t * n);
+int gtx_reads_set_inflate_device(gtx_reads *, int device); /* see gtx_inflate_create */
+int gtx_reads_inflate_counts(uint64_t * by_device, uint64_t * fell_back, uint64_t * by_reader);
 void gtx_reads_close(gtx_reads *);
 
 /* ---- the host loop around the path, inside the library.  gtx_pipeline_run replaces the reference's worker threads over BAM

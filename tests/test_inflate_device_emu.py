@@ -1,0 +1,154 @@
+"""The device DEFLATE decoder (graphtyper_amd/csrc/gtx_inflate_dev.hpp, the source of gtx_inflate_kernel) run member by member
+through a sequential wave emulation under AddressSanitizer / UBSan (tests/emu_inflate), against zlib: every valid stream of the
+corpus is inflated -- none refused, none left out --, its bytes are zlib's and its CRC-32 verdict is zlib.crc32's; damaged
+streams are refused or give what zlib gives, without a sanitizer report and within the driver's time limit.  Every member's
+stream and output lie in heap blocks of exactly their sizes.  The device: test_gpu_bgzf_inflate.py."""
+import ctypes as C
+import os
+import subprocess
+import zlib
+
+import numpy as np
+import pytest
+
+import inflate_corpus as ic
+from graphtyper_amd import lib as gtx
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+@pytest.fixture(scope="session")
+def emu_inflate(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("emu_inflate") / "emu_inflate")
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_inflate"), "-s", "OUT=" + out])
+    return out
+
+
+def _check_valid(emu, tmp_path, pairs):
+    """pairs: [(data, stream)], every one a valid stream: status ok with the right CRC, CRC status with a wrong one, zlib's bytes"""
+    blob, where = ic.pack([s for _, s in pairs])
+    members = [(off, n, 0, len(d), zlib.crc32(d)) for (off, n), (d, _) in zip(where, pairs)]
+    st, out = ic.run_emu(emu, tmp_path, members, blob, mode=0)
+    refused = [i for i in range(len(pairs)) if st[i] != ic.OK]
+    assert refused == [], "valid streams refused: %s" % [(i, int(st[i]), len(pairs[i][0])) for i in refused]
+    assert out == b"".join(d for d, _ in pairs)
+    wrong = [(off, n, 0, len(d), zlib.crc32(d) ^ 0x40) for (off, n), (d, _) in zip(where, pairs)]
+    st, out = ic.run_emu(emu, tmp_path, wrong, blob, mode=0)
+    assert (st == ic.CRC).all()
+    st, out = ic.run_emu(emu, tmp_path, wrong, blob, mode=0, check_crc=False)
+    assert (st == ic.OK).all() and out == b"".join(d for d, _ in pairs)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_corpus_equals_zlib(emu_inflate, tmp_path, seed):
+    corpus = ic.seeded(seed)
+    assert len(corpus) == 120
+    _check_valid(emu_inflate, tmp_path, [(d, s) for d, s, _ in corpus])
+
+
+def test_sizes_levels_strategies_and_long_codes(emu_inflate, tmp_path):
+    ex = ic.extras()
+    assert {0, 1, 2, 3, 65535, 65536} <= {len(d) for d, _ in ex}
+    # (the skewed alphabets do bring 15-bit codes: the canonical walk behind the first-level table is exercised)
+    assert max(ic.max_code_bits(s) for d, s in ex[-5:]) == 15
+    _check_valid(emu_inflate, tmp_path, ex)
+
+
+def test_hand_made_streams(emu_inflate, tmp_path):
+    blob, where = ic.pack([s for s, _, _ in ic.HAND_MADE])
+    members = [(off, n, 0, out_len, zlib.crc32(want or b"")) for (off, n), (_, out_len, want) in zip(where, ic.HAND_MADE)]
+    st, out = ic.run_emu(emu_inflate, tmp_path, members, blob, mode=0)
+    at = 0
+    for i, (_, out_len, want) in enumerate(ic.HAND_MADE):
+        if want is None:
+            assert st[i] not in (ic.OK, ic.CRC, ic.BAD_MEMBER), i
+        else:
+            assert st[i] == ic.OK and out[at:at + out_len] == want, i
+        at += out_len
+    # a match that reaches in front of the output is "not a valid stream", whatever room the output has
+    assert st[len(ic.HAND_MADE) - 1] == ic.BAD_STREAM
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_damaged_streams(emu_inflate, tmp_path, seed):
+    """a flipped bit, truncation, out_len off by one, bytes appended (test_inflate.py's damage): refused, or zlib's bytes"""
+    corpus = ic.seeded(seed)
+    blob, where = ic.pack([bad for _, _, (bad, _) in corpus])
+    members = [(off, n, 0, want, 0) for (off, n), (_, _, (_, want)) in zip(where, corpus)]
+    st, out = ic.run_emu(emu_inflate, tmp_path, members, blob, mode=0, check_crc=False)
+    at, taken = 0, 0
+    for i, (_, _, (bad, want)) in enumerate(corpus):
+        verdict = ic.zlib_verdict(bad, want)
+        if st[i] == ic.OK:
+            assert verdict is not None and out[at:at + want] == verdict, i
+            taken += 1
+        else:
+            assert st[i] in (ic.BAD_STREAM, ic.SHORT, ic.LONG), i
+            # (what zlib takes at that size is a valid stream: the device may not refuse it either)
+            assert verdict is None, i
+        at += want
+    assert 0 < taken < len(corpus)
+    # with the CRC of the undamaged data: what decodes to other bytes is a CRC failure, never ok
+    members = [(off, n, 0, want, zlib.crc32(d)) for (off, n), (d, _, (_, want)) in zip(where, corpus)]
+    st2, out2 = ic.run_emu(emu_inflate, tmp_path, members, blob, mode=0)
+    at = 0
+    for i, (d, _, (bad, want)) in enumerate(corpus):
+        assert (st2[i] == ic.OK) == (st[i] == ic.OK and out[at:at + want] == d), i
+        assert st2[i] == st[i] or (st[i] == ic.OK and st2[i] == ic.CRC), i
+        at += want
+
+
+def test_out_len_off_by_one_names_the_direction(emu_inflate, tmp_path):
+    data = b"chr20\t1234\t.\tA\tC\t" * 100
+    comp = ic._deflate(data, 6, zlib.Z_DEFAULT_STRATEGY, [])
+    blob, where = ic.pack([comp, comp, comp])
+    members = [(where[0][0], where[0][1], 0, len(data) + 1, 0), (where[1][0], where[1][1], 0, len(data) - 1, 0),
+               (where[2][0], where[2][1], 0, 0, 0)]
+    st, _ = ic.run_emu(emu_inflate, tmp_path, members, blob, mode=0, check_crc=False)
+    assert list(st) == [ic.SHORT, ic.LONG, ic.LONG]
+
+
+def test_batch_odd_offsets_outputs_back_to_back(emu_inflate, tmp_path):
+    """the batch as the device entry point takes it: streams at odd offsets of one input buffer, outputs back to back in one
+    output buffer behind a margin; the bytes outside every member's range keep their fill, whatever the member's status"""
+    rng = np.random.default_rng(5)
+    corpus = ic.seeded(1)[:60]
+    streams, lens, crcs = [], [], []
+    for k, (d, s, (bad, want)) in enumerate(corpus):
+        if k % 3 == 2:
+            streams.append(bad), lens.append(want), crcs.append(zlib.crc32(d))
+        else:
+            streams.append(s), lens.append(len(d)), crcs.append(zlib.crc32(d))
+    blob, where = ic.pack(streams, rng)
+    margin, at, members = 77, 77, []
+    for (off, n), out_len, crc in zip(where, lens, crcs):
+        members.append((off, n, at, out_len, crc))
+        at += out_len
+    out_size = at + margin
+    # descriptors that point outside the buffers are refused without a load or a store
+    members += [(len(blob) - 1, 2, 0, 0, 0), (0, 2, out_size - 1, 2, 0), (0, 2, 0, 65537, 0), (len(blob) + 1, 0, 0, 0, 0)]
+    st, out = ic.run_emu(emu_inflate, tmp_path, members, blob, mode=1, out_size=out_size, fill=0x5A)
+    assert len(out) == out_size
+    assert out[:margin] == b"\x5a" * margin and out[at:] == b"\x5a" * margin
+    assert list(st[-4:]) == [ic.BAD_MEMBER] * 4
+    for k, ((d, s, (bad, want)), m) in enumerate(zip(corpus, members)):
+        got = out[m[2]:m[2] + m[3]]
+        if k % 3 != 2:
+            assert st[k] == ic.OK and got == d, k
+        else:
+            assert (st[k] == ic.OK) == (ic.zlib_verdict(bad, want) == d), k
+
+
+def test_create_without_a_device():
+    gtx.build()
+    L = gtx.lib()
+    h = C.c_void_p()
+    assert L.gtx_inflate_create(-1, C.byref(h)) == 2 and not h.value  # GTX_ERR_NO_DEVICE
+    assert b"no CPU" in L.gtx_last_error()
+    try:
+        import torch
+        has_gpu = torch.cuda.is_available()
+    except ImportError:
+        has_gpu = False
+    if not has_gpu:
+        assert L.gtx_inflate_create(0, C.byref(h)) == 2 and not h.value
