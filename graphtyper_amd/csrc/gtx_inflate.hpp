@@ -24,7 +24,11 @@ namespace gtx
 namespace inflate_detail
 {
 constexpr unsigned LITLEN_BITS = 11, DIST_BITS = 8;
-constexpr unsigned LITLEN_SIZE = (1u << LITLEN_BITS) + 1024, DIST_SIZE = (1u << DIST_BITS) + 512; // first level + room for the second
+// first level + room for the second.  The room cannot be outgrown: over all complete codes of up to 15 bits (a walk over the
+// numbers of codes per length, as zlib's enough.c does it; it gives zlib's own 852 and 592 for 9 / 6 first-level bits) the second
+// levels take at most 292 entries for 286 literal / length symbols behind 11 bits (294 for 288) and 144 for 30 distance symbols
+// behind 8 bits (146 for 32).  build_table's `cap` check therefore never fires on a stream; it stays as the bound it is.
+constexpr unsigned LITLEN_SIZE = (1u << LITLEN_BITS) + 1024, DIST_SIZE = (1u << DIST_BITS) + 512;
 
 // entry: bits 0..4 code length to consume (second-level entries: the part behind the first level)
 //        bits 5..7 kind: 0 literal, 1 length, 2 end of block, 3 second-level pointer, 4 invalid

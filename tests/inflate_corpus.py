@@ -159,3 +159,40 @@ def pack(streams, rng=None):
         where.append((len(blob), len(s)))
         blob += s
     return bytes(blob), where
+
+
+def recorded_inputs():
+    """the inputs of tests/golden/libdeflate_streams.bin, from their seeds: {name: bytes} -- test_inflate._data's kinds and the
+    records of a BAM file as tests/bam_writer.py writes them"""
+    import bam_writer as bw
+    rng = np.random.default_rng(1951)
+    out = {"acgt": _data(rng, 1, 24000), "text": _data(rng, 2, 65536), "runs": _data(rng, 3, 40000), "zipf": _data(rng, 4, 12000),
+           "noise": _data(rng, 0, 600), "empty": b"", "one": b"G"}
+    recs, pos = bytearray(), 1000
+    for i in range(400):
+        pos += int(rng.integers(0, 40))
+        if len(recs) > 16000:
+            break
+        recs += bw.record("read%d" % i, int(rng.choice([0, 16, 99, 147])), 0, pos, int(rng.integers(0, 61)), [("M", 100), ("I", 2), ("M", 49)], 0, pos + 200, 351,
+                          rng.choice([1, 2, 4, 8], size=151).astype(np.uint8), [("AS", "C", int(rng.integers(0, 151))), ("XS", "C", 20), ("RG", "Z", "grp1")],
+                          qual=rng.choice([11, 25, 37, 40], size=151, p=[0.05, 0.1, 0.25, 0.6]))
+    out["bam_records"] = bytes(recs)
+    return out
+
+
+def recorded_libdeflate():
+    """the streams libdeflate made of recorded_inputs() at levels 1, 6, 9 and 12 (tests/golden/make_libdeflate_streams.py wrote
+    them; only the fixture is read here, never the library): [(name, level, data, stream)].  The file: uint32 n, then per stream
+    16 bytes of name, uint32 level, size, crc32, stream length, and the stream."""
+    import os
+    raw = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "libdeflate_streams.bin"), "rb").read()
+    inputs, out, at = recorded_inputs(), [], 4
+    for _ in range(struct.unpack_from("<I", raw, 0)[0]):
+        name, level, size, crc, n = struct.unpack_from("<16s4I", raw, at)
+        name, at = name.rstrip(b"\0").decode(), at + 32
+        data = inputs[name]
+        assert len(data) == size and zlib.crc32(data) == crc, "the input %s is not what the fixture was made of" % name
+        out.append((name, level, data, raw[at:at + n]))
+        at += n
+    assert at == len(raw)
+    return out
