@@ -11,11 +11,15 @@
 // of a read -- by going over the reads in stream order, then applies the two support filters over the coverage arrays.
 // gtx_disc_first_pass_haplotypes takes the pass to its end (the sample's haplotype map, :1186-1365), gtx_disc_merge puts the files'
 // results together (merge_haplotypes2 :64-165, the union of the indels :2853-2903).
-// (Next: the per-event sums as a device sort + segmented reduction; only the reads with >= 12 events need the order.)
+// Device again: gtx_disc_first_pass_device does the host stage's work up to and including the filters over the device arrays
+// (sort by event, one lane per distinct event in read order, a second sort for the phase counts; the second half of this file),
+// with the accumulation step and the filters of gtx_disc_support.hpp, which the host stage calls too.
+#include <cstring> // (rocPRIM's texture iterator calls memset on the host)
+
 #include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
-#include <cstring>
 #include <limits>
 #include <map>
 #include <set>
@@ -27,6 +31,7 @@
 #include "../../include/gtx.h"
 #include "graph_dev.hpp"
 #include "gtx_devmem.hpp"
+#include "gtx_disc_support.hpp"
 
 namespace gtx
 {
@@ -40,6 +45,7 @@ struct gtx_disc
   std::string reference; // region's bases as given (upper case letters)
   uint32_t * d_refp = nullptr;
   uint32_t ref_groups = 0;
+  uint8_t * d_refc = nullptr; // the letters themselves (the span of an indel compares them as the host does)
 };
 
 namespace
@@ -243,16 +249,20 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
     for (uint32_t b = 0; b < 4; ++b)
       planes[4 * (i >> 5) + b] |= ((code >> b) & 1u) << (i & 31u);
   }
-  void * p = nullptr;
+  void *p = nullptr, *c = nullptr;
   if (hipSetDevice(device) != hipSuccess || gtx::dev_malloc(&p, planes.size() * 4) != hipSuccess ||
-      hipMemcpy(p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess || gtx::dev_malloc(&c, reference_len) != hipSuccess ||
+      hipMemcpy(c, reference, reference_len, hipMemcpyHostToDevice) != hipSuccess)
   {
     if (p)
       (void)gtx::dev_free(p);
+    if (c)
+      (void)gtx::dev_free(c);
     g_last_error = "gtx_disc_create: upload of the reference failed";
     return GTX_ERR_HIP;
   }
   d->d_refp = static_cast<uint32_t *>(p);
+  d->d_refc = static_cast<uint8_t *>(c);
   *out = d.release();
   return GTX_OK;
 }
@@ -266,6 +276,7 @@ extern "C" void gtx_disc_destroy(gtx_disc * d)
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
     (void)gtx::dev_free(d->d_refp);
+    (void)gtx::dev_free(d->d_refc);
   }
   delete d;
 }
@@ -319,11 +330,8 @@ struct Ev // Event (include/graphtyper/typer/event.hpp:30-73) with its ordering 
   }
 };
 
-struct Support // EventSupport (event.hpp:75-113): what the first pass fills
+struct Support : DiscCounters // EventSupport (event.hpp:75-113): what the first pass fills
 {
-  uint32_t hq = 0, lq = 0, proper = 0, first = 0, reversed = 0, clipped = 0;
-  uint8_t max_mapq = 0, max_distance = 0;
-  int32_t u1 = -1, u2 = -1, u3 = -1;
   uint16_t span = 1;
   bool realign = false, good = false;
   uint32_t max_log_qual = 0;
@@ -338,18 +346,7 @@ struct PassState // what run_first_pass has when its two filters are through
   long REF = 0, B = 0, begin = 0;
 };
 
-uint16_t wrap16(uint32_t v) { return static_cast<uint16_t>(v); } // (the reference's counters are uint16_t and wrap)
-
-bool good_snp(Support const & s, long cov) // EventSupport::has_good_support with the default Options (event.cpp:226-256)
-{
-  cov = std::max(cov, 1l);
-  int const hq = wrap16(s.hq), raw = wrap16(s.hq) + wrap16(s.lq), pp = wrap16(s.proper), fip = wrap16(s.first), rev = wrap16(s.reversed), cl = wrap16(s.clipped);
-  double const ratio = static_cast<double>(raw) / static_cast<double>(cov);
-  bool const very = s.u3 != -1 && ((hq >= 8 && ratio >= 0.35) || (hq >= 7 && ratio >= 0.40)) && pp >= 6;
-  bool const prom = s.u3 != -1 && ((hq >= 7 && ratio >= 0.20) || (hq >= 6 && ratio >= 0.30) || (hq >= 5 && ratio >= 0.40)) && pp >= 4;
-  return s.u2 != -1 && pp >= 2 && hq >= 3 && (prom || (fip > 0 && fip < raw)) && (very || (prom && rev > 0 && rev < raw) || (rev > 1 && rev < raw - 1)) &&
-         (cl <= 1 || cl + 5 <= raw) && (s.max_distance >= 10 || (prom && hq >= 10)) && (hq + (raw - hq) / 2.0) >= 3.9 && (ratio > 0.26 || prom);
-}
+uint16_t wrap16(uint32_t v) { return disc_wrap16(v); }
 } // namespace
 
 // run_first_pass up to and including its two support filters (caller.cpp:488-1186) from the device's events
@@ -431,52 +428,13 @@ static int first_pass_state(const gtx_disc * d, const gtx_disc_read * reads, con
             ++span;
         s.span = static_cast<uint16_t>(std::min<long>(span, std::numeric_limits<uint16_t>::max() - 1) + 1); // (bucket.cpp:128-131, 156-159)
       }
-      if (e.type == 'X')
-      {
-        if (e.hq)
-          ++s.hq;
-        else
-          ++s.lq;
-        s.first += (r.flag & 64u) != 0;
-        if (s.u1 == -1)
-          s.u1 = r.pos;
-        else if (s.u2 == -1)
-        {
-          if (s.u1 != r.pos)
-            s.u2 = r.pos;
-        }
-        else if (s.u3 == -1 && s.u2 != r.pos)
-          s.u3 = r.pos;
-        if (static_cast<long>(e.max_distance) > static_cast<long>(s.max_distance))
-          s.max_distance = static_cast<uint8_t>(e.max_distance);
-      }
-      else
-        ++s.hq;
-      if (r.mapq != 255 && r.mapq > s.max_mapq)
-        s.max_mapq = r.mapq;
-      s.proper += (r.flag & 2u) != 0;
-      s.reversed += (r.flag & 16u) != 0;
-      s.clipped += clipped;
+      disc_accumulate(s, e.type, e.hq, e.max_distance, r.pos, r.flag, r.mapq, clipped); // (shared with the device walk)
       mine.push_back(ins.first);
     }
     // reads with many events (caller.cpp:777-822)
     if (mine.size() >= 12)
       for (auto & it : mine)
-      {
-        Support & s = it->second;
-        if (mine.size() >= 18)
-        {
-          if (wrap16(s.hq) > 0)
-            --s.hq;
-          else if (wrap16(s.lq) > 0)
-            --s.lq;
-        }
-        else if (wrap16(s.hq) > 0)
-        {
-          --s.hq;
-          ++s.lq;
-        }
-      }
+        disc_many_events(it->second, static_cast<uint32_t>(mine.size()));
     if (mine.size() < 18)
       for (size_t b2 = 1; b2 < mine.size(); ++b2)
         for (size_t a = 0; a < b2; ++a)
@@ -505,7 +463,7 @@ static int first_pass_state(const gtx_disc * d, const gtx_disc_read * reads, con
         if (at + 1 > b * B)
           for (long o = b * B; o <= at; ++o)
             cov += delta(o);
-        if (good_snp(it->second, cov))
+        if (disc_good_snp(it->second, cov))
           ++it;
         else
           it = buckets[b].erase(it);
@@ -528,10 +486,9 @@ static int first_pass_state(const gtx_disc * d, const gtx_disc_read * reads, con
         continue;
       }
       Support & s = it->second;
-      double const len = static_cast<double>(it->first.seq.size());
-      long const pad = static_cast<long>(4.0 + len / 3.0), pos = static_cast<long>(it->first.pos);
-      long const lo = std::max(0l, pos - pad - begin), hi = std::min(REF, pos + s.span + pad - begin);
-      double const count = (it->first.type == 'I' ? (len / 2.0 + 8.0) / 8.0 : (len / 3.0 + 10.0) / 10.0) * (wrap16(s.hq) + wrap16(s.lq));
+      uint32_t const len = static_cast<uint32_t>(it->first.seq.size());
+      long lo = 0, hi = 0;
+      disc_indel_window(static_cast<long>(it->first.pos), len, s.span, begin, REF, lo, hi);
       long cov = depth, o = lo;
       if (o <= b * B)
         for (; o < b * B; ++o)
@@ -541,18 +498,16 @@ static int first_pass_state(const gtx_disc * d, const gtx_disc_read * reads, con
           cov += delta(o);
       for (; o <= hi; ++o)
         cov -= o < REF ? static_cast<long>(down[o]) : 0l;
-      double const corrected = std::max(static_cast<double>(cov), count), anti = corrected - count;
-      double const gt00 = count * 10.0, gt_alt = std::min(count + anti, anti * 10.0); // get_log_qual_double (event.cpp:102-113)
-      uint32_t const log_qual = gt00 > gt_alt ? static_cast<uint32_t>(gt00 - gt_alt + 0.5) : 0u;
-      int const hq = wrap16(s.hq), rev = wrap16(s.reversed), pp = wrap16(s.proper), cl = wrap16(s.clipped);
-      if (hq >= 6 && count >= 8.0 && log_qual >= 60 && rev > 0 && rev < hq && pp >= 3 && s.max_mapq >= 20 && (cl == 0 || cl + 3 <= hq))
+      uint32_t log_qual = 0;
+      int const verdict = disc_indel_class(s, it->first.type == 'I', len, cov, log_qual); // (shared with the device walk)
+      if (verdict == 2)
       {
         s.good = s.realign = true;
         s.max_log_qual = log_qual;
         s.file_i = file_index;
         ++it;
       }
-      else if (count >= 3.0 && log_qual > 0 && pp >= 1 && (hq >= 5 || s.max_mapq >= 25) && s.max_mapq >= 10 && cl < hq)
+      else if (verdict == 1)
       {
         s.realign = true;
         s.max_log_qual = log_qual;
@@ -718,6 +673,8 @@ extern "C" int gtx_disc_first_pass(const gtx_disc * d, const gtx_disc_read * rea
   return hand_over(w, out, cap, n_words);
 }
 
+static int haplotypes_of(PassState & st, uint32_t * out, uint64_t cap, uint64_t * n_words);
+
 // run_first_pass to its end (caller.cpp:1186-1365): for every event that is left, which later events within two buckets it
 // travels with -- "ever": in enough of the reads that cover both (by its phase counts and the coverage between the two; any
 // shared read when one of them is an indel), "always": those of them at most ten positions on -- the sample's haplotype map;
@@ -735,6 +692,12 @@ extern "C" int gtx_disc_first_pass_haplotypes(const gtx_disc * d, const gtx_disc
   int const rc = first_pass_state(d, reads, cigar, read_out, n_reads, events, n_events, seq, seq_stride, bucket_size, file_index, st);
   if (rc != GTX_OK)
     return rc;
+  return haplotypes_of(st, out, cap, n_words);
+}
+
+// (the state behind the two filters may come from first_pass_state or from the device's survivors: gtx_disc_first_pass_haplotypes_device)
+static int haplotypes_of(PassState & st, uint32_t * out, uint64_t cap, uint64_t * n_words)
+{
   long const REF = st.REF, B = st.B, begin = st.begin, NB = static_cast<long>(st.buckets.size());
   auto delta = [&](long o) { return static_cast<long>(st.up[o]) - static_cast<long>(st.down[o]); };
   FileResult res;
@@ -865,4 +828,743 @@ extern "C" int gtx_disc_merge(const uint32_t * into, uint64_t n_into, const uint
   std::vector<uint32_t> w;
   put_result(w, a);
   return hand_over(w, out, cap, n_words);
+}
+
+// ---- device: the first pass over the events (what first_pass_state does on the host, without a download) -----------------
+// The counted reads' events are laid out in stream order (a scan over the reads), keyed by (position, kind, sequence) and
+// sorted stably: the events of one Event are then a run in read order.  One lane walks a run with the host's own accumulation
+// step, finds the span of an indel and applies the filter of its kind over prefix sums of the coverage arrays.  The phase
+// counts are a second sort: every ordered pair of a read's events is a (group, group) key, equal keys are counted.  The
+// survivors are written as the words of gtx_disc_first_pass by the device, and only those come down.
+namespace
+{
+constexpr uint32_t DTB = 256;
+constexpr uint32_t INS_DIGITS = 13;     // bases of an insertion in the key: 13 digits of base 5 (0: behind its end) fit the key's 31 bits
+constexpr uint64_t KEY_DROPPED = ~0ull; // an event in front of the region, of no known kind, or nobody's: sorts last, never leaves
+enum : uint32_t
+{
+  M_END = 0,    // n_reads - index of the first GTX_DISC_END read (0: none)
+  M_ERR = 1,    // a read's events lie behind the event buffer
+  M_GROUPS = 2, // distinct events
+  M_RUNS = 3,   // distinct phase pairs
+  M_EVENTS = 4, // events of the counted reads
+  M_PAIRS = 5,  // phase pairs of the counted reads
+  M_WORDS = 8
+};
+
+struct DiscGroup // one distinct event with what the pass knows of it
+{
+  DiscCounters c;
+  uint32_t pos, rep, span, log_qual, phase_first;
+  uint16_t len;
+  uint8_t type, verdict; // verdict 0: dropped, 1: stays (an indel: worth a realignment), 2: an indel with good support
+};
+
+struct DiscInput
+{
+  gtx_disc_event const * events;
+  uint64_t n_events;
+  gtx_disc_read const * reads;
+  gtx_disc_read_out const * read_out;
+  uint32_t const * cigar;
+  uint32_t n_reads;
+  uint8_t const * rows;
+  uint32_t plane_stride;
+  uint8_t const * refc;
+  long REF, begin, B;
+};
+
+inline uint32_t dblocks(uint64_t n) { return static_cast<uint32_t>((n + DTB - 1) / DTB); }
+
+// base k of an insertion event as 0..3 = A C G T (the events kernel lets only such insertions through)
+__device__ inline uint32_t ins_base(DiscInput const & in, gtx_disc_event const & e, uint32_t k)
+{
+  uint32_t const * row = reinterpret_cast<uint32_t const *>(in.rows + static_cast<uint64_t>(e.read) * in.plane_stride);
+  uint32_t const at = e.seq + k, g = at >> 5, s = at & 31u;
+  if (g >= in.plane_stride / PLANE_GROUP_BYTES)
+    return 0;
+  uint32_t const code = ((row[4 * g] >> s) & 1u) | (((row[4 * g + 1] >> s) & 1u) << 1) | (((row[4 * g + 2] >> s) & 1u) << 2) | (((row[4 * g + 3] >> s) & 1u) << 3);
+  return code == 1 ? 0u : code == 2 ? 1u : code == 4 ? 2u : 3u;
+}
+
+// std::string order of two insertions that agree in their first INS_DIGITS bases
+__device__ inline int ins_compare(DiscInput const & in, gtx_disc_event const & a, gtx_disc_event const & b)
+{
+  uint32_t const m = a.len < b.len ? a.len : b.len;
+  for (uint32_t k = INS_DIGITS; k < m; ++k)
+  {
+    uint32_t const x = ins_base(in, a, k), y = ins_base(in, b, k);
+    if (x != y)
+      return x < y ? -1 : 1;
+  }
+  return a.len < b.len ? -1 : a.len > b.len ? 1 : 0;
+}
+
+// a key whose insertion fills all digits: longer strings may hide behind it
+__device__ inline bool key_is_long_insertion(uint64_t key) { return key != KEY_DROPPED && ((key >> 31) & 3u) == 0 && (key & 0x7FFFFFFFull) % 5u != 0; }
+
+__global__ __launch_bounds__(DTB) void gtx_disc_end_kernel(gtx_disc_read_out const * __restrict__ read_out, uint32_t n_reads, uint32_t * meta)
+{
+  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_reads && read_out[i].state == GTX_DISC_END)
+    atomicMax(meta + M_END, n_reads - i);
+}
+
+// per read: how many events and phase pairs it brings, and its two coverage marks
+__global__ __launch_bounds__(DTB) void gtx_disc_reads_kernel(DiscInput in, uint32_t * meta, uint32_t * __restrict__ n_ev, uint32_t * __restrict__ n_pairs,
+                                                             uint32_t * up, uint32_t * down)
+{
+  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > in.n_reads)
+    return;
+  uint32_t ne = 0, np = 0;
+  if (i < in.n_reads && i < in.n_reads - meta[M_END])
+  {
+    gtx_disc_read_out const ro = in.read_out[i];
+    if (ro.state == GTX_DISC_COUNTED)
+    {
+      if (static_cast<uint64_t>(ro.first_event) + ro.n_events > in.n_events)
+        atomicOr(meta + M_ERR, 1u);
+      else
+      {
+        ne = ro.n_events;
+        np = ne >= 2 && ne < 18 ? ne * (ne - 1) / 2 : 0;
+      }
+      long const rel = static_cast<long>(in.reads[i].pos) - in.begin;
+      if (rel >= 0 && rel < in.REF)
+        atomicAdd(up + rel, 1u);
+      if (ro.pos_end >= 0 && ro.pos_end < in.REF)
+        atomicAdd(down + ro.pos_end, 1u);
+    }
+  }
+  n_ev[i] = ne;
+  n_pairs[i] = np;
+}
+
+__global__ __launch_bounds__(DTB) void gtx_disc_delta_kernel(uint32_t const * __restrict__ up, uint32_t const * __restrict__ down, uint32_t n, uint32_t * __restrict__ delta)
+{
+  uint32_t const o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o < n)
+    delta[o] = up[o] - down[o];
+}
+
+// event j -> its place in stream order (its read's offset + its place in the read) with its key
+__global__ __launch_bounds__(DTB) void gtx_disc_keys_kernel(DiscInput in, uint32_t const * __restrict__ meta, uint32_t const * __restrict__ ev_off,
+                                                            uint64_t * __restrict__ keys, uint32_t * __restrict__ vals)
+{
+  uint64_t const j = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j >= in.n_events)
+    return;
+  gtx_disc_event const e = in.events[j];
+  uint32_t const i = e.read;
+  if (i >= in.n_reads || i >= in.n_reads - meta[M_END])
+    return;
+  gtx_disc_read_out const ro = in.read_out[i];
+  if (ro.state != GTX_DISC_COUNTED || j < ro.first_event || j - ro.first_event >= ro.n_events || ev_off[i + 1] - ev_off[i] != ro.n_events)
+    return;
+  uint32_t const r = ev_off[i] + static_cast<uint32_t>(j - ro.first_event);
+  uint64_t key = KEY_DROPPED;
+  long const rel = static_cast<long>(e.pos) - in.begin;
+  // (an event at or behind the region's end keeps its key: it sorts behind the region's own, the walk drops it, and as a phase
+  // target it is still the event it was)
+  if (rel >= 0 && rel < (1l << 31) && (e.type == 'I' || e.type == 'D' || e.type == 'X'))
+  {
+    uint32_t code = 0;
+    if (e.type == 'X')
+      code = e.seq & 0xFFu;
+    else if (e.type == 'D')
+      code = e.len;
+    else
+      for (uint32_t k = 0; k < INS_DIGITS; ++k)
+        code = code * 5u + (k < e.len ? 1u + ins_base(in, e, k) : 0u);
+    uint32_t const kind = e.type == 'I' ? 0u : e.type == 'D' ? 1u : 2u; // (event.cpp:198-207: insertions, deletions, SNPs)
+    key = (static_cast<uint64_t>(rel) << 33) | (static_cast<uint64_t>(kind) << 31) | code;
+  }
+  keys[r] = key;
+  vals[r] = static_cast<uint32_t>(j);
+}
+
+// the exact second step: a run of equal keys of insertions longer than the key holds is put into string order by one lane,
+// stably (an insertion sort: a run of one string costs one comparison per event)
+__global__ __launch_bounds__(DTB) void gtx_disc_ties_kernel(DiscInput in, uint64_t const * __restrict__ keys, uint32_t * vals, uint32_t n)
+{
+  uint32_t const t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n || t + 1 >= n)
+    return;
+  uint64_t const key = keys[t];
+  if (!key_is_long_insertion(key) || keys[t + 1] != key || (t != 0 && keys[t - 1] == key))
+    return;
+  uint32_t end = t + 1;
+  while (end < n && keys[end] == key)
+    ++end;
+  for (uint32_t k = t + 1; k < end; ++k)
+  {
+    uint32_t const x = vals[k];
+    gtx_disc_event const ex = in.events[x];
+    uint32_t s = k;
+    while (s > t && ins_compare(in, in.events[vals[s - 1]], ex) > 0)
+    {
+      vals[s] = vals[s - 1];
+      --s;
+    }
+    vals[s] = x;
+  }
+}
+
+__global__ __launch_bounds__(DTB) void gtx_disc_heads_kernel(DiscInput in, uint64_t const * __restrict__ keys, uint32_t const * __restrict__ vals, uint32_t n,
+                                                             uint32_t * __restrict__ head)
+{
+  uint32_t const t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n)
+    return;
+  bool h = t == 0 || keys[t - 1] != keys[t];
+  if (!h && key_is_long_insertion(keys[t]))
+    h = ins_compare(in, in.events[vals[t - 1]], in.events[vals[t]]) != 0;
+  head[t] = h;
+}
+
+// gid1: inclusive scan of the heads (group index + 1)
+__global__ __launch_bounds__(DTB) void gtx_disc_groups_kernel(uint32_t const * __restrict__ head, uint32_t const * __restrict__ gid1, uint32_t const * __restrict__ vals,
+                                                              uint32_t n, uint32_t * __restrict__ gstart, uint32_t * __restrict__ gid_of, uint32_t * meta)
+{
+  uint32_t const t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n)
+    return;
+  uint32_t const g = gid1[t] - 1;
+  if (head[t])
+    gstart[g] = t;
+  gid_of[vals[t]] = g;
+  if (t == n - 1)
+  {
+    gstart[g + 1] = n;
+    meta[M_GROUPS] = g + 1;
+  }
+}
+
+// the ordered pairs of a read's events as (group of the earlier, group of the later)
+__global__ __launch_bounds__(DTB) void gtx_disc_pairs_kernel(DiscInput in, uint32_t const * __restrict__ pair_off, uint32_t const * __restrict__ gid_of,
+                                                             uint32_t shift, uint64_t * __restrict__ pairs)
+{
+  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= in.n_reads || pair_off[i + 1] == pair_off[i])
+    return;
+  gtx_disc_read_out const ro = in.read_out[i];
+  uint64_t * out = pairs + pair_off[i];
+  for (uint32_t b = 1; b < ro.n_events; ++b)
+  {
+    uint64_t const gb = gid_of[ro.first_event + b];
+    for (uint32_t a = 0; a < b; ++a)
+      *out++ = (static_cast<uint64_t>(gid_of[ro.first_event + a]) << shift) | gb;
+  }
+}
+
+__global__ __launch_bounds__(DTB) void gtx_disc_pair_heads_kernel(uint64_t const * __restrict__ pairs, uint32_t n, uint32_t * __restrict__ head)
+{
+  uint32_t const p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n)
+    head[p] = p == 0 || pairs[p - 1] != pairs[p];
+}
+
+__global__ __launch_bounds__(DTB) void gtx_disc_runs_kernel(uint64_t const * __restrict__ pairs, uint32_t const * __restrict__ head, uint32_t const * __restrict__ rid1,
+                                                            uint32_t n, uint32_t shift, uint64_t * __restrict__ run_key, uint32_t * __restrict__ run_start,
+                                                            uint32_t * __restrict__ phase_first, uint32_t * meta)
+{
+  uint32_t const p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n)
+    return;
+  uint32_t const r = rid1[p] - 1;
+  if (head[p])
+  {
+    run_key[r] = pairs[p];
+    run_start[r] = p;
+    if (p == 0 || (pairs[p - 1] >> shift) != (pairs[p] >> shift))
+      phase_first[pairs[p] >> shift] = r;
+  }
+  if (p == n - 1)
+  {
+    run_start[r + 1] = n;
+    meta[M_RUNS] = r + 1;
+  }
+}
+
+// one lane, one distinct event: its run of events in read order through the host's accumulation step, the span, the filter
+__global__ __launch_bounds__(DTB) void gtx_disc_walk_kernel(DiscInput in, uint32_t const * __restrict__ meta, uint64_t const * __restrict__ keys,
+                                                            uint32_t const * __restrict__ vals, uint32_t const * __restrict__ gstart,
+                                                            uint32_t const * __restrict__ cov_delta, uint32_t const * __restrict__ cov_down,
+                                                            uint32_t const * __restrict__ phase_first, DiscGroup * __restrict__ groups)
+{
+  uint32_t const g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= meta[M_GROUPS])
+    return;
+  uint32_t const t0 = gstart[g], t1 = gstart[g + 1];
+  gtx_disc_event const e0 = in.events[vals[t0]];
+  DiscGroup out;
+  out.pos = e0.pos;
+  out.rep = vals[t0];
+  out.len = e0.len;
+  out.type = e0.type;
+  out.span = 1;
+  out.log_qual = 0;
+  out.verdict = 0;
+  out.phase_first = phase_first[g];
+  if (keys[t0] == KEY_DROPPED) // (nothing of it is read again: as a phase target it would be an event without letters)
+  {
+    out.type = 0;
+    out.len = 0;
+    groups[g] = out;
+    return;
+  }
+  DiscCounters c;
+  for (uint32_t t = t0; t < t1;)
+  {
+    uint32_t const i = in.events[vals[t]].read; // (a counted read: the keys kernel placed no other's events)
+    gtx_disc_read const r = in.reads[i];
+    uint32_t const n_of_read = in.read_out[i].n_events;
+    bool clipped = false;
+    if (r.n_cigar)
+    {
+      uint32_t const front = in.cigar[r.cigar_off], back = in.cigar[r.cigar_off + r.n_cigar - 1];
+      clipped = ((front & 15u) == 4 && (front >> 4) >= 1) || ((back & 15u) == 4 && (back >> 4) >= 1); // is_clipped (caller.cpp:167-196)
+    }
+    uint32_t u = t;
+    for (; u < t1; ++u) // the read's own events of this kind (more than one: two equal insertions at one place)
+    {
+      gtx_disc_event const e = in.events[vals[u]];
+      if (e.read != i)
+        break;
+      disc_accumulate(c, e.type, e.hq, e.max_distance, r.pos, r.flag, r.mapq, clipped);
+    }
+    if (n_of_read >= 12) // the correction comes when the read is through, before the next read's events
+      for (uint32_t k = t; k < u; ++k)
+        disc_many_events(c, n_of_read);
+    t = u;
+  }
+  out.c = c;
+  long const REF = in.REF, rel = static_cast<long>(e0.pos) - in.begin;
+  if (rel >= REF) // its bucket lies behind the region's last: the reference cuts it off before the filters
+  {
+    groups[g] = out;
+    return;
+  }
+  if (e0.type == 'X')
+    out.verdict = disc_good_snp(c, static_cast<long>(static_cast<int32_t>(cov_delta[rel + 1]))) ? 1 : 0;
+  else
+  {
+    // span of an indel (bucket.cpp:100-160): how far it can be shifted
+    long span = 0, count = e0.len;
+    uint8_t const * ref = in.refc;
+    if (e0.type == 'I')
+    {
+      while (span < count && rel + span < REF && "ACGT"[ins_base(in, e0, static_cast<uint32_t>(span))] == ref[rel + span])
+        ++span;
+      if (span == count)
+        while (rel + span < REF && ref[rel + span - count] == ref[rel + span])
+          ++span;
+    }
+    else
+      while (rel + span < REF && rel + span + count < REF && ref[rel + span] == ref[rel + span + count])
+        ++span;
+    out.span = static_cast<uint16_t>((span < 0xFFFE ? span : 0xFFFE) + 1);
+    // coverage over its window (caller.cpp:1003-1040) from the prefix sums: what lies in front of the window, less the reads that end in it
+    // (counted from the event's bucket on, as the reference does)
+    long lo = 0, hi = 0;
+    disc_indel_window(static_cast<long>(e0.pos), e0.len, out.span, in.begin, REF, lo, hi);
+    long const bucket_begin = rel / in.B * in.B, from = lo > bucket_begin ? lo : bucket_begin, to = hi < REF - 1 ? hi : REF - 1;
+    long cov = static_cast<long>(static_cast<int32_t>(cov_delta[lo]));
+    if (to >= from)
+      cov -= static_cast<long>(cov_down[to + 1] - cov_down[from]);
+    out.verdict = static_cast<uint8_t>(disc_indel_class(c, e0.type == 'I', e0.len, cov, out.log_qual));
+    if (out.verdict == 0)
+      out.log_qual = 0;
+  }
+  groups[g] = out;
+}
+
+// words of a surviving event: itself, 16 support words, its phase entries
+__global__ __launch_bounds__(DTB) void gtx_disc_sizes_kernel(uint32_t const * __restrict__ meta, DiscGroup const * __restrict__ groups,
+                                                             uint64_t const * __restrict__ run_key, uint32_t shift, uint32_t n, uint32_t * __restrict__ words)
+{
+  uint32_t const g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > n)
+    return;
+  uint32_t w = 0;
+  if (g < meta[M_GROUPS] && groups[g].verdict != 0)
+  {
+    w = 3u + groups[g].len + 16u;
+    uint64_t const mask = (1ull << shift) - 1;
+    for (uint32_t r = groups[g].phase_first; r < meta[M_RUNS] && (run_key[r] >> shift) == g; ++r)
+      w += 4u + groups[run_key[r] & mask].len;
+  }
+  words[g] = w;
+}
+
+__device__ inline uint32_t * emit_event(DiscInput const & in, gtx_disc_event const * events, DiscGroup const & g, uint32_t * w)
+{
+  *w++ = g.pos;
+  *w++ = g.type;
+  *w++ = g.len;
+  gtx_disc_event const e = events[g.rep];
+  if (g.type == 'X')
+    *w++ = e.seq & 0xFFu;
+  else if (g.type == 'D')
+    for (uint32_t k = 0; k < g.len; ++k)
+      *w++ = static_cast<long>(e.seq) + k < in.REF ? in.refc[e.seq + k] : static_cast<uint32_t>('N');
+  else
+    for (uint32_t k = 0; k < g.len; ++k)
+      *w++ = static_cast<uint32_t>("ACGT"[ins_base(in, e, k)]);
+  return w;
+}
+
+__global__ __launch_bounds__(DTB) void gtx_disc_emit_kernel(DiscInput in, uint32_t const * __restrict__ meta, DiscGroup const * __restrict__ groups,
+                                                            uint64_t const * __restrict__ run_key, uint32_t const * __restrict__ run_start, uint32_t shift,
+                                                            uint32_t const * __restrict__ word_off, uint32_t * __restrict__ out)
+{
+  uint32_t const g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= meta[M_GROUPS] || groups[g].verdict == 0)
+    return;
+  DiscGroup const G = groups[g];
+  DiscCounters const & s = G.c;
+  uint32_t * w = emit_event(in, in.events, G, out + word_off[g]);
+  bool const indel = G.type != 'X';
+  uint32_t const fields[15] = {disc_wrap16(s.hq), disc_wrap16(s.lq), disc_wrap16(s.proper), disc_wrap16(s.first), disc_wrap16(s.reversed),
+                               disc_wrap16(s.clipped), s.max_mapq, s.max_distance, static_cast<uint32_t>(s.u1), static_cast<uint32_t>(s.u2),
+                               static_cast<uint32_t>(s.u3), G.span, indel ? 1u : 0u, indel && G.verdict == 2 ? 1u : 0u, G.log_qual};
+  for (uint32_t k = 0; k < 15; ++k)
+    *w++ = fields[k];
+  uint32_t * n_phase = w++;
+  uint32_t np = 0;
+  uint64_t const mask = (1ull << shift) - 1;
+  for (uint32_t r = G.phase_first; r < meta[M_RUNS] && (run_key[r] >> shift) == g; ++r, ++np)
+  {
+    w = emit_event(in, in.events, groups[run_key[r] & mask], w);
+    *w++ = disc_wrap16(run_start[r + 1] - run_start[r]); // (a uint16_t that wraps, event.hpp)
+  }
+  *n_phase = np;
+}
+
+bool disc_ok(hipError_t e, char const * what)
+{
+  if (e == hipSuccess)
+    return true;
+  g_last_error = std::string("gtx_disc_first_pass_device: ") + what + ": " + hipGetErrorString(e);
+  return false;
+}
+
+struct DiscPool // temporary blocks of one pass; they go back to the cache when the stream is through with them
+{
+  std::vector<void *> temps;
+  hipStream_t stream = nullptr;
+  bool fine = true;
+  template <class T>
+  T * get(size_t n, char const * what, int fill = -1)
+  {
+    void * p = nullptr;
+    if (!fine)
+      return nullptr;
+    fine = disc_ok(gtx::dev_malloc(&p, (n ? n : 1) * sizeof(T)), what);
+    if (fine && fill >= 0)
+      fine = disc_ok(hipMemsetAsync(p, fill, (n ? n : 1) * sizeof(T), stream), what);
+    if (p)
+      temps.push_back(p);
+    return static_cast<T *>(p);
+  }
+  ~DiscPool()
+  {
+    if (!temps.empty())
+      (void)hipStreamSynchronize(stream);
+    for (void * p : temps)
+      (void)gtx::dev_free(p);
+  }
+};
+
+bool disc_scan(DiscPool & pool, uint32_t const * in, uint32_t * out, size_t n, bool inclusive)
+{
+  size_t bytes = 0;
+  hipError_t e = inclusive ? rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::plus<uint32_t>(), pool.stream)
+                           : rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), pool.stream);
+  if (!disc_ok(e, "scan (size)"))
+    return false;
+  void * tmp = pool.get<char>(bytes, "scan temporary");
+  if (!pool.fine)
+    return false;
+  e = inclusive ? rocprim::inclusive_scan(tmp, bytes, in, out, n, rocprim::plus<uint32_t>(), pool.stream)
+                : rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), pool.stream);
+  return disc_ok(e, "scan");
+}
+
+bool disc_download_async(void * to, void const * from, size_t bytes, hipStream_t stream)
+{
+  return disc_ok(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, stream), "download");
+}
+
+bool disc_wait(hipStream_t stream) { return disc_ok(hipStreamSynchronize(stream), "synchronise"); }
+
+bool disc_download(void * to, void const * from, size_t bytes, hipStream_t stream) { return disc_download_async(to, from, bytes, stream) && disc_wait(stream); }
+
+bool disc_launched() { return disc_ok(hipGetLastError(), "kernel launch"); }
+
+struct DiscDeviceResult
+{
+  uint32_t * d_words = nullptr; // the words of gtx_disc_first_pass
+  uint64_t n_words = 0;
+  uint32_t *d_up = nullptr, *d_down = nullptr; // cov_up / cov_down (REF + 1 words each)
+};
+
+int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+                     const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
+                     const uint32_t * d_counts, uint32_t bucket_size, DiscDeviceResult & res)
+{
+  pool.stream = stream;
+  long const REF = static_cast<long>(d->reference.size());
+  uint32_t counts[2] = {0, 0};
+  if (!disc_download(counts, d_counts, sizeof counts, stream))
+    return GTX_ERR_HIP;
+  if (counts[1] != 0)
+  {
+    g_last_error = "gtx_disc_first_pass_device: the event buffer overflowed (d_counts[1] != 0: event_cap too small)";
+    return GTX_ERR_CAPACITY;
+  }
+  if (counts[0] > (1u << 28))
+  {
+    g_last_error = "gtx_disc_first_pass_device: more than 2^28 events in one pass";
+    return GTX_ERR_UNSUPPORTED;
+  }
+  DiscInput in{d_events, counts[0], d_reads, d_read_out, d_cigar, n_reads, d_planes, plane_stride, d->d_refc, REF, static_cast<long>(d->region_begin),
+               static_cast<long>(bucket_size)};
+  uint32_t * meta = pool.get<uint32_t>(M_WORDS, "counters", 0);
+  res.d_up = pool.get<uint32_t>(REF + 1, "cov_up", 0);
+  res.d_down = pool.get<uint32_t>(REF + 1, "cov_down", 0);
+  uint32_t * n_ev = pool.get<uint32_t>(n_reads + 1, "events per read");
+  uint32_t * n_pairs = pool.get<uint32_t>(n_reads + 1, "pairs per read");
+  uint32_t * ev_off = pool.get<uint32_t>(n_reads + 1, "event offsets");
+  uint32_t * pair_off = pool.get<uint32_t>(n_reads + 1, "pair offsets");
+  uint32_t * delta = pool.get<uint32_t>(REF + 1, "coverage differences");
+  uint32_t * cov_delta = pool.get<uint32_t>(REF + 1, "coverage prefix");
+  uint32_t * cov_down = pool.get<uint32_t>(REF + 1, "cov_down prefix");
+  if (!pool.fine)
+    return GTX_ERR_HIP;
+  res.n_words = 0;
+  if (n_reads == 0)
+    return GTX_OK;
+  hipLaunchKernelGGL(gtx_disc_end_kernel, dim3(dblocks(n_reads)), dim3(DTB), 0, stream, d_read_out, n_reads, meta);
+  hipLaunchKernelGGL(gtx_disc_reads_kernel, dim3(dblocks(n_reads + 1)), dim3(DTB), 0, stream, in, meta, n_ev, n_pairs, res.d_up, res.d_down);
+  hipLaunchKernelGGL(gtx_disc_delta_kernel, dim3(dblocks(REF + 1)), dim3(DTB), 0, stream, res.d_up, res.d_down, static_cast<uint32_t>(REF + 1), delta);
+  if (!disc_scan(pool, n_ev, ev_off, n_reads + 1, false) || !disc_scan(pool, n_pairs, pair_off, n_reads + 1, false) ||
+      !disc_scan(pool, delta, cov_delta, REF + 1, false) || !disc_scan(pool, res.d_down, cov_down, REF + 1, false))
+    return GTX_ERR_HIP;
+  // the two totals join the counters: one copy, one wait
+  uint32_t head_words[M_WORDS];
+  if (!disc_launched() || !disc_ok(hipMemcpyAsync(meta + M_EVENTS, ev_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
+      !disc_ok(hipMemcpyAsync(meta + M_PAIRS, pair_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
+      !disc_download(head_words, meta, sizeof head_words, stream))
+    return GTX_ERR_HIP;
+  uint32_t const ne = head_words[M_EVENTS], np = head_words[M_PAIRS];
+  if (head_words[M_ERR])
+  {
+    g_last_error = "gtx_disc_first_pass_device: a read's events lie behind the event buffer (it overflowed: event_cap too small)";
+    return GTX_ERR_CAPACITY;
+  }
+  res.n_words = 0;
+  if (ne == 0)
+    return GTX_OK;
+  // the events in stream order, keyed and sorted
+  uint64_t * keys_in = pool.get<uint64_t>(ne, "keys", 0xFF);
+  uint64_t * keys = pool.get<uint64_t>(ne, "sorted keys");
+  uint32_t * vals_in = pool.get<uint32_t>(ne, "event indices", 0);
+  uint32_t * vals = pool.get<uint32_t>(ne, "sorted event indices");
+  uint32_t * head = pool.get<uint32_t>(ne, "heads");
+  uint32_t * gid1 = pool.get<uint32_t>(ne, "group numbers");
+  uint32_t * gstart = pool.get<uint32_t>(ne + 1, "group starts");
+  uint32_t * gid_of = pool.get<uint32_t>(counts[0], "group of an event", 0);
+  uint32_t * phase_first = pool.get<uint32_t>(ne, "first phase run", 0xFF);
+  DiscGroup * groups = pool.get<DiscGroup>(ne, "groups");
+  uint32_t * words = pool.get<uint32_t>(ne + 1, "words per group");
+  uint32_t * word_off = pool.get<uint32_t>(ne + 1, "word offsets");
+  if (!pool.fine)
+    return GTX_ERR_HIP;
+  hipLaunchKernelGGL(gtx_disc_keys_kernel, dim3(dblocks(counts[0])), dim3(DTB), 0, stream, in, meta, ev_off, keys_in, vals_in);
+  {
+    size_t bytes = 0;
+    if (!disc_ok(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys, vals_in, vals, ne, 0u, 64u, stream), "radix sort (size)"))
+      return GTX_ERR_HIP;
+    void * tmp = pool.get<char>(bytes, "sort temporary");
+    if (!pool.fine || !disc_ok(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys, vals_in, vals, ne, 0u, 64u, stream), "radix sort"))
+      return GTX_ERR_HIP;
+  }
+  hipLaunchKernelGGL(gtx_disc_ties_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, keys, vals, ne);
+  hipLaunchKernelGGL(gtx_disc_heads_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, keys, vals, ne, head);
+  if (!disc_scan(pool, head, gid1, ne, true))
+    return GTX_ERR_HIP;
+  hipLaunchKernelGGL(gtx_disc_groups_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, head, gid1, vals, ne, gstart, gid_of, meta);
+  // the phase counts: pairs of groups, sorted, run lengths
+  uint32_t shift = 1;
+  while ((1ull << shift) < ne)
+    ++shift;
+  uint64_t * run_key = pool.get<uint64_t>(np + 1, "phase keys");
+  uint32_t * run_start = pool.get<uint32_t>(np + 1, "phase run starts");
+  if (np)
+  {
+    uint64_t * pairs_in = pool.get<uint64_t>(np, "pairs");
+    uint64_t * pairs = pool.get<uint64_t>(np, "sorted pairs");
+    uint32_t * phead = pool.get<uint32_t>(np, "pair heads");
+    uint32_t * rid1 = pool.get<uint32_t>(np, "run numbers");
+    if (!pool.fine)
+      return GTX_ERR_HIP;
+    hipLaunchKernelGGL(gtx_disc_pairs_kernel, dim3(dblocks(n_reads)), dim3(DTB), 0, stream, in, pair_off, gid_of, shift, pairs_in);
+    size_t bytes = 0;
+    if (!disc_ok(rocprim::radix_sort_keys(nullptr, bytes, pairs_in, pairs, np, 0u, 2 * shift, stream), "radix sort of the pairs (size)"))
+      return GTX_ERR_HIP;
+    void * tmp = pool.get<char>(bytes, "sort temporary");
+    if (!pool.fine || !disc_ok(rocprim::radix_sort_keys(tmp, bytes, pairs_in, pairs, np, 0u, 2 * shift, stream), "radix sort of the pairs"))
+      return GTX_ERR_HIP;
+    hipLaunchKernelGGL(gtx_disc_pair_heads_kernel, dim3(dblocks(np)), dim3(DTB), 0, stream, pairs, np, phead);
+    if (!disc_scan(pool, phead, rid1, np, true))
+      return GTX_ERR_HIP;
+    hipLaunchKernelGGL(gtx_disc_runs_kernel, dim3(dblocks(np)), dim3(DTB), 0, stream, pairs, phead, rid1, np, shift, run_key, run_start, phase_first, meta);
+  }
+  if (!pool.fine)
+    return GTX_ERR_HIP;
+  hipLaunchKernelGGL(gtx_disc_walk_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, meta, keys, vals, gstart, cov_delta, cov_down, phase_first, groups);
+  hipLaunchKernelGGL(gtx_disc_sizes_kernel, dim3(dblocks(ne + 1)), dim3(DTB), 0, stream, meta, groups, run_key, shift, ne, words);
+  if (!disc_scan(pool, words, word_off, ne + 1, false))
+    return GTX_ERR_HIP;
+  uint32_t total = 0;
+  if (!disc_launched() || !disc_download(&total, word_off + ne, 4, stream))
+    return GTX_ERR_HIP;
+  res.n_words = total;
+  if (total == 0)
+    return GTX_OK;
+  res.d_words = pool.get<uint32_t>(total, "result words");
+  if (!pool.fine)
+    return GTX_ERR_HIP;
+  hipLaunchKernelGGL(gtx_disc_emit_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, meta, groups, run_key, run_start, shift, word_off, res.d_words);
+  return disc_launched() ? GTX_OK : GTX_ERR_HIP;
+}
+
+int disc_device_args(char const * name, const gtx_disc * d, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+                     const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
+                     const uint32_t * d_counts, uint32_t bucket_size, uint32_t * out, uint64_t cap, uint64_t * n_words)
+{
+  if (!d || !n_words || bucket_size == 0 || plane_stride == 0 || (plane_stride % PLANE_GROUP_BYTES) != 0 || (reinterpret_cast<uintptr_t>(d_planes) & 3u) != 0 ||
+      !d_counts || (n_reads != 0 && (!d_planes || !d_reads || !d_cigar || !d_read_out)) || (cap && !out) || n_reads == 0xFFFFFFFFu)
+  {
+    g_last_error = std::string(name) + ": bad argument";
+    return GTX_ERR_ARG;
+  }
+  (void)d_events; // (may be NULL when no event was made)
+  if (d->device < 0)
+  {
+    g_last_error = std::string(name) + ": the object was created without a device (libgtx has no CPU path)";
+    return GTX_ERR_NO_DEVICE;
+  }
+  return hipSetDevice(d->device) == hipSuccess ? GTX_OK : GTX_ERR_HIP;
+}
+} // namespace
+
+extern "C" int gtx_disc_first_pass_device(const gtx_disc * d, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+                                          const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
+                                          const uint32_t * d_counts, uint32_t bucket_size, uint32_t * out, uint64_t cap, uint64_t * n_words, void * stream)
+{
+  int rc = disc_device_args("gtx_disc_first_pass_device", d, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, out,
+                            cap, n_words);
+  if (rc != GTX_OK)
+    return rc;
+  hipStream_t const s = static_cast<hipStream_t>(stream);
+  DiscPool pool;
+  DiscDeviceResult res;
+  rc = disc_device_pass(d, s, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
+  if (rc != GTX_OK)
+    return rc;
+  *n_words = res.n_words;
+  if (res.n_words > cap)
+    return GTX_ERR_CAPACITY;
+  if (res.n_words && !disc_download(out, res.d_words, res.n_words * 4, s))
+    return GTX_ERR_HIP;
+  return GTX_OK;
+}
+
+extern "C" int gtx_disc_first_pass_haplotypes_device(const gtx_disc * d, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+                                                     const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads,
+                                                     const gtx_disc_event * d_events, const uint32_t * d_counts, uint32_t bucket_size, int32_t file_index,
+                                                     uint32_t * out, uint64_t cap, uint64_t * n_words, void * stream)
+{
+  int rc = disc_device_args("gtx_disc_first_pass_haplotypes_device", d, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts,
+                            bucket_size, out, cap, n_words);
+  if (rc != GTX_OK)
+    return rc;
+  hipStream_t const hs = static_cast<hipStream_t>(stream);
+  PassState st;
+  st.REF = static_cast<long>(d->reference.size());
+  st.B = bucket_size;
+  st.begin = d->region_begin;
+  std::vector<uint32_t> w;
+  {
+    DiscPool pool;
+    DiscDeviceResult res;
+    rc = disc_device_pass(d, hs, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
+    if (rc != GTX_OK)
+      return rc;
+    w.resize(res.n_words);
+    st.up.resize(st.REF);
+    st.down.resize(st.REF);
+    if ((res.n_words && !disc_download_async(w.data(), res.d_words, res.n_words * 4, hs)) || !disc_download_async(st.up.data(), res.d_up, st.REF * 4, hs) ||
+        !disc_download_async(st.down.data(), res.d_down, st.REF * 4, hs) || !disc_wait(hs))
+      return GTX_ERR_HIP;
+  }
+  // the survivors back into the buckets of the host stage
+  st.buckets.resize((st.REF - 1) / st.B + 1);
+  size_t at = 0;
+  bool whole = true; // (the words are the device's own; a cut stream is still not read behind its end)
+  auto event = [&]()
+  {
+    if (at + 3 > w.size() || w[at + 2] > w.size() - at - 3)
+    {
+      whole = false;
+      at = w.size();
+      return Ev{};
+    }
+    Ev e{w[at], static_cast<uint8_t>(w[at + 1]), {}};
+    uint32_t const len = w[at + 2];
+    for (uint32_t k = 0; k < len; ++k)
+      e.seq.push_back(static_cast<char>(w[at + 3 + k]));
+    at += 3 + len;
+    return e;
+  };
+  while (at < w.size())
+  {
+    Ev e = event();
+    if (!whole || at + 16 > w.size())
+    {
+      whole = false;
+      break;
+    }
+    Support s;
+    s.hq = w[at]; s.lq = w[at + 1]; s.proper = w[at + 2]; s.first = w[at + 3]; s.reversed = w[at + 4]; s.clipped = w[at + 5];
+    s.max_mapq = static_cast<uint8_t>(w[at + 6]); s.max_distance = static_cast<uint8_t>(w[at + 7]);
+    s.u1 = static_cast<int32_t>(w[at + 8]); s.u2 = static_cast<int32_t>(w[at + 9]); s.u3 = static_cast<int32_t>(w[at + 10]);
+    s.span = static_cast<uint16_t>(w[at + 11]); s.realign = w[at + 12] != 0; s.good = w[at + 13] != 0; s.max_log_qual = w[at + 14];
+    s.file_i = e.type != 'X' ? file_index : 0;
+    uint32_t const n_phase = w[at + 15];
+    at += 16;
+    for (uint32_t k = 0; k < n_phase; ++k)
+    {
+      Ev pe = event();
+      if (!whole || at >= w.size())
+      {
+        whole = false;
+        break;
+      }
+      s.phase[pe] = static_cast<uint16_t>(w[at++]);
+    }
+    if (!whole)
+      break;
+    size_t const b = static_cast<size_t>((static_cast<long>(e.pos) - st.begin) / st.B);
+    st.buckets[b].insert({std::move(e), std::move(s)});
+  }
+  if (!whole)
+  {
+    g_last_error = "gtx_disc_first_pass_haplotypes_device: the device's words do not parse";
+    return GTX_ERR_HIP;
+  }
+  return haplotypes_of(st, out, cap, n_words);
 }

@@ -32,7 +32,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_disc_create", "gtx_disc_destroy", "gtx_disc_events_batch", "gtx_disc_first_pass", "gtx_vcf_header", "gtx_bgzf_compress",
            "gtx_shrink_params_default", "gtx_bam_shrink", "gtx_inflate_raw", "gtx_tabix_build", "gtx_tabix_start", "gtx_pipeline_run", "gtx_regions_run", "gtx_regions_free", "gtx_bam_shrink_multi", "gtx_disc_first_pass_haplotypes", "gtx_disc_merge",
            "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged",
-           "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts"]
+           "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts",
+           "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device"]
 
 
 class GraphView(C.Structure):
@@ -204,6 +205,10 @@ def lib():
         L.gtx_disc_first_pass_haplotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                                      C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_disc_merge.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gtx_disc_first_pass_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.gtx_disc_first_pass_haplotypes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                            C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []
@@ -457,6 +462,28 @@ def graph_from_files(fasta, vcf, region, add_all_variants=False, is_sv_graph=Fal
         table = buf.raw[:int(n.value)].decode()
     tables = _graph_tables(h)
     return (tables, (int(b.value), int(e.value)), table) if with_sv_table else (tables, (int(b.value), int(e.value)))
+
+
+def disc_first_pass_device(handle, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size=50, file_index=None,
+                           stream=None, cap=1 << 16):
+    """gtx_disc_first_pass_device (file_index None) or gtx_disc_first_pass_haplotypes_device over the device arrays of
+    gtx_disc_events_batch (device pointers as integers) -> the result words; the call is repeated once with the size it names when
+    `cap` words are too few.  Raises GtxError on any other status."""
+    L = lib()
+    n_words = C.c_uint64()
+    while True:
+        words = np.zeros(max(int(cap), 1), np.uint32)
+        if file_index is None:
+            rc = L.gtx_disc_first_pass_device(handle, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, _p(words),
+                                              int(cap), C.byref(n_words), stream)
+        else:
+            rc = L.gtx_disc_first_pass_haplotypes_device(handle, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size,
+                                                         file_index, _p(words), int(cap), C.byref(n_words), stream)
+        if rc == 5 and n_words.value > cap:
+            cap = int(n_words.value)
+            continue
+        check(rc)
+        return words[:n_words.value]
 
 
 def pack_nibbles(codes, stride=None):

@@ -1024,8 +1024,9 @@ int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const 
  * add_indel_event_to_bucket src/typer/bucket.cpp:75-182), the correction for reads with 12 and more events and the phase
  * counts between the events of a read (caller.cpp:777-822), the coverage difference arrays, and the two support filters
  * (EventSupport::has_good_support src/typer/event.cpp:226-256 for SNPs; good / realignment support of indels,
- * caller.cpp:990-1186).  Not built: what follows -- the haplotypes of the surviving events, the realignment of reads to the
- * indels (paw::pairwise_alignment, a dependency that is absent from the reference tree), the second pass, the pool merge.
+ * caller.cpp:990-1186) -- on the host over downloaded arrays (gtx_disc_first_pass) or on the device (gtx_disc_first_pass_device) --
+ * and, below, the haplotypes of the surviving events and the merge of the files' results.  Not built: the realignment of reads
+ * to the indels (paw::pairwise_alignment, a dependency that is absent from the reference tree) and the second pass behind it.
  *   gtx_disc_create        the region's reference (upper-case letters; reference[0] = contig position region_begin, 0-based) on `device`
  *   gtx_disc_events_batch  device: the events of n_reads reads in stream order.  d_planes: the reads as plane rows (gtx_pack_planes),
  *                          d_qual: their base qualities (qual_stride bytes per read), d_reads / d_cigar: the bam1_t fields and the raw
@@ -1093,6 +1094,29 @@ int gtx_disc_first_pass_haplotypes(const gtx_disc *, const gtx_disc_read * reads
                                    uint32_t n_reads, const gtx_disc_event * events, uint64_t n_events, const uint8_t * seq, uint32_t seq_stride,
                                    uint32_t bucket_size, int32_t file_index, uint32_t * out, uint64_t cap, uint64_t * n_words);
 int gtx_disc_merge(const uint32_t * into, uint64_t n_into, const uint32_t * from, uint64_t n_from, uint32_t * out, uint64_t cap, uint64_t * n_words);
+
+/* The same two stages over the device arrays of gtx_disc_events_batch, as it takes and leaves them, without a download: the
+ * counted reads' events are put in stream order, keyed by (position, kind, sequence) and sorted stably on the device; one lane
+ * per distinct event runs the reference's sequential state over its events in read order (the counters, the three start
+ * positions, the corrections for reads with 12 and with 18 and more events at their read's place), finds the span of an indel
+ * and applies the support filter of its kind over prefix sums of the coverage arrays; the phase counts are a second sort of
+ * (event, event) pairs.  The inserted bases of an insertion come from the plane rows (four planes give the BAM nibble back, and
+ * only insertions of A / C / G / T are events), so there is no nibble-row argument.  Only the survivors' words come to the
+ * host -- and, for the haplotype stage, which stays host code, plain copies of the two coverage arrays.
+ * gtx_disc_first_pass_device writes the words of gtx_disc_first_pass, gtx_disc_first_pass_haplotypes_device those of
+ * gtx_disc_first_pass_haplotypes, word for word.  d_counts[1] != 0 (the event buffer overflowed) or a read whose events lie
+ * behind d_counts[0]: GTX_ERR_CAPACITY; a gtx_disc made with device -1: GTX_ERR_NO_DEVICE; *n_words > cap: GTX_ERR_CAPACITY with
+ * the size needed.  An event at or behind the region's end never leaves, as the reference cuts the buckets behind the last
+ * ((REF - 1) / bucket_size) off, but stays what it was in the phase entries of others; gtx_disc_events_batch writes none (a read's
+ * walk ends at the region's end).  The calls wait for `stream`; the arrays must be complete on it (or before it) when they are made.  At most
+ * 2^28 events per call. */
+int gtx_disc_first_pass_device(const gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads, const uint32_t * d_cigar,
+                               const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events, const uint32_t * d_counts,
+                               uint32_t bucket_size, uint32_t * out, uint64_t cap, uint64_t * n_words, void * stream);
+int gtx_disc_first_pass_haplotypes_device(const gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+                                          const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
+                                          const uint32_t * d_counts, uint32_t bucket_size, int32_t file_index, uint32_t * out, uint64_t cap,
+                                          uint64_t * n_words, void * stream);
 
 #ifdef __cplusplus
 }
