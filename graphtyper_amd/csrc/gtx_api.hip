@@ -1479,69 +1479,23 @@ __global__ __launch_bounds__(256) void gtx_calls_kernel(GraphView g, uint32_t n_
 // ---------------------------------------------------------------------------------------------------------------
 thread_local std::string g_last_error;
 
-static bool hip_ok(hipError_t e, char const * what)
+// n (at least one) elements into an owner; zero: cleared, and the call returns when they are (dev_zero)
+template <class T>
+static bool dev_alloc(DevPtr<T> & dst, size_t n, char const * what, bool zero = false)
 {
-  if (e == hipSuccess)
+  size_t const bytes = (n ? n : 1) * sizeof(std::conditional_t<std::is_void<T>::value, char, T>); // (a block without a type: n bytes)
+  if (hip_ok(alloc_e(dst, bytes), what) && (!zero || hip_ok(gtx::dev_zero(dst.get(), bytes), what)))
     return true;
-  g_last_error = std::string(what) + ": " + hipGetErrorString(e);
+  dst.reset();
   return false;
 }
 
-template <class T>
-static bool upload(std::vector<void *> & owned, T const *& dst, T const * src, size_t n, char const * what)
-{
-  void * p = nullptr;
-  size_t const bytes = (n ? n : 1) * sizeof(T);
-  if (!hip_ok(gtx::dev_malloc(&p, bytes), what))
-    return false;
-  owned.push_back(p);
-  if (n && !hip_ok(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice), what))
-    return false;
-  dst = static_cast<T const *>(p);
-  return true;
-}
-
-template <class T>
-static bool dev_alloc(T *& dst, size_t n, char const * what, bool zero = false)
-{
-  void * p = nullptr;
-  if (!hip_ok(gtx::dev_malloc(&p, (n ? n : 1) * sizeof(T)), what))
-    return false;
-  if (zero && !hip_ok(gtx::dev_zero(p, (n ? n : 1) * sizeof(T)), what))
-  {
-    (void)gtx::dev_free(p);
-    return false;
-  }
-  dst = static_cast<T *>(p);
-  return true;
-}
-
 // ---- per-call scratch (gtx_ctx.hpp) ----------------------------------------------------------------------------
-static void scratch_free(CallScratch & s)
-{
-  // (d_big_state lies behind d_counters in one allocation: one reset for both)
-  void * ptrs[] = {s.d_counter_sets, s.d_queue1, s.d_queue, s.d_big_tasks, s.d_big_ws, s.d_score_state, s.d_score_queue,
-                   s.d_score_tables, s.d_score_work, s.d_var_masks, s.d_wide_tasks, s.d_wide_ws, s.d_planes, s.d_exact_tasks,
-                   s.d_long_state, s.d_long_tasks, s.d_long_ws};
-  for (void * p : ptrs)
-    if (p)
-      (void)gtx::dev_free(p);
-  for (auto & slot : s.time_ring)
-    for (auto & e : slot)
-      if (e)
-        (void)hipEventDestroy(static_cast<hipEvent_t>(e));
-  if (s.done)
-    (void)hipEventDestroy(static_cast<hipEvent_t>(s.done));
-  if (s.h_span)
-    (void)hipHostFree(s.h_span);
-  s = CallScratch();
-}
-
 // d_counters and the pointers into it name set k of the scratch's two (gtx_ctx.hpp)
 static void counter_set_select(CallScratch & s, uint32_t k)
 {
   s.counter_set = k;
-  s.d_counters = s.d_counter_sets + static_cast<size_t>(k) * CallScratch::COUNTER_PITCH;
+  s.d_counters = s.d_counter_sets.get() + static_cast<size_t>(k) * CallScratch::COUNTER_PITCH;
   s.d_span = reinterpret_cast<unsigned long long *>(s.d_counters + 8 + 48); // (its pinned home is made by the first timed call)
   s.d_big_state = s.has_big ? s.d_counters + 8 : nullptr;
   s.d_wide_state = s.has_wide ? s.d_big_state + 8 : nullptr;
@@ -1551,10 +1505,9 @@ static void counter_set_select(CallScratch & s, uint32_t k)
 static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
 {
   auto s = std::make_unique<CallScratch>();
-  hipEvent_t ev;
+  hipEvent_t ev = nullptr;
   bool ok = hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "scratch event");
-  if (ok)
-    s->done = ev;
+  s->done.reset(ev);
   static_assert(CallScratch::COUNTER_WORDS == 8 + 48 + 4 && CallScratch::COUNTER_WORDS <= CallScratch::COUNTER_PITCH, "counter sets");
   ok = ok && dev_alloc(s->d_counter_sets, 2 * CallScratch::COUNTER_PITCH, "task counters + second-pass state", true); // (two sets: gtx_ctx.hpp)
   s->has_big = !c.params.no_second_pass;
@@ -1563,51 +1516,32 @@ static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
     counter_set_select(*s, 0);
   if (ok && !c.params.no_second_pass)
   {
-    void * ws = nullptr;
     // (workspaces for a small batch -- one workgroup per CU; a large batch grows them to c.big_blocks: align_planes)
     s->big_blocks = std::min<uint32_t>(c.big_blocks, static_cast<uint32_t>(c.n_cu > 0 ? c.n_cu : 256));
-    ok = ok && hip_ok(gtx::dev_malloc(&ws, static_cast<size_t>(s->big_blocks) * sizeof(big::AlignWorkspace)), "second-pass workspaces");
-    s->d_big_ws = ws;
+    ok = ok && dev_alloc(s->d_big_ws, static_cast<size_t>(s->big_blocks) * sizeof(big::AlignWorkspace), "second-pass workspaces");
     if (ok && c.has_wide_sites)
     {
       ok = ok && dev_alloc(s->d_wide_tasks, CallScratch::WIDE_TASK_CAP, "wide-site pass queue");
-      void * wws = nullptr;
-      ok = ok && hip_ok(gtx::dev_malloc(&wws, static_cast<size_t>(CallScratch::WIDE_BLOCKS) * sizeof(wide::AlignWorkspace)), "wide-site pass workspaces");
-      s->d_wide_ws = wws;
+      ok = ok && dev_alloc(s->d_wide_ws, static_cast<size_t>(CallScratch::WIDE_BLOCKS) * sizeof(wide::AlignWorkspace), "wide-site pass workspaces");
     }
     // the exact pass: two queues (what did not fit the tables above; what did not fit a part of the slab) and the slab
     ok = ok && dev_alloc(s->d_exact_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "exact pass queues");
     if (ok && c.params.max_read_len > GTX_MAX_READ)
     {
       // the long reads' passes: tier 1's workspaces (four workgroups per CU), tier 2's queues and the state words of both
-      void * lws = nullptr;
       s->long_blocks = static_cast<uint32_t>(c.n_cu > 0 ? c.n_cu : 256) * 4u;
-      ok = ok && hip_ok(gtx::dev_malloc(&lws, static_cast<size_t>(s->long_blocks) * long_workspace_bytes()), "long-read pass workspaces");
-      s->d_long_ws = lws;
+      ok = ok && dev_alloc(s->d_long_ws, static_cast<size_t>(s->long_blocks) * long_workspace_bytes(), "long-read pass workspaces");
       ok = ok && dev_alloc(s->d_long_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "long-read exact pass queues");
       ok = ok && dev_alloc(s->d_long_state, 8 + 32, "long-read pass state", true);
     }
     ok = ok && dev_alloc(s->d_score_state, 8, "second-pass score state", true); // (two sets of four words; [2]: the work queue's count)
     ok = ok && dev_alloc(s->d_score_queue, gtx_ctx::SCORE_QUEUE_CAP, "second-pass score queue");
     if (c.has_wide_sites)
-    {
-      RecentHapWide * tables = nullptr;
-      ok = ok && dev_alloc(tables, static_cast<size_t>(gtx_ctx::SCORE_BIG_THREADS) * 2 * SCORE_MAX_HAPS_WIDE, "wide-site score tables");
-      s->d_score_tables = tables;
-    }
+      ok = ok && dev_alloc(s->d_score_tables, static_cast<size_t>(gtx_ctx::SCORE_BIG_THREADS) * 2 * SCORE_MAX_HAPS_WIDE * sizeof(RecentHapWide), "wide-site score tables");
     else
-    {
-      RecentHap * tables = nullptr;
-      ok = ok && dev_alloc(tables, static_cast<size_t>(gtx_ctx::SCORE_BIG_THREADS) * 2 * SCORE_MAX_HAPS_BIG, "second-pass score tables");
-      s->d_score_tables = tables;
-    }
+      ok = ok && dev_alloc(s->d_score_tables, static_cast<size_t>(gtx_ctx::SCORE_BIG_THREADS) * 2 * SCORE_MAX_HAPS_BIG * sizeof(RecentHap), "second-pass score tables");
   }
-  if (!ok)
-  {
-    scratch_free(*s);
-    return nullptr;
-  }
-  return s;
+  return ok ? std::move(s) : nullptr;
 }
 
 // A scratch nobody is inside of: the one this stream used last (stream order separates the calls), else one whose last
@@ -1621,7 +1555,7 @@ static CallScratch * scratch_acquire(gtx_ctx & c, hipStream_t stream)
       pick = s.get();
   if (!pick)
     for (auto & s : c.pool)
-      if (!pick && !s->busy && (!s->used || hipEventQuery(static_cast<hipEvent_t>(s->done)) == hipSuccess))
+      if (!pick && !s->busy && (!s->used || hipEventQuery(s->done.get()) == hipSuccess))
         pick = s.get();
   if (!pick)
   {
@@ -1643,7 +1577,7 @@ static CallScratch * scratch_acquire(gtx_ctx & c, hipStream_t stream)
     {
       pick->busy = true; // (ours from here on; the wait itself is outside the lock)
       lock.unlock();
-      (void)hipEventSynchronize(static_cast<hipEvent_t>(pick->done));
+      (void)hipEventSynchronize(pick->done.get());
       return pick;
     }
   }
@@ -1662,7 +1596,7 @@ static CallScratch * scratch_acquire(gtx_ctx & c, hipStream_t stream)
 static void scratch_release(gtx_ctx & c, CallScratch * s, hipStream_t stream, bool was_align, hipStream_t submit_stream)
 {
   s->submit_stream = submit_stream;
-  (void)hipEventRecord(static_cast<hipEvent_t>(s->done), stream);
+  (void)hipEventRecord(s->done.get(), stream);
   std::lock_guard<std::mutex> lock(c.pool_mutex);
   s->used = true;
   s->last_stream = stream;
@@ -1673,13 +1607,13 @@ static void scratch_release(gtx_ctx & c, CallScratch * s, hipStream_t stream, bo
 }
 
 template <class T>
-static bool grow(T *& p, uint64_t & cap, uint64_t want, char const * what)
+static bool grow(DevPtr<T> & p, uint64_t & cap, uint64_t want, char const * what)
 {
   if (want <= cap)
     return true;
-  if (p && (!hip_ok(hipDeviceSynchronize(), what) || !hip_ok(gtx::dev_free(p), what))) // (earlier launches may still use the old buffer)
+  if (p && !hip_ok(hipDeviceSynchronize(), what)) // (earlier launches may still use the old buffer)
     return false;
-  p = nullptr;
+  p.reset();
   cap = 0;
   if (!dev_alloc(p, want, what))
     return false;
@@ -1785,101 +1719,84 @@ int ctx_upload(gtx_ctx & c, int device)
   std::vector<uint8_t> & stage = c.upload_stage; // (lives until the stream has been waited for: gtx_ctx_create drops it)
   size_t cursor = 0;
   auto room = [&](size_t bytes) { size_t const at = cursor; cursor += (std::max<size_t>(bytes, 1) + 255) / 256 * 256; return at; };
-  struct Piece { size_t at; void const * src; size_t bytes; };
+  // a table: where the view keeps its pointer, its host source, its bytes, its place in the block.  The view's pointers have
+  // seven element types and are set only once the block exists, so `dst` is type-erased and written by memcpy below (every
+  // object pointer has one representation here); a typed closure per table would cost an allocation each on a path that takes
+  // well under a millisecond.
+  struct Piece { void * dst; void const * src; size_t bytes; size_t at; };
   std::vector<Piece> pieces;
-  auto place = [&](void const * src, size_t bytes) { pieces.push_back({room(bytes), src, bytes}); return pieces.back().at; };
-  size_t const at_ref_order = place(h.ref_order.data(), h.ref_order.size() * sizeof(h.ref_order[0]));
-  size_t const at_ref_len = place(h.ref_len.data(), h.ref_len.size() * sizeof(h.ref_len[0]));
-  size_t const at_ref_dna = place(h.ref_dna.data(), h.ref_dna.size() * sizeof(h.ref_dna[0]));
-  size_t const at_ref_nvar = place(h.ref_nvar.data(), h.ref_nvar.size() * sizeof(h.ref_nvar[0]));
-  size_t const at_ref_first_var = place(h.ref_first_var.data(), h.ref_first_var.size() * sizeof(h.ref_first_var[0]));
-  size_t const at_var_order = place(h.var_order.data(), h.var_order.size() * sizeof(h.var_order[0]));
-  size_t const at_var_len = place(h.var_len.data(), h.var_len.size() * sizeof(h.var_len[0]));
-  size_t const at_var_dna = place(h.var_dna.data(), h.var_dna.size() * sizeof(h.var_dna[0]));
-  size_t const at_var_out_ref = place(h.var_out_ref.data(), h.var_out_ref.size() * sizeof(h.var_out_ref[0]));
-  size_t const at_site_ref_reach = place(h.site_ref_reach.data(), h.site_ref_reach.size() * sizeof(h.site_ref_reach[0]));
-  size_t const at_site_special_base = place(h.site_special_base.data(), h.site_special_base.size() * sizeof(h.site_special_base[0]));
-  size_t const at_special_ref_reach = place(h.special_ref_reach.data(), h.special_ref_reach.size() * sizeof(h.special_ref_reach[0]));
-  size_t const at_special_actual = place(h.special_actual.data(), h.special_actual.size() * sizeof(h.special_actual[0]));
-  size_t const at_pos_bucket = place(h.pos_bucket.data(), h.pos_bucket.size() * sizeof(h.pos_bucket[0]));
-  size_t const at_codes = place(h.codes.data(), h.codes.size() * sizeof(h.codes[0]));
-  size_t const at_tri_off = place(h.tri_off.data(), h.tri_off.size() * sizeof(h.tri_off[0]));
-  size_t const at_allele_off = place(h.allele_off.data(), h.allele_off.size() * sizeof(h.allele_off[0]));
-  size_t const at_near_last = place(h.near_last.data(), h.near_last.size() * sizeof(h.near_last[0]));
-  size_t const at_near_off = place(h.near_off.data(), h.near_off.size() * sizeof(h.near_off[0]));
+  auto place = [&](auto const *& dst, auto const & host)
+  {
+    static_assert(sizeof(*dst) == sizeof(host[0]), "a table of the view and its host vector have the same element");
+    size_t const bytes = host.size() * sizeof(host[0]);
+    pieces.push_back({&dst, host.data(), bytes, room(bytes)});
+  };
+  place(v.ref_order, h.ref_order);
+  place(v.ref_len, h.ref_len);
+  place(v.ref_dna, h.ref_dna);
+  place(v.ref_nvar, h.ref_nvar);
+  place(v.ref_first_var, h.ref_first_var);
+  place(v.var_order, h.var_order);
+  place(v.var_len, h.var_len);
+  place(v.var_dna, h.var_dna);
+  place(v.var_out_ref, h.var_out_ref);
+  place(v.site_ref_reach, h.site_ref_reach);
+  place(v.site_special_base, h.site_special_base);
+  place(v.special_ref_reach, h.special_ref_reach);
+  place(v.special_actual, h.special_actual);
+  place(v.pos_bucket, h.pos_bucket);
+  place(v.dna, h.codes);
+  place(v.tri_off, h.tri_off);
+  place(v.allele_off, h.allele_off);
+  place(v.near_last, h.near_last);
+  place(v.near_off, h.near_off);
   stage.assign(cursor, 0);
   for (Piece const & pc : pieces)
     if (pc.bytes)
       std::memcpy(stage.data() + pc.at, pc.src, pc.bytes);
-  void * block = nullptr;
-  ok = hip_ok(gtx::dev_malloc(&block, cursor), "graph tables");
+  // a block of the context's own (it lives as long as the context): nullptr, and the message, when there is none
+  auto ctx_alloc = [&c](auto *& dst, size_t bytes, char const * what)
+  {
+    DevPtr<> p;
+    if (!hip_ok(alloc_e(p, bytes), what))
+      return false;
+    dst = static_cast<std::remove_reference_t<decltype(dst)>>(p.get());
+    c.dev_allocs.push_back(std::move(p));
+    return true;
+  };
+  uint8_t * block = nullptr;
+  ok = ctx_alloc(block, cursor, "graph tables");
   if (ok)
   {
-    c.dev_allocs.push_back(block);
     ok = hip_ok(hipMemcpyAsync(block, stage.data(), cursor, hipMemcpyHostToDevice, bs), "graph tables");
-    auto at = [&](auto const *& dst, size_t off) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(static_cast<uint8_t *>(block) + off); };
-    at(v.ref_order, at_ref_order);
-    at(v.ref_len, at_ref_len);
-    at(v.ref_dna, at_ref_dna);
-    at(v.ref_nvar, at_ref_nvar);
-    at(v.ref_first_var, at_ref_first_var);
-    at(v.var_order, at_var_order);
-    at(v.var_len, at_var_len);
-    at(v.var_dna, at_var_dna);
-    at(v.var_out_ref, at_var_out_ref);
-    at(v.site_ref_reach, at_site_ref_reach);
-    at(v.site_special_base, at_site_special_base);
-    at(v.special_ref_reach, at_special_ref_reach);
-    at(v.special_actual, at_special_actual);
-    at(v.pos_bucket, at_pos_bucket);
-    at(v.dna, at_codes);
-    at(v.tri_off, at_tri_off);
-    at(v.allele_off, at_allele_off);
-    at(v.near_last, at_near_last);
-    at(v.near_off, at_near_off);
+    for (Piece const & pc : pieces)
+    {
+      void const * const table = block + pc.at;
+      std::memcpy(pc.dst, &table, sizeof table); // (the view's pointer, whatever it points to)
+    }
   }
   if (ok && h.pos_table_len != 0)
   {
     // position -> where its base is, how far its reference node goes on and back, which node it is: made here from the
     // node tables (flatten_graph fills the host's copies for contexts without a device only)
     uint32_t const n = h.pos_table_len;
-    void *pi = nullptr, *pb = nullptr, *pn = nullptr;
-    ok = hip_ok(gtx::dev_malloc(&pi, n * sizeof(uint32_t)), "pos_info");
-    if (ok)
-      c.dev_allocs.push_back(pi);
-    ok = ok && hip_ok(gtx::dev_malloc(&pb, n), "pos_back");
-    if (ok)
-      c.dev_allocs.push_back(pb);
-    ok = ok && hip_ok(gtx::dev_malloc(&pn, n * sizeof(uint32_t)), "pos_node");
+    uint32_t *pi = nullptr, *pn = nullptr;
+    uint8_t * pb = nullptr;
+    ok = ctx_alloc(pi, n * sizeof(uint32_t), "pos_info") && ctx_alloc(pb, n, "pos_back") && ctx_alloc(pn, n * sizeof(uint32_t), "pos_node");
     if (ok)
     {
-      c.dev_allocs.push_back(pn);
-      v.pos_info = static_cast<uint32_t *>(pi);
-      v.pos_back = static_cast<uint8_t *>(pb);
-      v.pos_node = static_cast<uint32_t *>(pn);
+      v.pos_info = pi;
+      v.pos_back = pb;
+      v.pos_node = pn;
       v.n_pos_info = n;
-      hipLaunchKernelGGL(gtx_pos_tables_kernel, dim3((n + 255u) / 256u), dim3(256), 0, bs, v, n, static_cast<uint32_t *>(pi),
-                         static_cast<uint8_t *>(pb), static_cast<uint32_t *>(pn));
+      hipLaunchKernelGGL(gtx_pos_tables_kernel, dim3((n + 255u) / 256u), dim3(256), 0, bs, v, n, pi, pb, pn);
       ok = hip_ok(hipGetLastError(), "gtx_pos_tables_kernel launch");
     }
   }
   lap("graph tables");
-  void * pf = nullptr;
-  ok = ok && hip_ok(gtx::dev_malloc(&pf, PROF_WORDS * sizeof(unsigned long long)), "profile counters");
-  if (ok)
-  {
-    c.dev_allocs.push_back(pf);
-    v.prof = static_cast<unsigned long long *>(pf);
-    ok = hip_ok(gtx::dev_zero(pf, PROF_WORDS * sizeof(unsigned long long)), "profile counters");
-  }
-  void * ef = nullptr;
-  ok = ok && hip_ok(gtx::dev_malloc(&ef, sizeof(uint32_t)), "error flag");
-  if (ok)
-  {
-    c.dev_allocs.push_back(ef);
-    c.d_error_flag = static_cast<uint32_t *>(ef);
-    ok = hip_ok(gtx::dev_zero(ef, sizeof(uint32_t)), "error flag");
-  }
+  ok = ok && ctx_alloc(v.prof, PROF_WORDS * sizeof(unsigned long long), "profile counters") &&
+       hip_ok(gtx::dev_zero(v.prof, PROF_WORDS * sizeof(unsigned long long)), "profile counters");
+  ok = ok && ctx_alloc(c.d_error_flag, sizeof(uint32_t), "error flag") && hip_ok(gtx::dev_zero(c.d_error_flag, sizeof(uint32_t)), "error flag");
   lap("counters");
   // (what the runtime says about the device and the kernels does not change between contexts: asked once per device -- these
   //  calls take the runtime's lock, which the builder threads of gtx_regions_run share with every launch)
@@ -1925,24 +1842,13 @@ int ctx_upload(gtx_ctx & c, int device)
           c.exact_fixed_parts = true;
         }
     }
-    void * p = nullptr;
-    ok = ok && hip_ok(gtx::dev_malloc(&p, c.big_record_words * sizeof(uint32_t)), "big-record arena");
+    ok = ok && ctx_alloc(c.d_big_records, c.big_record_words * sizeof(uint32_t), "big-record arena");
     if (ok)
-    {
-      c.dev_allocs.push_back(p);
-      c.d_big_records = static_cast<uint32_t *>(p);
-    }
-    if (ok && (c.h_big_seen = static_cast<uint32_t *>(gtx::pinned_slot_get())) != nullptr)
+      c.h_big_seen.reset(static_cast<uint32_t *>(gtx::pinned_slot_get())); // (nullptr: without it the pass is launched whole)
+    if (c.h_big_seen.get())
       c.h_big_seen[0] = c.h_big_seen[2] = 0xFFFFFFFFu; // ([0]: tasks that left the general pass in the last batch, [2]: tasks that reached the exact pass)
-    else
-      c.h_big_seen = nullptr; // (without it the pass is launched whole)
-    ok = ok && hip_ok(gtx::dev_malloc(&p, sizeof(unsigned long long)), "arena cursor");
-    if (ok)
-    {
-      c.dev_allocs.push_back(p);
-      c.d_arena_cursor = static_cast<unsigned long long *>(p);
-      ok = hip_ok(gtx::dev_zero(p, sizeof(unsigned long long)), "arena cursor");
-    }
+    ok = ok && ctx_alloc(c.d_arena_cursor, sizeof(unsigned long long), "arena cursor") &&
+         hip_ok(gtx::dev_zero(c.d_arena_cursor, sizeof(unsigned long long)), "arena cursor");
   }
   if (!ok)
     return GTX_ERR_HIP;
@@ -1975,8 +1881,8 @@ void ctx_release_scratch(gtx_ctx & c)
   for (auto & s : c.pool)
   {
     if (s->used) // (behind the last launch that used it, whichever stream that was on)
-      (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
-    scratch_free(*s);
+      (void)hipEventSynchronize(s->done.get());
+    s.reset(); // (its blocks go back to the cache here, behind the wait)
   }
   c.pool.clear();
   c.last_align = nullptr;
@@ -1990,28 +1896,15 @@ void ctx_release_device(gtx_ctx & c)
     if (!c.quiet) // (gtx_regions_run has waited for the one stream that used the context: no reason to wait for the other regions')
       (void)hipDeviceSynchronize();
   }
-  if (c.h_big_seen)
-  {
-    gtx::pinned_slot_put(c.h_big_seen);
-    c.h_big_seen = nullptr;
-  }
-  for (auto & s : c.pool)
-    scratch_free(*s);
+  // (everything the context owns goes here, behind the wait above, not in its destructor: the cache hands a freed block out again at once)
+  c.h_big_seen.reset();
   c.pool.clear();
   c.last_align = nullptr;
-  for (int k = 0; k < c.n_exact_slots; ++k)
-  {
-    if (c.exact_slot[k].idle)
-      (void)hipEventDestroy(static_cast<hipEvent_t>(c.exact_slot[k].idle));
-    c.exact_slot[k] = gtx_ctx::ExactSlot(); // (the slabs are among dev_allocs)
-  }
+  for (gtx_ctx::ExactSlot & slot : c.exact_slot)
+    slot = gtx_ctx::ExactSlot();
   c.n_exact_slots = 0;
-  for (void * st : c.pipeline_streams_all)
-    (void)hipStreamDestroy(static_cast<hipStream_t>(st));
   c.pipeline_streams_all.clear();
   c.pipeline_streams_idle.clear();
-  for (void * p : c.dev_allocs)
-    (void)gtx::dev_free(p);
   c.dev_allocs.clear();
 }
 
@@ -2063,13 +1956,8 @@ extern "C" int gtx_reads_to_planes(gtx_ctx * c, const uint8_t * d_seq, uint32_t 
     g_last_error = "gtx_reads_to_planes: bad argument (plane rows are 16-byte groups at a 16-byte aligned address)";
     return GTX_ERR_ARG;
   }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   return launch_planes_kernel(d_seq, seq_stride, n_reads, d_planes, plane_stride, static_cast<hipStream_t>(stream));
 }
 
@@ -2117,13 +2005,8 @@ extern "C" int gtx_packed_to_planes(gtx_ctx * c, const uint8_t * d_packed, uint3
   }
   if (!packed_args_ok(d_packed, packed_stride, d_exc_start, d_exc, n_exc, n_reads))
     return GTX_ERR_ARG;
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   return launch_packed_kernel(d_packed, packed_stride, d_exc_start, d_exc, n_exc, n_reads, d_planes, plane_stride, static_cast<hipStream_t>(stream));
 }
 
@@ -2147,7 +2030,7 @@ static gtx_ctx::ExactSlot const * exact_slot_for_call(gtx_ctx & c, uint64_t want
   *wait = false;
   gtx_ctx::ExactSlot * idle_small = nullptr;
   for (int k = 0; k < c.n_exact_slots; ++k)
-    if (hipEventQuery(static_cast<hipEvent_t>(c.exact_slot[k].idle)) == hipSuccess)
+    if (hipEventQuery(c.exact_slot[k].idle.get()) == hipSuccess)
     {
       if (c.exact_slot[k].bytes >= want)
         return &c.exact_slot[k];
@@ -2155,19 +2038,16 @@ static gtx_ctx::ExactSlot const * exact_slot_for_call(gtx_ctx & c, uint64_t want
     }
   if (c.n_exact_slots < gtx_ctx::EXACT_SLOTS)
   {
-    void * p = nullptr;
+    gtx_ctx::ExactSlot & slot = c.exact_slot[c.n_exact_slots];
     hipEvent_t ev = nullptr;
-    bool ok = hip_ok(gtx::dev_malloc(&p, want), "exact pass slab");
-    if (ok)
-      c.dev_allocs.push_back(p);
-    ok = ok && hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "exact pass event");
-    if (ok)
+    if (dev_alloc(slot.slab, want, "exact pass slab") && hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "exact pass event"))
     {
-      c.exact_slot[c.n_exact_slots].slab = static_cast<uint8_t *>(p);
-      c.exact_slot[c.n_exact_slots].bytes = want;
-      c.exact_slot[c.n_exact_slots].idle = ev;
-      return &c.exact_slot[c.n_exact_slots++];
+      slot.bytes = want;
+      slot.idle.reset(ev);
+      ++c.n_exact_slots;
+      return &slot;
     }
+    slot.slab.reset();
     if (c.n_exact_slots == 0)
       return nullptr;
   }
@@ -2234,7 +2114,7 @@ struct AlignCall
   void mark(int k, hipStream_t on) const
   {
     if (timed)
-      (void)hipEventRecord(static_cast<hipEvent_t>(s->time_ring[slot][k]), on);
+      (void)hipEventRecord(s->time_ring[slot][k].get(), on);
   }
 };
 
@@ -2248,7 +2128,7 @@ static int align_setup(AlignCall & a)
   //  CallScratch::d_counter_sets; after a call that failed on its way the set is zeroed here, as every call did before round 6)
   uint32_t const use = s->counter_set ^ 1u;
   if (!s->spare_set_clean &&
-      !hip_ok(hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(use) * CallScratch::COUNTER_PITCH, 0, CallScratch::COUNTER_PITCH * sizeof(uint32_t), a.r.stream), "task counter reset"))
+      !hip_ok(hipMemsetAsync(s->d_counter_sets.get() + static_cast<size_t>(use) * CallScratch::COUNTER_PITCH, 0, CallScratch::COUNTER_PITCH * sizeof(uint32_t), a.r.stream), "task counter reset"))
     return GTX_ERR_HIP;
   counter_set_select(*s, use);
   s->spare_set_clean = false;
@@ -2291,8 +2171,9 @@ static int align_setup(AlignCall & a)
   a.slot = a.timed ? s->ring_used : 0u;
   if (a.timed && !s->h_span) // (pinned: only a host that asks for kernel times pays for it; without it pass 0's time is the interval between its events)
   {
-    if (hipHostMalloc(reinterpret_cast<void **>(&s->h_span), CallScratch::TIME_RING * 2 * sizeof(unsigned long long)) != hipSuccess)
-      s->h_span = nullptr;
+    void * p = nullptr;
+    if (hipHostMalloc(&p, CallScratch::TIME_RING * 2 * sizeof(unsigned long long)) == hipSuccess)
+      s->h_span.reset(static_cast<unsigned long long *>(p));
   }
   if (a.timed && s->h_span)
     s->h_span[2 * a.slot] = s->h_span[2 * a.slot + 1] = 0ull;
@@ -2302,7 +2183,7 @@ static int align_setup(AlignCall & a)
       hipEvent_t ev;
       if (!hip_ok(hipEventCreate(&ev), "pass events"))
         return GTX_ERR_HIP;
-      e = ev;
+      e.reset(ev);
     }
   // (gtx_align_batch_planes_triaged where item i is read i: a bit per read, written by the position-hinted pass, completed behind
   //  the last pass)
@@ -2310,7 +2191,7 @@ static int align_setup(AlignCall & a)
   {
     if (!grow(s->d_var_masks, s->var_mask_cap, (static_cast<uint64_t>(n_reads) + 63u) / 64u, "variant-site bits of the reads"))
       return GTX_ERR_HIP;
-    a.var_masks = s->d_var_masks;
+    a.var_masks = s->d_var_masks.get();
   }
   return GTX_OK;
 }
@@ -2350,13 +2231,13 @@ static int align_front(AlignCall & a)
     uint32_t const hint_threads = 64u * ((hint_long || hint_dense) ? GTX_HINT_WAVES : GTX_HINT_WAVES_LEAN);
     hipLaunchKernelGGL(hint_long ? gtx_align_hinted_long_kernel : hint_dense ? gtx_align_hinted_dense_kernel : gtx_align_hinted_kernel,
                        dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, r.stream, c->dev_graph, c->dev_index, r.seq, r.seq_stride,
-                       r.meta, n, r.records, r.rec_words, force_both, s->d_queue1, s->d_queue, reinterpret_cast<unsigned long long *>(counters + 2),
+                       r.meta, n, r.records, r.rec_words, force_both, s->d_queue1.get(), s->d_queue.get(), reinterpret_cast<unsigned long long *>(counters + 2),
                        static_cast<uint32_t>(force != 0 || (eh && eh[0] == 'd')) | (sv_skips_express ? 4u : 0u)
 #ifdef GTX_PROF
                          | (eh && eh[0] == 'x' ? 2u : 0u)
 #endif
                          ,
-                       r.task_flags, r.compact, a.timed && s->h_span ? s->d_span : static_cast<unsigned long long *>(nullptr), a.var_masks);
+                       r.task_flags, r.compact, a.timed && s->h_span.get() ? s->d_span : static_cast<unsigned long long *>(nullptr), a.var_masks);
     if (!hip_ok(hipGetLastError(), "gtx_align_hinted_kernel launch"))
       return GTX_ERR_HIP;
   }
@@ -2378,22 +2259,22 @@ static int align_front(AlignCall & a)
     //  reads of a small batch; the kernel sizes its claims to the queue)
     uint32_t const blocks4q = static_cast<uint32_t>(std::min<uint64_t>((static_cast<uint64_t>(n) + 3u) / 4u, static_cast<uint64_t>(n_cu) * express4_per_cu));
     hipLaunchKernelGGL(wide ? gtx_align_express4q_wide_kernel : gtx_align_express4q_kernel, dim3(blocks4q), dim3(64), 0, a.sq, c->dev_graph,
-                       c->dev_index, r.seq, r.seq_stride, r.meta, r.records, r.rec_words, counters, s->d_queue1, counters + 3, s->d_queue, counters + 2,
+                       c->dev_index, r.seq, r.seq_stride, r.meta, r.records, r.rec_words, counters, s->d_queue1.get(), counters + 3, s->d_queue.get(), counters + 2,
                        counters + 4, static_cast<uint32_t>(force != 0));
     // (the call's launch of the position-hinted pass has added to the span: home with it -- on the stream of the short queues,
     //  behind the express launch: on the caller's stream the copy sat between the pass and whatever the caller queues behind it)
-    if (a.timed && s->h_span)
-      (void)hipMemcpyAsync(s->h_span + 2 * a.slot, s->d_span, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, a.sq);
+    if (a.timed && s->h_span.get())
+      (void)hipMemcpyAsync(s->h_span.get() + 2 * a.slot, s->d_span, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, a.sq);
   }
   else if (four)
     hipLaunchKernelGGL(wide ? gtx_align_express4_wide_kernel : gtx_align_express4_kernel,
                        dim3(static_cast<uint32_t>(std::min<uint64_t>(chunks, static_cast<uint64_t>(n_cu) * express4_per_cu))), dim3(64), 0, a.sq,
-                       c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, n, r.records, r.rec_words, force_both, counters, s->d_queue,
+                       c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, n, r.records, r.rec_words, force_both, counters, s->d_queue.get(),
                        counters + 2, static_cast<uint32_t>(force != 0));
   else
     hipLaunchKernelGGL(gtx_align_express_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>(chunks, static_cast<uint64_t>(n_cu) * c->express_blocks_per_cu))),
                        dim3(64), 0, a.sq, c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, n, r.records, r.rec_words, force_both, counters,
-                       s->d_queue, counters + 2, static_cast<uint32_t>(force != 0));
+                       s->d_queue.get(), counters + 2, static_cast<uint32_t>(force != 0));
   if (!hip_ok(hipGetLastError(), "express kernel launch"))
     return GTX_ERR_HIP;
   a.mark(2, a.sq);
@@ -2404,7 +2285,7 @@ static int align_front(AlignCall & a)
   a.mark(3, a.sq);
   // (task base 0 and claim 0: the kernel sizes its claims to its queue)
   hipLaunchKernelGGL(gtx_align_kernel, dim3(blocks2), dim3(64), 0, a.sq, c->dev_graph, c->dev_index, r.seq, r.seq_stride, r.meta, r.records,
-                     r.rec_words, s->d_queue, counters + 2, counters + 1, s->d_big_state ? s->d_big_tasks : nullptr, s->big_task_cap, s->d_big_state,
+                     r.rec_words, s->d_queue.get(), counters + 2, counters + 1, s->d_big_state ? s->d_big_tasks.get() : nullptr, s->big_task_cap, s->d_big_state,
                      static_cast<uint32_t>(force == 1), 0u, 0u, counters + 5);
   if (!hip_ok(hipGetLastError(), "gtx_align_kernel launch"))
     return GTX_ERR_HIP;
@@ -2421,9 +2302,9 @@ static LongPassArgs long_args(AlignCall const & a)
   l.max_len = max_read_len_of(a.c->params);
   l.force_both = a.c->params.force_align_both_orientations != 0;
   l.blocks = a.s->long_blocks;
-  l.ws = a.s->d_long_ws;
-  l.tasks = a.s->d_long_tasks;
-  l.state = a.s->d_long_state;
+  l.ws = a.s->d_long_ws.get();
+  l.tasks = a.s->d_long_tasks.get();
+  l.state = a.s->d_long_state.get();
   return l;
 }
 
@@ -2452,39 +2333,38 @@ static int align_hbm(AlignCall & a)
   h.meta = r.meta;
   h.records = r.records;
   h.rec_words = r.rec_words;
-  h.big_tasks = s->d_big_tasks;
+  h.big_tasks = s->d_big_tasks.get();
   h.big_task_cap = s->big_task_cap;
   h.big_state = s->d_big_state;
   // (a large batch: the HBM-table pass with all its workgroups -- the workspaces grow once, the scratch is this call's)
   if (r.n_reads >= gtx_ctx::HBM_SMALL_BATCH && s->big_blocks < c->big_blocks)
   {
-    void * ws = nullptr;
-    if (!hip_ok(gtx::dev_malloc(&ws, static_cast<size_t>(c->big_blocks) * big_workspace_bytes()), "second-pass workspaces"))
+    DevPtr<> ws;
+    if (!dev_alloc(ws, static_cast<size_t>(c->big_blocks) * big_workspace_bytes(), "second-pass workspaces"))
       return GTX_ERR_HIP;
     // (the scratch came back to this stream in stream order only -- scratch_acquire does not wait for the host: an earlier,
     //  small call's HBM-table pass may still be running on the old block, and a block goes back to the cache only when no
     //  kernel can still use it, gtx_devmem.hpp: another context's thread could be handed it for another stream.  Once per
     //  scratch, at its first large batch.)
     if (s->d_big_ws && s->used && s->done)
-      (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
-    (void)gtx::dev_free(s->d_big_ws);
-    s->d_big_ws = ws;
+      (void)hipEventSynchronize(s->done.get());
+    s->d_big_ws = std::move(ws); // (the old block goes back to the cache here, behind the wait)
     s->big_blocks = c->big_blocks;
   }
   h.big_blocks = r.n_reads >= gtx_ctx::HBM_SMALL_BATCH ? s->big_blocks : std::min<uint32_t>(s->big_blocks, static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256));
-  if (c->h_big_seen)
+  if (c->h_big_seen.get())
   {
     // (tasks are claimed one by one from the queue: any number of workgroups does them all -- fewer only take longer when the
     //  guess is too low, and the next call knows better)
-    uint32_t const seen = *static_cast<uint32_t volatile *>(c->h_big_seen);
+    uint32_t const seen = *static_cast<uint32_t volatile *>(c->h_big_seen.get());
     if (adaptive && seen != 0xFFFFFFFFu)
       h.big_blocks = static_cast<uint32_t>(std::min<uint64_t>(h.big_blocks, 2ull * seen + 32u));
   }
-  h.big_ws = s->d_big_ws;
-  h.wide_tasks = s->d_wide_tasks;
+  h.big_ws = s->d_big_ws.get();
+  h.wide_tasks = s->d_wide_tasks.get();
   h.wide_state = s->d_wide_state;
-  h.wide_ws = s->d_wide_ws;
-  h.exact_tasks = s->d_exact_tasks;
+  h.wide_ws = s->d_wide_ws.get();
+  h.exact_tasks = s->d_exact_tasks.get();
   h.exact_state = s->d_exact_state;
   h.exact_slab = nullptr;
   h.exact_slab_bytes = c->exact_slab_bytes;
@@ -2508,27 +2388,27 @@ static int align_hbm(AlignCall & a)
     if (!slot)
       return GTX_ERR_HIP;
     if (wait)
-      (void)hipStreamWaitEvent(a.sq, static_cast<hipEvent_t>(slot->idle), 0);
-    h.exact_slab = slot->slab;
+      (void)hipStreamWaitEvent(a.sq, slot->idle.get(), 0);
+    h.exact_slab = slot->slab.get();
     h.exact_slab_bytes = slot->bytes;
     if (!c->exact_fixed_parts) // (as many parts as the slab has room for: none smaller than 2 MB, 32 MB where allele sets are wide)
       h.exact_parts = static_cast<uint32_t>(std::min<uint64_t>(c->exact_parts, std::max<uint64_t>(1u, (slot->bytes >> 20) / (c->has_wide_sites ? 32u : 2u))));
     // (the launches' grids by what the batch before sent this way -- tasks are claimed one by one, any number of workgroups does
     //  them all: a workgroup of the pass wants 32 KB of LDS, and beside the position-hinted pass of the next batch a thousand of them
     //  waited for that pass' end to find an empty queue -- 150-200 us on the stream of the short queues, the scoring behind them)
-    uint32_t const seen_exact = c->h_big_seen ? static_cast<uint32_t volatile *>(c->h_big_seen)[2] : 0xFFFFFFFFu;
+    uint32_t const seen_exact = c->h_big_seen.get() ? static_cast<uint32_t volatile *>(c->h_big_seen.get())[2] : 0xFFFFFFFFu;
     h.exact_grid_limit = (!adaptive || c->exact_fixed_parts || seen_exact == 0xFFFFFFFFu) ? 0u : 2u * seen_exact + 4u;
     what = launch_exact_passes(h, a.sq);
     // the long reads (gtx_params::max_read_len > GTX_MAX_READ): tier 1 over the batch, tier 2 with the same slab, behind the above
-    if (!what && s->d_long_state)
+    if (!what && s->d_long_state.get())
     {
-      if (!hip_ok(hipMemsetAsync(s->d_long_state, 0, (8 + 32) * sizeof(uint32_t), a.sq), "long-read pass state"))
+      if (!hip_ok(hipMemsetAsync(s->d_long_state.get(), 0, (8 + 32) * sizeof(uint32_t), a.sq), "long-read pass state"))
         return GTX_ERR_HIP;
       what = launch_long_passes(h, long_args(a), a.sq);
     }
-    if (!what && c->h_big_seen)
-      hipLaunchKernelGGL(gtx_seen_kernel, dim3(1), dim3(64), 0, a.sq, c->h_big_seen, s->d_big_state, s->d_exact_state);
-    (void)hipEventRecord(static_cast<hipEvent_t>(slot->idle), a.sq);
+    if (!what && c->h_big_seen.get())
+      hipLaunchKernelGGL(gtx_seen_kernel, dim3(1), dim3(64), 0, a.sq, c->h_big_seen.get(), s->d_big_state, s->d_exact_state);
+    (void)hipEventRecord(slot->idle.get(), a.sq);
   }
   if (what)
   {
@@ -2556,9 +2436,9 @@ static int align_side_bytes(AlignCall & a)
       //  workgroups of two wavefronts take every pair of slots a retiring one frees -- a workgroup of four wavefronts waited for that
       //  pass' end, 130-180 us in the trace of the staggered schedule, and the scoring of this batch with it)
       hipLaunchKernelGGL(gtx_task_flags_fixup_kernel, dim3(static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256) * 16u), dim3(64), 0, a.sq, r.records,
-                         r.rec_words, r.task_flags, s->d_queue1, counters + 3, s->d_queue, counters + 2, a.var_masks);
+                         r.rec_words, r.task_flags, s->d_queue1.get(), counters + 3, s->d_queue.get(), counters + 2, a.var_masks);
       // (... and the long reads, which that pass left as reads it does not align)
-      if (s->d_long_state)
+      if (s->d_long_state.get())
         if (char const * what = launch_long_flags(long_args(a), r.records, r.rec_words, r.task_flags, a.var_masks, a.sq))
         {
           (void)hip_ok(hipErrorLaunchFailure, what);
@@ -2610,7 +2490,7 @@ static void align_end(AlignCall & a)
     (void)hipEventRecord(a.r.done_event, a.sq);
   // the other set of counters, zeroed for the next call behind this call's last launch (the scratch is handed on in the order of
   // that stream, or when the event recorded behind this is through: scratch_release)
-  s->spare_set_clean = hipMemsetAsync(s->d_counter_sets + static_cast<size_t>(s->counter_set ^ 1u) * CallScratch::COUNTER_PITCH, 0,
+  s->spare_set_clean = hipMemsetAsync(s->d_counter_sets.get() + static_cast<size_t>(s->counter_set ^ 1u) * CallScratch::COUNTER_PITCH, 0,
                                       CallScratch::COUNTER_PITCH * sizeof(uint32_t), a.sq) == hipSuccess;
   s->timed_reads = a.r.n_reads;
   if (a.timed)
@@ -2620,11 +2500,8 @@ static void align_end(AlignCall & a)
 // The one way into the alignment passes, behind the argument checks of the eight align entry points
 static int align_call(gtx_ctx * c, AlignRequest r)
 {
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   if (r.tail_stream && !r.front_event)
   {
     g_last_error = "gtx_align_batch_planes_staged: a tail stream needs the front event (it is what the tail stream waits for)";
@@ -2634,8 +2511,6 @@ static int align_call(gtx_ctx * c, AlignRequest r)
   {
     if (!r.front_event && !r.done_event && !r.triage)
       return GTX_OK;
-    if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-      return GTX_ERR_HIP;
     if (r.front_event && !hip_ok(hipEventRecord(r.front_event, r.stream), "front event"))
       return GTX_ERR_HIP;
     if (r.triage && !hip_ok(hipMemsetAsync(r.triage->d_work, 0, GTX_WORK_HEADER_WORDS * sizeof(uint32_t), r.stream), "work queue reset")) // (no read: no item has work)
@@ -2644,8 +2519,6 @@ static int align_call(gtx_ctx * c, AlignRequest r)
       return GTX_ERR_HIP;
     return GTX_OK;
   }
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
   ScratchHold hold{*c, scratch_acquire(*c, r.stream), r.stream, true};
   CallScratch * s = hold.s;
   if (!s)
@@ -2655,9 +2528,9 @@ static int align_call(gtx_ctx * c, AlignRequest r)
     uint32_t const plane_stride = (r.seq_stride + PLANE_GROUP_BYTES - 1u) / PLANE_GROUP_BYTES * PLANE_GROUP_BYTES;
     if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(r.n_reads) * plane_stride, "plane rows"))
       return GTX_ERR_HIP;
-    if (int const rc = launch_planes_kernel(r.seq, r.seq_stride, r.n_reads, s->d_planes, plane_stride, r.stream))
+    if (int const rc = launch_planes_kernel(r.seq, r.seq_stride, r.n_reads, s->d_planes.get(), plane_stride, r.stream))
       return rc;
-    r.seq = s->d_planes;
+    r.seq = s->d_planes.get();
     r.seq_stride = plane_stride;
   }
   else if (r.packed)
@@ -2666,10 +2539,10 @@ static int align_call(gtx_ctx * c, AlignRequest r)
     uint32_t const plane_stride = (2u * r.seq_stride + PLANE_GROUP_BYTES - 1u) / PLANE_GROUP_BYTES * PLANE_GROUP_BYTES;
     if (!grow(s->d_planes, s->planes_cap, static_cast<uint64_t>(r.n_reads) * plane_stride, "plane rows"))
       return GTX_ERR_HIP;
-    if (int const rc = launch_packed_kernel(r.seq, r.seq_stride, r.packed->exc_start, r.packed->exc, r.packed->n_exc, r.n_reads, s->d_planes,
+    if (int const rc = launch_packed_kernel(r.seq, r.seq_stride, r.packed->exc_start, r.packed->exc, r.packed->n_exc, r.n_reads, s->d_planes.get(),
                                             plane_stride, r.stream))
       return rc;
-    r.seq = s->d_planes;
+    r.seq = s->d_planes.get();
     r.seq_stride = plane_stride;
   }
   AlignCall a{c, s, r, r.stream};
@@ -2850,15 +2723,15 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
     uint32_t const used = std::min(u->ring_used, CallScratch::TIME_RING);
     for (uint32_t slot = 0; slot < used; ++slot)
     {
-      auto ev = [&](int k) { return static_cast<hipEvent_t>(u->time_ring[slot][k]); };
+      auto ev = [&](int k) { return u->time_ring[slot][k].get(); };
       if (!hip_ok(hipEventSynchronize(ev(5)), "pass events"))
         continue;
       float d = 0.0f;
       if (hipEventElapsedTime(&d, ev(0), ev(1)) == hipSuccess)
       {
         // (the position-hinted pass by its own clock where the call brought it home: gtx_align_hinted_kernel's span)
-        unsigned long long const t0 = u->h_span ? ~u->h_span[2 * slot] : 0ull, t1 = u->h_span ? u->h_span[2 * slot + 1] : 0ull;
-        if (u->h_span && u->h_span[2 * slot + 1] != 0ull && t1 > t0 && c->wall_clock_khz > 0)
+        unsigned long long const t0 = u->h_span.get() ? ~u->h_span[2 * slot] : 0ull, t1 = u->h_span.get() ? u->h_span[2 * slot + 1] : 0ull;
+        if (u->h_span.get() && u->h_span[2 * slot + 1] != 0ull && t1 > t0 && c->wall_clock_khz > 0)
           d = static_cast<float>(static_cast<double>(t1 - t0) / static_cast<double>(c->wall_clock_khz));
         sum[0] += d;
       }
@@ -2877,7 +2750,7 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
     ms[k] = static_cast<float>(sum[k] / calls);
   // (the last call's counters: when that call was beyond the ring its stream may still be busy -- wait for the scratch's own event)
   if (s->done && s->used)
-    (void)hipEventSynchronize(static_cast<hipEvent_t>(s->done));
+    (void)hipEventSynchronize(s->done.get());
   uint32_t cnt[8] = {}, big[4] = {0, 0, 0, 0};
   (void)hipMemcpy(cnt, s->d_counters, sizeof(cnt), hipMemcpyDeviceToHost);
   if (s->d_big_state)
@@ -2916,20 +2789,166 @@ extern "C" int gtx_ctx_pass_times(gtx_ctx * c, float * ms, uint32_t * queued)
   return rc;
 }
 
+// What a scoring call works on (the entry points below fill it after their own argument checks), like AlignRequest for the
+// alignment.  The replay's pass over the items (replay_collect) takes the same.
+struct ScoreRequest
+{
+  gtx_score_item const * d_items = nullptr;
+  uint32_t const * d_item_words = nullptr; // gtx_score_batch_words' compact form of the items (NULL: none)
+  uint32_t n_items = 0;
+  uint32_t const * d_records = nullptr;
+  uint32_t rec_words = 0;
+  uint8_t const * d_task_flags = nullptr;
+  uint32_t const * d_compact = nullptr; // compact records (d_task_flags is then their side array)
+  uint32_t const * d_work = nullptr;    // gtx_score_batch_queued: the work queue the first stage left behind the alignment
+  gtx_score_buffers const * acc = nullptr;
+  hipStream_t stream = nullptr;
+};
+
+// the kernels' view of the caller's accumulators
+static ScoreAcc score_acc(gtx_ctx const & c, gtx_score_buffers const & acc, ScoreRequest const & r)
+{
+  ScoreAcc a;
+  a.n_samples = acc.n_samples;
+  a.conn_cap = acc.conn_cap;
+  a.log_score = acc.d_log_score;
+  a.gt_cov = acc.d_gt_cov;
+  a.hap_u32 = acc.d_hap_u32;
+  a.stat_u64 = reinterpret_cast<unsigned long long *>(acc.d_stat_u64);
+  a.stat_u32 = acc.d_stat_u32;
+  a.conn_log = acc.d_conn_log;
+  a.conn_count = acc.d_conn_count;
+  a.conn_near = acc.d_conn_near;
+  a.big_records = c.d_big_records;
+  // (the scoring kernel's table names a counter by its distance from the lowest of these: score_core.hpp)
+  unsigned long long base = reinterpret_cast<unsigned long long>(a.log_score);
+  for (void const * p : {static_cast<void const *>(a.gt_cov), static_cast<void const *>(a.hap_u32), static_cast<void const *>(a.stat_u64),
+                         static_cast<void const *>(a.stat_u32), static_cast<void const *>(a.conn_near)})
+    if (p)
+      base = std::min(base, reinterpret_cast<unsigned long long>(p));
+  a.combine_base = base & ~7ull;
+  a.compact = r.d_compact;
+  a.compact_flags = r.d_compact ? r.d_task_flags : nullptr;
+  a.ref_depth = c.params.is_sv_graph ? acc.d_ref_depth : nullptr;
+  a.ref_depth_len = acc.ref_depth_len;
+  return a;
+}
+
+static ScoreParams score_params(gtx_ctx const & c)
+{
+  return ScoreParams{static_cast<uint32_t>(c.params.is_sv_graph != 0), static_cast<uint32_t>(c.params.hq_reads != 0),
+                     static_cast<uint32_t>(c.params.is_segment_calling != 0), 0};
+}
+
+// The kernels that score out of tables in device memory come in pairs: `wide` where the graph has a site of more than 64 alleles,
+// else `big`.  launch(kernel, tables) gets the one this context runs and the scratch's tables as that kernel takes them.
+template <class Big, class Wide, class Launch>
+static void launch_big_or_wide(gtx_ctx const & c, CallScratch const & s, Big big, Wide wide, Launch launch)
+{
+  if (c.has_wide_sites)
+    launch(wide, static_cast<RecentHapWide *>(s.d_score_tables.get()));
+  else
+    launch(big, static_cast<RecentHap *>(s.d_score_tables.get()));
+}
+
+static int score_batch(gtx_ctx * c, ScoreRequest const & r)
+{
+  gtx_score_item const * const d_items = r.d_items;
+  uint32_t const * const d_records = r.d_records, * const d_work = r.d_work;
+  gtx_score_buffers const * const acc = r.acc;
+  uint32_t const n_items = r.n_items, rec_words = r.rec_words;
+  if (!c || !d_items || !d_records || !acc || !acc->d_log_score || !acc->d_gt_cov || !acc->d_hap_u32 || !acc->d_stat_u64 ||
+      !acc->d_stat_u32 || !acc->d_conn_log || !acc->d_conn_count)
+  {
+    g_last_error = "gtx_score_batch: bad argument";
+    return GTX_ERR_ARG;
+  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
+  if (n_items == 0)
+    return GTX_OK;
+  hipStream_t const st = r.stream;
+  ScratchHold hold{*c, scratch_acquire(*c, st), st, false};
+  CallScratch * s = hold.s;
+  if (!s)
+    return GTX_ERR_HIP;
+  ScoreAcc const a = score_acc(*c, *acc, r);
+  if (a.ref_depth && a.ref_depth_len != c->graph.ref_order.back() + c->graph.ref_len.back() - c->graph.ref_order.front())
+  {
+    g_last_error = "gtx_score_batch: ref_depth_len is not the length of the region's reference (gtx_score_layout::ref_depth_len)";
+    return GTX_ERR_ARG;
+  }
+  ScoreParams const par = score_params(*c);
+  uint32_t const blocks = (n_items + GTX_SCORE_THREADS - 1u) / GTX_SCORE_THREADS;
+  bool const second_pass = s->d_score_state.get() != nullptr;
+  // the state of the second pass and the work queue's count: the set of four words the last call's triage kernel zeroed (zeroed
+  // here after a call whose triage launch failed)
+  uint32_t * score_state = nullptr, * score_state_next = nullptr;
+  if (second_pass)
+  {
+    uint32_t const use = s->score_set ^ 1u;
+    score_state = s->d_score_state.get() + 4u * use;
+    score_state_next = s->d_score_state.get() + 4u * (use ^ 1u);
+    if (!s->score_spare_clean && !hip_ok(hipMemsetAsync(score_state, 0, 4 * sizeof(uint32_t), st), "second-pass state + work count reset"))
+      return GTX_ERR_HIP;
+    s->score_set = use;
+    s->score_spare_clean = false;
+  }
+  // work queue of stage 2: room for every item ([0] = count, [1..] = item indices)
+  uint64_t cap = s->score_work_cap ? static_cast<uint64_t>(s->score_work_cap) + 1 : 0;
+  if (!grow(s->d_score_work, cap, static_cast<uint64_t>(n_items) + 1, "score work queue"))
+    return GTX_ERR_HIP;
+  s->score_work_cap = static_cast<uint32_t>(cap - 1);
+  uint32_t const * work_count = second_pass ? score_state + 2 : s->d_score_work.get();
+  uint32_t const * work_queue = s->d_score_work.get() + 1;
+  if (d_work)
+  {
+    // (gtx_score_batch_queued: the first stage ran behind the alignment -- the queue is the caller's; the second pass' state for
+    //  the next call on this scratch is zeroed by the launch that ends this call, below)
+    work_count = d_work;
+    work_queue = d_work + GTX_WORK_HEADER_WORDS;
+  }
+  else
+  {
+    if (!second_pass && !hip_ok(hipMemsetAsync(s->d_score_work.get(), 0, sizeof(uint32_t), st), "score work queue reset"))
+      return GTX_ERR_HIP;
+    hipLaunchKernelGGL(gtx_score_triage_kernel, dim3((n_items + TRIAGE_THREADS * TRIAGE_PER_THREAD - 1) / (TRIAGE_THREADS * TRIAGE_PER_THREAD)), dim3(TRIAGE_THREADS), 0, st, d_items, n_items, d_records, rec_words, s->d_score_work.get() + 1,
+                       second_pass ? score_state + 2 : s->d_score_work.get(), static_cast<uint32_t>(a.ref_depth != nullptr), r.d_task_flags, r.d_item_words, score_state_next);
+    if (!hip_ok(hipGetLastError(), "gtx_score_triage_kernel launch"))
+      return GTX_ERR_HIP;
+    s->score_spare_clean = second_pass;
+  }
+  uint32_t const work_blocks = std::min<uint32_t>(blocks, static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256) * c->score_blocks_per_cu);
+  hipLaunchKernelGGL(gtx_score_kernel, dim3(work_blocks), dim3(GTX_SCORE_THREADS), 0, st, c->dev_graph, par, d_items, work_queue, work_count,
+                     d_records, rec_words, a, c->d_error_flag, second_pass ? s->d_score_queue.get() : nullptr,
+                     second_pass ? gtx_ctx::SCORE_QUEUE_CAP : 0u, score_state);
+  if (!hip_ok(hipGetLastError(), "gtx_score_kernel launch"))
+    return GTX_ERR_HIP;
+  if (second_pass)
+  {
+    uint32_t * const zero_next = d_work ? score_state_next : nullptr; // (the set the next call on this scratch uses: nobody reads it in this call)
+    launch_big_or_wide(*c, *s, gtx_score_big_kernel, gtx_score_wide_kernel, [&](auto kernel, auto * tables) {
+      hipLaunchKernelGGL(kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, par, d_items, d_records, rec_words, a,
+                         c->d_error_flag, s->d_score_queue.get(), gtx_ctx::SCORE_QUEUE_CAP, score_state, tables, zero_next);
+    });
+    if (!hip_ok(hipGetLastError(), "gtx_score_big_kernel launch"))
+      return GTX_ERR_HIP;
+    if (d_work)
+      s->score_spare_clean = true;
+  }
+  return GTX_OK;
+}
+
 extern "C" int gtx_score_batch(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
                                uint32_t rec_words, const gtx_score_buffers * acc, void * stream)
 {
   return gtx_score_batch_flags(c, d_items, n_items, d_records, rec_words, nullptr, acc, stream);
 }
 
-static int score_batch(gtx_ctx * c, const gtx_score_item * d_items, const uint32_t * d_item_words, uint32_t n_items, const uint32_t * d_records,
-                       uint32_t rec_words, const uint8_t * d_task_flags, const gtx_score_buffers * acc, void * stream, const uint32_t * d_compact = nullptr,
-                       const uint32_t * d_work = nullptr);
-
 extern "C" int gtx_score_batch_flags(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
                                      uint32_t rec_words, const uint8_t * d_task_flags, const gtx_score_buffers * acc, void * stream)
 {
-  return score_batch(c, d_items, nullptr, n_items, d_records, rec_words, d_task_flags, acc, stream);
+  return score_batch(c, ScoreRequest{d_items, nullptr, n_items, d_records, rec_words, d_task_flags, nullptr, nullptr, acc, static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int gtx_score_batch_words(gtx_ctx * c, const gtx_score_item * d_items, const uint32_t * d_item_words, uint32_t n_items,
@@ -2941,7 +2960,7 @@ extern "C" int gtx_score_batch_words(gtx_ctx * c, const gtx_score_item * d_items
     g_last_error = "gtx_score_batch_words: the compact item array needs the task-flag array (gtx_align_batch_flags / _planes)";
     return GTX_ERR_ARG;
   }
-  return score_batch(c, d_items, d_item_words, n_items, d_records, rec_words, d_task_flags, acc, stream);
+  return score_batch(c, ScoreRequest{d_items, d_item_words, n_items, d_records, rec_words, d_task_flags, nullptr, nullptr, acc, static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int gtx_score_batch_compact(gtx_ctx * c, const gtx_score_item * d_items, const uint32_t * d_item_words, uint32_t n_items,
@@ -2953,7 +2972,7 @@ extern "C" int gtx_score_batch_compact(gtx_ctx * c, const gtx_score_item * d_ite
     g_last_error = "gtx_score_batch_compact: needs the compact records and the side array gtx_align_batch_planes_compact filled";
     return GTX_ERR_ARG;
   }
-  return score_batch(c, d_items, d_item_words, n_items, d_records, rec_words, d_task_flags, acc, stream, d_compact);
+  return score_batch(c, ScoreRequest{d_items, d_item_words, n_items, d_records, rec_words, d_task_flags, d_compact, nullptr, acc, static_cast<hipStream_t>(stream)});
 }
 
 // stage 2 alone, over the work queue gtx_align_batch_planes_triaged left
@@ -2966,7 +2985,7 @@ extern "C" int gtx_score_batch_queued(gtx_ctx * c, const gtx_score_item * d_item
     g_last_error = "gtx_score_batch_queued: needs the work queue and the side array of gtx_align_batch_planes_triaged";
     return GTX_ERR_ARG;
   }
-  return score_batch(c, d_items, nullptr, n_items, d_records, rec_words, d_task_flags, acc, stream, d_compact, d_work);
+  return score_batch(c, ScoreRequest{d_items, nullptr, n_items, d_records, rec_words, d_task_flags, d_compact, d_work, acc, static_cast<hipStream_t>(stream)});
 }
 
 // gtx_score_batch_words' compact form of the items (host)
@@ -2984,158 +3003,15 @@ extern "C" int gtx_item_words(const gtx_score_item * items, uint32_t n_items, ui
   return GTX_OK;
 }
 
-static int score_batch(gtx_ctx * c, const gtx_score_item * d_items, const uint32_t * d_item_words, uint32_t n_items, const uint32_t * d_records,
-                       uint32_t rec_words, const uint8_t * d_task_flags, const gtx_score_buffers * acc, void * stream, const uint32_t * d_compact,
-                       const uint32_t * d_work)
-{
-  if (!c || !d_items || !d_records || !acc || !acc->d_log_score || !acc->d_gt_cov || !acc->d_hap_u32 || !acc->d_stat_u64 ||
-      !acc->d_stat_u32 || !acc->d_conn_log || !acc->d_conn_count)
-  {
-    g_last_error = "gtx_score_batch: bad argument";
-    return GTX_ERR_ARG;
-  }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
-  if (n_items == 0)
-    return GTX_OK;
-  hipStream_t const st = static_cast<hipStream_t>(stream);
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
-  ScratchHold hold{*c, scratch_acquire(*c, st), st, false};
-  CallScratch * s = hold.s;
-  if (!s)
-    return GTX_ERR_HIP;
-  ScoreAcc a;
-  a.n_samples = acc->n_samples;
-  a.conn_cap = acc->conn_cap;
-  a.log_score = acc->d_log_score;
-  a.gt_cov = acc->d_gt_cov;
-  a.hap_u32 = acc->d_hap_u32;
-  a.stat_u64 = reinterpret_cast<unsigned long long *>(acc->d_stat_u64);
-  a.stat_u32 = acc->d_stat_u32;
-  a.conn_log = acc->d_conn_log;
-  a.conn_count = acc->d_conn_count;
-  a.conn_near = acc->d_conn_near;
-  a.big_records = c->d_big_records;
-  {
-    // (the scoring kernel's table names a counter by its distance from the lowest of these: score_core.hpp)
-    unsigned long long base = reinterpret_cast<unsigned long long>(a.log_score);
-    for (void const * p : {static_cast<void const *>(a.gt_cov), static_cast<void const *>(a.hap_u32), static_cast<void const *>(a.stat_u64),
-                           static_cast<void const *>(a.stat_u32), static_cast<void const *>(a.conn_near)})
-      if (p)
-        base = std::min(base, reinterpret_cast<unsigned long long>(p));
-    a.combine_base = base & ~7ull;
-  }
-  a.compact = d_compact;
-  a.compact_flags = d_compact ? d_task_flags : nullptr;
-  a.ref_depth = c->params.is_sv_graph ? acc->d_ref_depth : nullptr;
-  a.ref_depth_len = acc->ref_depth_len;
-  if (a.ref_depth && a.ref_depth_len != c->graph.ref_order.back() + c->graph.ref_len.back() - c->graph.ref_order.front())
-  {
-    g_last_error = "gtx_score_batch: ref_depth_len is not the length of the region's reference (gtx_score_layout::ref_depth_len)";
-    return GTX_ERR_ARG;
-  }
-  ScoreParams par{static_cast<uint32_t>(c->params.is_sv_graph != 0), static_cast<uint32_t>(c->params.hq_reads != 0),
-                  static_cast<uint32_t>(c->params.is_segment_calling != 0), 0};
-  uint32_t const blocks = (n_items + GTX_SCORE_THREADS - 1u) / GTX_SCORE_THREADS;
-  bool const second_pass = s->d_score_state != nullptr;
-  // the state of the second pass and the work queue's count: the set of four words the last call's triage kernel zeroed (zeroed
-  // here after a call whose triage launch failed)
-  uint32_t * score_state = nullptr, * score_state_next = nullptr;
-  if (second_pass)
-  {
-    uint32_t const use = s->score_set ^ 1u;
-    score_state = s->d_score_state + 4u * use;
-    score_state_next = s->d_score_state + 4u * (use ^ 1u);
-    if (!s->score_spare_clean && !hip_ok(hipMemsetAsync(score_state, 0, 4 * sizeof(uint32_t), st), "second-pass state + work count reset"))
-      return GTX_ERR_HIP;
-    s->score_set = use;
-    s->score_spare_clean = false;
-  }
-  // work queue of stage 2: room for every item ([0] = count, [1..] = item indices)
-  uint64_t cap = s->score_work_cap ? static_cast<uint64_t>(s->score_work_cap) + 1 : 0;
-  if (!grow(s->d_score_work, cap, static_cast<uint64_t>(n_items) + 1, "score work queue"))
-    return GTX_ERR_HIP;
-  s->score_work_cap = static_cast<uint32_t>(cap - 1);
-  uint32_t const * work_count = second_pass ? score_state + 2 : s->d_score_work;
-  uint32_t const * work_queue = s->d_score_work + 1;
-  if (d_work)
-  {
-    // (gtx_score_batch_queued: the first stage ran behind the alignment -- the queue is the caller's; the second pass' state for
-    //  the next call on this scratch is zeroed by the launch that ends this call, below)
-    work_count = d_work;
-    work_queue = d_work + GTX_WORK_HEADER_WORDS;
-  }
-  else
-  {
-    if (!second_pass && !hip_ok(hipMemsetAsync(s->d_score_work, 0, sizeof(uint32_t), st), "score work queue reset"))
-      return GTX_ERR_HIP;
-    hipLaunchKernelGGL(gtx_score_triage_kernel, dim3((n_items + TRIAGE_THREADS * TRIAGE_PER_THREAD - 1) / (TRIAGE_THREADS * TRIAGE_PER_THREAD)), dim3(TRIAGE_THREADS), 0, st, d_items, n_items, d_records, rec_words, s->d_score_work + 1,
-                       second_pass ? score_state + 2 : s->d_score_work, static_cast<uint32_t>(a.ref_depth != nullptr), d_task_flags, d_item_words, score_state_next);
-    if (!hip_ok(hipGetLastError(), "gtx_score_triage_kernel launch"))
-      return GTX_ERR_HIP;
-    s->score_spare_clean = second_pass;
-  }
-  uint32_t const work_blocks = std::min<uint32_t>(blocks, static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256) * c->score_blocks_per_cu);
-  hipLaunchKernelGGL(gtx_score_kernel, dim3(work_blocks), dim3(GTX_SCORE_THREADS), 0, st, c->dev_graph, par, d_items, work_queue, work_count,
-                     d_records, rec_words, a, c->d_error_flag, second_pass ? s->d_score_queue : nullptr,
-                     second_pass ? gtx_ctx::SCORE_QUEUE_CAP : 0u, score_state);
-  if (!hip_ok(hipGetLastError(), "gtx_score_kernel launch"))
-    return GTX_ERR_HIP;
-  if (second_pass)
-  {
-    uint32_t * const zero_next = d_work ? score_state_next : nullptr; // (the set the next call on this scratch uses: nobody reads it in this call)
-    if (c->has_wide_sites)
-      hipLaunchKernelGGL(gtx_score_wide_kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, par, d_items, d_records,
-                         rec_words, a, c->d_error_flag, s->d_score_queue, gtx_ctx::SCORE_QUEUE_CAP, score_state,
-                         static_cast<RecentHapWide *>(s->d_score_tables), zero_next);
-    else
-      hipLaunchKernelGGL(gtx_score_big_kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, par, d_items, d_records,
-                         rec_words, a, c->d_error_flag, s->d_score_queue, gtx_ctx::SCORE_QUEUE_CAP, score_state,
-                         static_cast<RecentHap *>(s->d_score_tables), zero_next);
-    if (!hip_ok(hipGetLastError(), "gtx_score_big_kernel launch"))
-      return GTX_ERR_HIP;
-    if (d_work)
-      s->score_spare_clean = true;
-  }
-  return GTX_OK;
-}
-
-// Sequential replay of the cells that reached the saturation guard of explain_to_score (score_replay.hpp).
-static int scores_replay(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records, uint32_t rec_words,
-                         const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed, uint64_t * n_unsupported, const uint32_t * d_compact,
-                         const uint8_t * d_task_flags);
-
-extern "C" int gtx_scores_replay(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
-                                 uint32_t rec_words, const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed,
-                                 uint64_t * n_unsupported)
-{
-  return scores_replay(c, d_items, n_items, d_records, rec_words, acc, stream, n_replayed, n_unsupported, nullptr, nullptr);
-}
-
-extern "C" int gtx_scores_replay_compact(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
-                                         uint32_t rec_words, const uint32_t * d_compact, const uint8_t * d_task_flags,
-                                         const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed, uint64_t * n_unsupported)
-{
-  if (!d_compact || !d_task_flags)
-  {
-    g_last_error = "gtx_scores_replay_compact: needs the compact records and their side array";
-    return GTX_ERR_ARG;
-  }
-  return scores_replay(c, d_items, n_items, d_records, rec_words, acc, stream, n_replayed, n_unsupported, d_compact, d_task_flags);
-}
-
 // the calls of explain_to_score on the cells of `acc` that stand at the guard, logged by a pass over the items (any order)
-static int replay_collect(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records, uint32_t rec_words,
-                          const gtx_score_buffers * acc, hipStream_t st, const uint32_t * d_compact, const uint8_t * d_task_flags,
-                          std::vector<ReplayEntry> & log, uint64_t & unsupported)
+static int replay_collect(gtx_ctx * c, ScoreRequest const & r, std::vector<ReplayEntry> & log, uint64_t & unsupported)
 {
   log.clear();
   unsupported = 0;
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice") || !hip_ok(hipStreamSynchronize(st), "stream synchronize"))
+  gtx_score_buffers const * const acc = r.acc;
+  hipStream_t const st = r.stream;
+  uint32_t const n_items = r.n_items;
+  if (!hip_ok(hipStreamSynchronize(st), "stream synchronize")) // (the device is the current one: the callers' device_ready)
     return GTX_ERR_HIP;
   HostGraph const & g = c->graph;
   uint64_t const n_cells = static_cast<uint64_t>(acc->n_samples) * g.n_hap;
@@ -3161,59 +3037,42 @@ static int replay_collect(gtx_ctx * c, const gtx_score_item * d_items, uint32_t 
     return GTX_OK;
   ScratchHold hold{*c, scratch_acquire(*c, st), st, false};
   CallScratch * s = hold.s;
-  if (!s || !s->d_score_tables)
+  if (!s || !s->d_score_tables.get())
   {
     g_last_error = "gtx_scores_replay: the context has no second scoring pass (gtx_params::no_second_pass)";
     return s ? GTX_ERR_UNSUPPORTED : GTX_ERR_HIP;
   }
-  uint32_t * d_marked = nullptr;
-  uint32_t * d_count = nullptr;
-  ReplayEntry * d_log = nullptr;
+  DevPtr<uint32_t> d_marked, d_count;
+  DevPtr<ReplayEntry> d_log;
   uint32_t cap = 1u << 20;
   bool ok = dev_alloc(d_marked, marked.size(), "replay bitmap") && dev_alloc(d_count, 1, "replay count") &&
-            hip_ok(hipMemcpy(d_marked, marked.data(), marked.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "replay bitmap");
+            hip_ok(hipMemcpy(d_marked.get(), marked.data(), marked.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "replay bitmap");
   for (int attempt = 0; ok && attempt < 2; ++attempt) // (a second launch when the log was too small)
   {
-    ok = dev_alloc(d_log, cap, "replay log") && hip_ok(gtx::dev_zero(d_count, sizeof(uint32_t)), "replay count");
+    ok = dev_alloc(d_log, cap, "replay log") && hip_ok(gtx::dev_zero(d_count.get(), sizeof(uint32_t)), "replay count");
     if (!ok)
       break;
-    ScoreAcc a;
-    a.n_samples = acc->n_samples;
+    ScoreAcc a = score_acc(*c, *acc, r);
     a.conn_cap = 0;
-    a.log_score = acc->d_log_score;
-    a.gt_cov = acc->d_gt_cov;
-    a.hap_u32 = acc->d_hap_u32;
-    a.stat_u64 = reinterpret_cast<unsigned long long *>(acc->d_stat_u64);
-    a.stat_u32 = acc->d_stat_u32;
-    a.conn_log = acc->d_conn_log;
-    a.conn_count = acc->d_conn_count;
-    a.conn_near = acc->d_conn_near;
-    a.big_records = c->d_big_records;
-    a.compact = d_compact;
-    a.compact_flags = d_compact ? d_task_flags : nullptr;
-    a.replay_cells = d_marked;
-    a.replay_log = d_log;
-    a.replay_count = d_count;
+    a.ref_depth = nullptr; // (score_item looks at it to leave early; the depths were counted by the scoring pass)
+    a.ref_depth_len = 0;
+    a.replay_cells = d_marked.get();
+    a.replay_log = d_log.get();
+    a.replay_count = d_count.get();
     a.replay_cap = cap;
-    ScoreParams par{static_cast<uint32_t>(c->params.is_sv_graph != 0), static_cast<uint32_t>(c->params.hq_reads != 0),
-                    static_cast<uint32_t>(c->params.is_segment_calling != 0), 0};
-    if (c->has_wide_sites)
-      hipLaunchKernelGGL(gtx_score_replay_wide_kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, par, d_items, n_items,
-                         d_records, rec_words, a, c->d_error_flag, static_cast<RecentHapWide *>(s->d_score_tables));
-    else
-      hipLaunchKernelGGL(gtx_score_replay_kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, par, d_items, n_items,
-                         d_records, rec_words, a, c->d_error_flag, static_cast<RecentHap *>(s->d_score_tables));
+    launch_big_or_wide(*c, *s, gtx_score_replay_kernel, gtx_score_replay_wide_kernel, [&](auto kernel, auto * tables) {
+      hipLaunchKernelGGL(kernel, dim3(gtx_ctx::SCORE_BIG_THREADS / 64), dim3(64), 0, st, c->dev_graph, score_params(*c), r.d_items, n_items, r.d_records,
+                         r.rec_words, a, c->d_error_flag, tables);
+    });
     uint32_t wanted = 0;
     ok = hip_ok(hipGetLastError(), "gtx_score_replay_kernel launch") && hip_ok(hipStreamSynchronize(st), "replay") &&
-         hip_ok(hipMemcpy(&wanted, d_count, sizeof(wanted), hipMemcpyDeviceToHost), "replay count");
+         hip_ok(hipMemcpy(&wanted, d_count.get(), sizeof(wanted), hipMemcpyDeviceToHost), "replay count");
     if (ok && wanted <= cap)
     {
       log.resize(wanted);
-      ok = wanted == 0 || hip_ok(hipMemcpy(log.data(), d_log, static_cast<size_t>(wanted) * sizeof(ReplayEntry), hipMemcpyDeviceToHost), "replay log");
+      ok = wanted == 0 || hip_ok(hipMemcpy(log.data(), d_log.get(), static_cast<size_t>(wanted) * sizeof(ReplayEntry), hipMemcpyDeviceToHost), "replay log");
       break;
     }
-    (void)gtx::dev_free(d_log);
-    d_log = nullptr;
     cap = wanted;
     if (attempt == 1)
     {
@@ -3221,10 +3080,7 @@ static int replay_collect(gtx_ctx * c, const gtx_score_item * d_items, uint32_t 
       ok = false;
     }
   }
-  for (void * p : {static_cast<void *>(d_marked), static_cast<void *>(d_count), static_cast<void *>(d_log)})
-    if (p)
-      (void)gtx::dev_free(p);
-  return ok ? GTX_OK : GTX_ERR_HIP;
+  return ok ? GTX_OK : GTX_ERR_HIP; // (every launch above has been waited for: the three blocks go back to the cache)
 }
 
 // the logged calls replayed one by one in call order (score_replay.hpp), the exact rows stored back into `acc`
@@ -3254,32 +3110,48 @@ static int replay_store(gtx_ctx * c, const gtx_score_buffers * acc, std::vector<
   return ok ? GTX_OK : GTX_ERR_HIP;
 }
 
-static int scores_replay(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records, uint32_t rec_words,
-                         const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed, uint64_t * n_unsupported, const uint32_t * d_compact,
-                         const uint8_t * d_task_flags)
+// Sequential replay of the cells that reached the saturation guard of explain_to_score (score_replay.hpp).
+static int scores_replay(gtx_ctx * c, ScoreRequest const & r, uint64_t * n_replayed, uint64_t * n_unsupported)
 {
-  if (!c || !acc || !acc->d_log_score || !acc->d_hap_u32 || (n_items && (!d_items || !d_records)))
+  gtx_score_buffers const * const acc = r.acc;
+  if (!c || !acc || !acc->d_log_score || !acc->d_hap_u32 || (r.n_items && (!r.d_items || !r.d_records)))
   {
     g_last_error = "gtx_scores_replay: bad argument";
     return GTX_ERR_ARG;
   }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   if (n_replayed)
     *n_replayed = 0;
   if (n_unsupported)
     *n_unsupported = 0;
   std::vector<ReplayEntry> log;
   uint64_t unsupported = 0;
-  int rc = replay_collect(c, d_items, n_items, d_records, rec_words, acc, static_cast<hipStream_t>(stream), d_compact, d_task_flags, log, unsupported);
+  int rc = replay_collect(c, r, log, unsupported);
   if (n_unsupported)
     *n_unsupported = unsupported;
   if (rc != GTX_OK || log.empty())
     return rc;
   return replay_store(c, acc, log, n_replayed);
+}
+
+extern "C" int gtx_scores_replay(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
+                                 uint32_t rec_words, const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed,
+                                 uint64_t * n_unsupported)
+{
+  return scores_replay(c, ScoreRequest{d_items, nullptr, n_items, d_records, rec_words, nullptr, nullptr, nullptr, acc, static_cast<hipStream_t>(stream)}, n_replayed, n_unsupported);
+}
+
+extern "C" int gtx_scores_replay_compact(gtx_ctx * c, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
+                                         uint32_t rec_words, const uint32_t * d_compact, const uint8_t * d_task_flags,
+                                         const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed, uint64_t * n_unsupported)
+{
+  if (!d_compact || !d_task_flags)
+  {
+    g_last_error = "gtx_scores_replay_compact: needs the compact records and their side array";
+    return GTX_ERR_ARG;
+  }
+  return scores_replay(c, ScoreRequest{d_items, nullptr, n_items, d_records, rec_words, d_task_flags, d_compact, nullptr, acc, static_cast<hipStream_t>(stream)}, n_replayed, n_unsupported);
 }
 
 // ---- the same in two halves for reads sharded over ranks: every rank logs what ITS items did to the cells that stand
@@ -3297,14 +3169,11 @@ extern "C" int gtx_scores_replay_log(gtx_ctx * c, const gtx_score_item * d_items
   *n = 0;
   if (n_unsupported)
     *n_unsupported = 0;
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   std::vector<ReplayEntry> log;
   uint64_t unsupported = 0;
-  int const rc = replay_collect(c, d_items, n_items, d_records, rec_words, acc, static_cast<hipStream_t>(stream), d_compact, d_task_flags, log, unsupported);
+  int const rc = replay_collect(c, ScoreRequest{d_items, nullptr, n_items, d_records, rec_words, d_task_flags, d_compact, nullptr, acc, static_cast<hipStream_t>(stream)}, log, unsupported);
   if (n_unsupported)
     *n_unsupported = unsupported;
   if (rc != GTX_OK)
@@ -3332,14 +3201,11 @@ extern "C" int gtx_scores_replay_apply(gtx_ctx * c, const gtx_score_buffers * ac
   }
   if (n_replayed)
     *n_replayed = 0;
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   if (n_entries == 0)
     return GTX_OK;
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice") || !hip_ok(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "stream synchronize"))
+  if (!hip_ok(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "stream synchronize"))
     return GTX_ERR_HIP;
   std::vector<ReplayEntry> log(n_entries);
   std::memcpy(log.data(), entries, n_entries * sizeof(ReplayEntry));
@@ -3421,12 +3287,12 @@ extern "C" int gtx_ctx_long_pass_tasks(gtx_ctx * c, uint64_t * out)
     std::lock_guard<std::mutex> lock(c->pool_mutex);
     s = c->last_align;
   }
-  if (!s || !s->d_long_state)
+  if (!s || !s->d_long_state.get())
     return GTX_OK;
   if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
     return GTX_ERR_HIP;
   uint32_t st[8 + 32]; // tier 1's 8 words, then tier 2's 8 per launch and what the last launch handed on (as d_exact_state)
-  if (!hip_ok(hipDeviceSynchronize(), "long-read pass state") || !hip_ok(hipMemcpy(st, s->d_long_state, sizeof(st), hipMemcpyDeviceToHost), "long-read pass state"))
+  if (!hip_ok(hipDeviceSynchronize(), "long-read pass state") || !hip_ok(hipMemcpy(st, s->d_long_state.get(), sizeof(st), hipMemcpyDeviceToHost), "long-read pass state"))
     return GTX_ERR_HIP;
   uint32_t const * x = st + 8;
   out[0] = st[1];
@@ -3454,16 +3320,11 @@ extern "C" int gtx_calls_batch(gtx_ctx * c, const gtx_score_buffers * acc, uint8
     g_last_error = "gtx_calls_batch: bad argument";
     return GTX_ERR_ARG;
   }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   uint64_t const cells = static_cast<uint64_t>(acc->n_samples) * c->dev_graph.n_hap;
   if (cells == 0)
     return GTX_OK;
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
   hipLaunchKernelGGL(gtx_calls_kernel, dim3(static_cast<uint32_t>((cells + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      c->dev_graph, acc->n_samples, acc->d_log_score, acc->d_gt_cov, acc->d_hap_u32, d_phred, d_calls);
   if (!hip_ok(hipGetLastError(), "gtx_calls_kernel launch"))
@@ -3491,32 +3352,26 @@ extern "C" int gtx_records_failed(gtx_ctx * c, const uint32_t * d_records, uint3
   if (!c || !out || rec_words < 8 || (n_reads && !d_records))
     return GTX_ERR_ARG;
   *out = 0;
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(c->device, "context"))
+    return rc;
   if (n_reads == 0)
     return GTX_OK;
-  if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
-    return GTX_ERR_HIP;
   hipStream_t const st = static_cast<hipStream_t>(stream);
-  void * d_count = nullptr;
-  if (!hip_ok(gtx::dev_malloc(&d_count, sizeof(unsigned long long)), "failed-record counter"))
+  DevPtr<unsigned long long> d_count;
+  if (!dev_alloc(d_count, 1, "failed-record counter"))
     return GTX_ERR_HIP;
   unsigned long long n = 0;
-  bool ok = hip_ok(hipMemsetAsync(d_count, 0, sizeof n, st), "failed-record counter");
+  bool ok = hip_ok(hipMemsetAsync(d_count.get(), 0, sizeof n, st), "failed-record counter");
   if (ok)
   {
     uint64_t const slots = 2ull * n_reads;
     uint32_t const blocks = static_cast<uint32_t>(std::min<uint64_t>((slots + 255u) / 256u, 4096u));
-    hipLaunchKernelGGL(gtx_records_failed_kernel, dim3(blocks), dim3(256), 0, st, d_records, rec_words, slots, static_cast<unsigned long long *>(d_count));
+    hipLaunchKernelGGL(gtx_records_failed_kernel, dim3(blocks), dim3(256), 0, st, d_records, rec_words, slots, d_count.get());
     ok = hip_ok(hipGetLastError(), "gtx_records_failed_kernel launch") &&
-         hip_ok(hipMemcpyAsync(&n, d_count, sizeof n, hipMemcpyDeviceToHost, st), "failed-record counter") &&
+         hip_ok(hipMemcpyAsync(&n, d_count.get(), sizeof n, hipMemcpyDeviceToHost, st), "failed-record counter") &&
          hip_ok(hipStreamSynchronize(st), "failed-record counter");
   }
-  (void)gtx::dev_free(d_count);
-  if (!ok)
+  if (!ok) // (the counter goes back to the cache with its owner: the stream has been waited for, or nothing was launched)
     return GTX_ERR_HIP;
   *out = n;
   return GTX_OK;

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "gtx_devmem.hpp"
 #include "gtx_flat.hpp"
 
 namespace gtx
@@ -16,6 +17,8 @@ namespace gtx
 // apart) and to a call on another stream once its `done` event has completed.  That is what makes the entry points
 // re-entrant: the reference calls align_read / update_haplotype_scores_geno from `jobs` threads at the same time
 // (src/typer/caller.cpp:399-436) against one immutable index + graph.
+// Its blocks and events are owners: a scratch that goes gives them back.  (The cache hands a freed block out again at once, so
+// whoever drops a scratch has waited for its `done` event or for the device first: ctx_release_scratch, ctx_release_device.)
 struct CallScratch
 {
   bool busy = false;         // a host thread is inside an entry point with it (guarded by gtx_ctx::pool_mutex)
@@ -23,72 +26,72 @@ struct CallScratch
   void * submit_stream = nullptr; // the stream the last call that used it was made on
   bool used = false;         // `done` has been recorded at least once
   uint64_t use_seq = 0;      // gtx_ctx::scratch_uses at its last release (the smallest: the one whose work was queued longest ago)
-  void * done = nullptr;     // hipEvent_t recorded behind the last launch that uses this scratch
+  Event done;                // recorded behind the last launch that uses this scratch
   // 8 words: [0] read / queue-1 claim counter of pass 1, [1] task counter of pass 2, [2] tasks queued for pass 2, [3] forward
   // tasks the position-hinted pass handed to pass 1, [4] forward tasks pass 1 handed to pass 2, [5] forward tasks pass 2 did
   // (those beyond [4] came straight from the position-hinted pass); [2] and [3] are one 64-bit word for that pass' single add
   // per workgroup
-  uint32_t * d_counters = nullptr;
+  uint32_t * d_counters = nullptr; // (inside d_counter_sets: not an owner)
   // TWO sets of them (round 6): a call counts in the set the call before it did not use and zeroes that one, behind its last
   // launch on its last stream, for the call after it -- the reset used to be a hipMemsetAsync in FRONT of the position-hinted pass
   // on the caller's stream: a fill kernel and the gaps around it, 25 us of an idle chip per step of 0.72 ms.  d_counters and
   // the pointers into the set (d_big_state, d_wide_state, d_exact_state, d_span) name the set of the last call.
   static constexpr uint32_t COUNTER_WORDS = 8 + 48 + 4, COUNTER_PITCH = 64; // (the pass counters; state of the HBM-table, wide-site, exact pass: 8 + 8 + 32 words; span: 2 x 64 bits)
-  uint32_t * d_counter_sets = nullptr; // [2][COUNTER_PITCH]
+  DevPtr<uint32_t> d_counter_sets;     // [2][COUNTER_PITCH]
   uint32_t counter_set = 0;            // the set of the last call
   bool spare_set_clean = true;         // the other one is zero (false after a call that failed on its way)
   bool has_big = false, has_wide = false;
-  uint8_t * d_planes = nullptr;  // plane rows of a batch that came as BAM nibbles (gtx_align_batch; grow-only)
+  DevPtr<uint8_t> d_planes;      // plane rows of a batch that came as BAM nibbles (gtx_align_batch; grow-only)
   uint64_t planes_cap = 0;
-  uint32_t * d_queue1 = nullptr; // reads whose forward task the position-hinted pass declined (grow-only)
+  DevPtr<uint32_t> d_queue1;     // reads whose forward task the position-hinted pass declined (grow-only)
   uint64_t queue1_cap = 0;
-  uint32_t * d_queue = nullptr;  // (read * 2 + orientation) tasks for pass 2 (grow-only)
+  DevPtr<uint32_t> d_queue;      // (read * 2 + orientation) tasks for pass 2 (grow-only)
   uint64_t queue_cap = 0;
   // Pass times of the calls since the last gtx_ctx_kernel_times (a ring: a host that keeps several calls in flight asks
   // once behind them).  Per call 6 events: [0] [1] around the position-hinted pass (caller's stream), [1] [2] around the express
   // pass, [3] [4] around the general pass, [5] the call's end (the stream of the short queues).  Created at a slot's first use.
   static constexpr uint32_t TIME_RING = 32;
-  void * time_ring[TIME_RING][6] = {};
+  Event time_ring[TIME_RING][6];
   uint32_t ring_used = 0;              // calls recorded in epoch ring_epoch (the first TIME_RING of them are kept)
   uint32_t ring_epoch = 0;             // gtx_ctx::time_epoch of the slots above
-  unsigned long long * d_span = nullptr; // behind d_counters: the position-hinted pass' own clock (gtx_api.hip: GTX_HINTED_PASS), reset with the counters
-  unsigned long long * h_span = nullptr; // pinned, [TIME_RING][2]: the spans of the timed calls
+  unsigned long long * d_span = nullptr; // inside d_counter_sets too, behind d_counters: the position-hinted pass' own clock (gtx_api.hip: GTX_HINTED_PASS), reset with the counters
+  PinnedPtr<unsigned long long[]> h_span;  // [TIME_RING][2]: the spans of the timed calls
   uint32_t timed_reads = 0;
   // HBM-table pass (reads that overflowed the LDS-sized tables)
-  uint32_t * d_big_tasks = nullptr;
+  DevPtr<uint32_t> d_big_tasks;
   uint32_t big_task_cap = 0;
-  uint32_t * d_big_state = nullptr; // [0] tasks queued, [1] claim cursor, [3] tasks dropped (list full)
-  void * d_big_ws = nullptr;
+  uint32_t * d_big_state = nullptr; // inside d_counter_sets, like the two states below: [0] tasks queued, [1] claim cursor, [3] tasks dropped (list full)
+  DevPtr<> d_big_ws;
   uint32_t big_blocks = 0;   // workspaces d_big_ws holds (grown to gtx_ctx::big_blocks by the first large batch)
   // wide-site pass (graphs with a site of more than 64 alleles only): tasks that met an allele number >= 64
-  uint32_t * d_wide_tasks = nullptr;
+  DevPtr<uint32_t> d_wide_tasks;
   uint32_t * d_wide_state = nullptr; // inside d_big_state's allocation (same layout)
-  void * d_wide_ws = nullptr;
+  DevPtr<> d_wide_ws;
   static constexpr uint32_t WIDE_TASK_CAP = 1u << 20, WIDE_BLOCKS = 64;
   // exact pass (align_core.hpp: namespace exact): tasks that exceeded the tables of the passes above; tables cut out of a slab
   // at run time -- gtx_ctx::exact_parts workgroups with a part of it each, then one workgroup with all of it
-  uint32_t * d_exact_tasks = nullptr; // three queues of EXACT_TASK_CAP (small parts, large parts, the whole slab)
+  DevPtr<uint32_t> d_exact_tasks;     // three queues of EXACT_TASK_CAP (small parts, large parts, the whole slab)
   uint32_t * d_exact_state = nullptr; // inside d_big_state's allocation: 8 words per launch (same layout) + 8 for what is left
   static constexpr uint32_t EXACT_TASK_CAP = 1u << 20;
   static constexpr uint32_t EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64; // the launch between the small parts and the whole slab
   static constexpr uint32_t EXACT_PART_SITES = 24;       // variant sites a path has room for while a task has a small part of the slab
   static constexpr uint32_t EXACT_PART_CANDIDATES = 8256; // ... and walk candidates (128 live sequences x 64 alleles + a round's slack)
   // the long reads' passes (gtx_params::max_read_len > GTX_MAX_READ only; gtx_hbm_passes.hpp: LongPassArgs)
-  uint32_t * d_long_state = nullptr; // 8 + 32 words, zeroed by every call: tier 1's read cursor and task count, tier 2's queue states
-  uint32_t * d_long_tasks = nullptr; // tier 2's three queues of EXACT_TASK_CAP
-  void * d_long_ws = nullptr;        // long_blocks x longr::AlignWorkspace
+  DevPtr<uint32_t> d_long_state;     // 8 + 32 words, zeroed by every call: tier 1's read cursor and task count, tier 2's queue states
+  DevPtr<uint32_t> d_long_tasks;     // tier 2's three queues of EXACT_TASK_CAP
+  DevPtr<> d_long_ws;                // long_blocks x longr::AlignWorkspace
   uint32_t long_blocks = 0;
   // second scoring pass (items whose reads touch more variant sites than the main pass' tables hold)
-  uint32_t * d_score_state = nullptr; // two sets of 4 words, used in turn ([0] items queued, [2] the work queue's count): the triage kernel of a call zeroes the other set
+  DevPtr<uint32_t> d_score_state;     // two sets of 4 words, used in turn ([0] items queued, [2] the work queue's count): the triage kernel of a call zeroes the other set
   uint32_t score_set = 0;
   bool score_spare_clean = true;
-  uint32_t * d_score_queue = nullptr;
-  void * d_score_tables = nullptr;
-  uint32_t * d_score_work = nullptr; // [0] number of items the triage kernel found worth scoring, [1..] their indices (grow-only)
+  DevPtr<uint32_t> d_score_queue;
+  DevPtr<> d_score_tables;
+  DevPtr<uint32_t> d_score_work;     // [0] number of items the triage kernel found worth scoring, [1..] their indices (grow-only)
   uint32_t score_work_cap = 0;
   // gtx_align_batch_planes_triaged, items that are the batch's reads: a bit per read (a word per wavefront of the position-hinted
   // pass) -- the forward record carries a variant site (grow-only)
-  unsigned long long * d_var_masks = nullptr;
+  DevPtr<unsigned long long> d_var_masks;
   uint64_t var_mask_cap = 0;
 };
 } // namespace gtx
@@ -101,7 +104,7 @@ struct gtx_ctx
   int device = -1; // -1: inspection-only context (no device entry point works)
   int n_cu = 0;
   uint32_t wall_clock_khz = 100000; // the rate of wall_clock64() (hipDeviceAttributeWallClockRate)
-  std::vector<void *> dev_allocs;
+  std::vector<gtx::DevPtr<>> dev_allocs; // the blocks behind dev_graph, dev_index and the d_ pointers below
   bool quiet = false; // set by a caller that knows every launch on this context has completed (ctx_release_device then does not wait for the device)
   std::vector<uint8_t> upload_stage; // host source of the graph tables' one asynchronous copy (ctx_upload); empty once the context is made
   gtx::GraphView dev_graph{};
@@ -116,7 +119,7 @@ struct gtx_ctx
   // the value read here may be a call or two old): the pass is launched with as many workgroups as that many tasks can use
   // instead of all of them -- nearly every batch queues nothing, and 2 048 wavefronts of 128 registers that only look at an empty
   // queue waited a quarter of a millisecond for room beside the other stream's kernels.  0xFFFFFFFF: nothing seen yet.
-  uint32_t * h_big_seen = nullptr;
+  gtx::PinnedSlot<uint32_t[]> h_big_seen;
   static constexpr uint32_t HBM_SMALL_BATCH = 1u << 20; // reads: below this a call takes the small configuration of the passes behind the general one
   bool exact_mb_given = false;   // gtx_params::exact_pass_mb / GTX_EXACT_PASS_MB: every call gets that slab
   bool has_wide_sites = false; // some site has more than 64 alleles: the wide-site passes (alignment, scoring) exist
@@ -129,9 +132,9 @@ struct gtx_ctx
   uint64_t exact_slab_bytes = 0;
   struct ExactSlot
   {
-    uint8_t * slab = nullptr;
-    uint64_t bytes = 0;    // (a slot made for a small batch is a quarter of the size: see exact_slab_for)
-    void * idle = nullptr; // hipEvent_t behind the slab's last exact launches
+    gtx::DevPtr<uint8_t> slab;
+    uint64_t bytes = 0; // (a slot made for a small batch is a quarter of the size: see exact_slab_for)
+    gtx::Event idle;    // behind the slab's last exact launches
   };
   static constexpr int EXACT_SLOTS = 4;
   ExactSlot exact_slot[EXACT_SLOTS];
@@ -149,7 +152,8 @@ struct gtx_ctx
   // events that were recorded on them -- a destroyed stream behind such an event is an error at the next query), idle ones
   // are taken again by the next run
   std::mutex pipeline_mutex;
-  std::vector<void *> pipeline_streams_idle, pipeline_streams_all; // hipStream_t
+  std::vector<void *> pipeline_streams_idle; // hipStream_t, each one of pipeline_streams_all
+  std::vector<std::unique_ptr<ihipStream_t, gtx::Free<hipStreamDestroy>>> pipeline_streams_all; // (destroyed behind ctx_release_device's wait: no wait of their own)
   // pool of per-call scratch (see CallScratch)
   std::mutex pool_mutex;
   std::vector<std::unique_ptr<gtx::CallScratch>> pool;

@@ -14,10 +14,7 @@
 // Device again: gtx_disc_first_pass_device does the host stage's work up to and including the filters over the device arrays
 // (sort by event, one lane per distinct event in read order, a second sort for the phase counts; the second half of this file),
 // with the accumulation step and the filters of gtx_disc_support.hpp, which the host stage calls too.
-#include <cstring> // (rocPRIM's texture iterator calls memset on the host)
-
 #include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <limits>
@@ -31,21 +28,17 @@
 #include "../../include/gtx.h"
 #include "graph_dev.hpp"
 #include "gtx_devmem.hpp"
+#include "gtx_devprim.hpp"
 #include "gtx_disc_support.hpp"
-
-namespace gtx
-{
-extern thread_local std::string g_last_error;
-}
 
 struct gtx_disc
 {
   int device = -1;
   int64_t region_begin = 0;
   std::string reference; // region's bases as given (upper case letters)
-  uint32_t * d_refp = nullptr;
+  gtx::DevPtr<uint32_t> d_refp; // (gtx_disc_destroy waits for the device before the two blocks go back to the cache)
   uint32_t ref_groups = 0;
-  uint8_t * d_refc = nullptr; // the letters themselves (the span of an indel compares them as the host does)
+  gtx::DevPtr<uint8_t> d_refc; // the letters themselves (the span of an indel compares them as the host does)
 };
 
 namespace
@@ -249,20 +242,13 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
     for (uint32_t b = 0; b < 4; ++b)
       planes[4 * (i >> 5) + b] |= ((code >> b) & 1u) << (i & 31u);
   }
-  void *p = nullptr, *c = nullptr;
-  if (hipSetDevice(device) != hipSuccess || gtx::dev_malloc(&p, planes.size() * 4) != hipSuccess ||
-      hipMemcpy(p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess || gtx::dev_malloc(&c, reference_len) != hipSuccess ||
-      hipMemcpy(c, reference, reference_len, hipMemcpyHostToDevice) != hipSuccess)
+  if (hipSetDevice(device) != hipSuccess || !alloc(d->d_refp, planes.size() * 4) ||
+      hipMemcpy(d->d_refp.get(), planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess || !alloc(d->d_refc, reference_len) ||
+      hipMemcpy(d->d_refc.get(), reference, reference_len, hipMemcpyHostToDevice) != hipSuccess)
   {
-    if (p)
-      (void)gtx::dev_free(p);
-    if (c)
-      (void)gtx::dev_free(c);
     g_last_error = "gtx_disc_create: upload of the reference failed";
     return GTX_ERR_HIP;
   }
-  d->d_refp = static_cast<uint32_t *>(p);
-  d->d_refc = static_cast<uint8_t *>(c);
   *out = d.release();
   return GTX_OK;
 }
@@ -275,8 +261,8 @@ extern "C" void gtx_disc_destroy(gtx_disc * d)
   {
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    (void)gtx::dev_free(d->d_refp);
-    (void)gtx::dev_free(d->d_refc);
+    d->d_refp.reset();
+    d->d_refc.reset();
   }
   delete d;
 }
@@ -291,16 +277,11 @@ extern "C" int gtx_disc_events_batch(gtx_disc * d, const uint8_t * d_planes, uin
     g_last_error = "gtx_disc_events_batch: bad argument";
     return GTX_ERR_ARG;
   }
-  if (d->device < 0)
-  {
-    g_last_error = "gtx_disc_events_batch: the object was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = device_ready(d->device, "gtx_disc_events_batch: the object"))
+    return rc;
   if (n_reads == 0)
     return GTX_OK;
-  if (hipSetDevice(d->device) != hipSuccess)
-    return GTX_ERR_HIP;
-  hipLaunchKernelGGL(gtx_disc_events_kernel, dim3((n_reads + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), d->d_refp, d->ref_groups,
+  hipLaunchKernelGGL(gtx_disc_events_kernel, dim3((n_reads + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), d->d_refp.get(), d->ref_groups,
                      static_cast<long>(d->reference.size()), static_cast<long>(d->region_begin), d_planes, plane_stride, d_qual, qual_stride, d_reads,
                      d_cigar, n_reads, d_events, event_cap, d_counts, d_read_out);
   if (hipGetLastError() != hipSuccess)
@@ -1242,66 +1223,18 @@ __global__ __launch_bounds__(DTB) void gtx_disc_emit_kernel(DiscInput in, uint32
   *n_phase = np;
 }
 
-bool disc_ok(hipError_t e, char const * what)
-{
-  if (e == hipSuccess)
-    return true;
-  g_last_error = std::string("gtx_disc_first_pass_device: ") + what + ": " + hipGetErrorString(e);
-  return false;
-}
-
-struct DiscPool // temporary blocks of one pass; they go back to the cache when the stream is through with them
-{
-  std::vector<void *> temps;
-  hipStream_t stream = nullptr;
-  bool fine = true;
-  template <class T>
-  T * get(size_t n, char const * what, int fill = -1)
-  {
-    void * p = nullptr;
-    if (!fine)
-      return nullptr;
-    fine = disc_ok(gtx::dev_malloc(&p, (n ? n : 1) * sizeof(T)), what);
-    if (fine && fill >= 0)
-      fine = disc_ok(hipMemsetAsync(p, fill, (n ? n : 1) * sizeof(T), stream), what);
-    if (p)
-      temps.push_back(p);
-    return static_cast<T *>(p);
-  }
-  ~DiscPool()
-  {
-    if (!temps.empty())
-      (void)hipStreamSynchronize(stream);
-    for (void * p : temps)
-      (void)gtx::dev_free(p);
-  }
-};
-
-bool disc_scan(DiscPool & pool, uint32_t const * in, uint32_t * out, size_t n, bool inclusive)
-{
-  size_t bytes = 0;
-  hipError_t e = inclusive ? rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::plus<uint32_t>(), pool.stream)
-                           : rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), pool.stream);
-  if (!disc_ok(e, "scan (size)"))
-    return false;
-  void * tmp = pool.get<char>(bytes, "scan temporary");
-  if (!pool.fine)
-    return false;
-  e = inclusive ? rocprim::inclusive_scan(tmp, bytes, in, out, n, rocprim::plus<uint32_t>(), pool.stream)
-                : rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), pool.stream);
-  return disc_ok(e, "scan");
-}
+constexpr char const * MSG_PREFIX = "gtx_disc_first_pass_device: "; // of the device pass' HIP error messages (its pool carries it too)
 
 bool disc_download_async(void * to, void const * from, size_t bytes, hipStream_t stream)
 {
-  return disc_ok(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, stream), "download");
+  return hip_ok(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, stream), "download", MSG_PREFIX);
 }
 
-bool disc_wait(hipStream_t stream) { return disc_ok(hipStreamSynchronize(stream), "synchronise"); }
+bool disc_wait(hipStream_t stream) { return hip_ok(hipStreamSynchronize(stream), "synchronise", MSG_PREFIX); }
 
 bool disc_download(void * to, void const * from, size_t bytes, hipStream_t stream) { return disc_download_async(to, from, bytes, stream) && disc_wait(stream); }
 
-bool disc_launched() { return disc_ok(hipGetLastError(), "kernel launch"); }
+bool disc_launched() { return hip_ok(hipGetLastError(), "kernel launch", MSG_PREFIX); }
 
 struct DiscDeviceResult
 {
@@ -1310,11 +1243,11 @@ struct DiscDeviceResult
   uint32_t *d_up = nullptr, *d_down = nullptr; // cov_up / cov_down (REF + 1 words each)
 };
 
-int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
+int disc_device_pass(const gtx_disc * d, TempPool & pool, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads,
                      const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
                      const uint32_t * d_counts, uint32_t bucket_size, DiscDeviceResult & res)
 {
-  pool.stream = stream;
+  hipStream_t const stream = pool.stream;
   long const REF = static_cast<long>(d->reference.size());
   uint32_t counts[2] = {0, 0};
   if (!disc_download(counts, d_counts, sizeof counts, stream))
@@ -1329,7 +1262,7 @@ int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, co
     g_last_error = "gtx_disc_first_pass_device: more than 2^28 events in one pass";
     return GTX_ERR_UNSUPPORTED;
   }
-  DiscInput in{d_events, counts[0], d_reads, d_read_out, d_cigar, n_reads, d_planes, plane_stride, d->d_refc, REF, static_cast<long>(d->region_begin),
+  DiscInput in{d_events, counts[0], d_reads, d_read_out, d_cigar, n_reads, d_planes, plane_stride, d->d_refc.get(), REF, static_cast<long>(d->region_begin),
                static_cast<long>(bucket_size)};
   uint32_t * meta = pool.get<uint32_t>(M_WORDS, "counters", 0);
   res.d_up = pool.get<uint32_t>(REF + 1, "cov_up", 0);
@@ -1349,13 +1282,13 @@ int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, co
   hipLaunchKernelGGL(gtx_disc_end_kernel, dim3(dblocks(n_reads)), dim3(DTB), 0, stream, d_read_out, n_reads, meta);
   hipLaunchKernelGGL(gtx_disc_reads_kernel, dim3(dblocks(n_reads + 1)), dim3(DTB), 0, stream, in, meta, n_ev, n_pairs, res.d_up, res.d_down);
   hipLaunchKernelGGL(gtx_disc_delta_kernel, dim3(dblocks(REF + 1)), dim3(DTB), 0, stream, res.d_up, res.d_down, static_cast<uint32_t>(REF + 1), delta);
-  if (!disc_scan(pool, n_ev, ev_off, n_reads + 1, false) || !disc_scan(pool, n_pairs, pair_off, n_reads + 1, false) ||
-      !disc_scan(pool, delta, cov_delta, REF + 1, false) || !disc_scan(pool, res.d_down, cov_down, REF + 1, false))
+  if (!exclusive_sum(pool, n_ev, ev_off, n_reads + 1, "scan", "scan temporary") || !exclusive_sum(pool, n_pairs, pair_off, n_reads + 1, "scan", "scan temporary") ||
+      !exclusive_sum(pool, delta, cov_delta, REF + 1, "scan", "scan temporary") || !exclusive_sum(pool, res.d_down, cov_down, REF + 1, "scan", "scan temporary"))
     return GTX_ERR_HIP;
   // the two totals join the counters: one copy, one wait
   uint32_t head_words[M_WORDS];
-  if (!disc_launched() || !disc_ok(hipMemcpyAsync(meta + M_EVENTS, ev_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
-      !disc_ok(hipMemcpyAsync(meta + M_PAIRS, pair_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
+  if (!disc_launched() || !pool.ok(hipMemcpyAsync(meta + M_EVENTS, ev_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
+      !pool.ok(hipMemcpyAsync(meta + M_PAIRS, pair_off + n_reads, 4, hipMemcpyDeviceToDevice, stream), "copy") ||
       !disc_download(head_words, meta, sizeof head_words, stream))
     return GTX_ERR_HIP;
   uint32_t const ne = head_words[M_EVENTS], np = head_words[M_PAIRS];
@@ -1383,17 +1316,11 @@ int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, co
   if (!pool.fine)
     return GTX_ERR_HIP;
   hipLaunchKernelGGL(gtx_disc_keys_kernel, dim3(dblocks(counts[0])), dim3(DTB), 0, stream, in, meta, ev_off, keys_in, vals_in);
-  {
-    size_t bytes = 0;
-    if (!disc_ok(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys, vals_in, vals, ne, 0u, 64u, stream), "radix sort (size)"))
-      return GTX_ERR_HIP;
-    void * tmp = pool.get<char>(bytes, "sort temporary");
-    if (!pool.fine || !disc_ok(rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys, vals_in, vals, ne, 0u, 64u, stream), "radix sort"))
-      return GTX_ERR_HIP;
-  }
+  if (!sort_pairs(pool, keys_in, keys, vals_in, vals, ne, 64u, "radix sort", "sort temporary"))
+    return GTX_ERR_HIP;
   hipLaunchKernelGGL(gtx_disc_ties_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, keys, vals, ne);
   hipLaunchKernelGGL(gtx_disc_heads_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, keys, vals, ne, head);
-  if (!disc_scan(pool, head, gid1, ne, true))
+  if (!inclusive_scan(pool, head, gid1, ne, rocprim::plus<uint32_t>(), "scan", "scan temporary"))
     return GTX_ERR_HIP;
   hipLaunchKernelGGL(gtx_disc_groups_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, head, gid1, vals, ne, gstart, gid_of, meta);
   // the phase counts: pairs of groups, sorted, run lengths
@@ -1411,14 +1338,10 @@ int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, co
     if (!pool.fine)
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(gtx_disc_pairs_kernel, dim3(dblocks(n_reads)), dim3(DTB), 0, stream, in, pair_off, gid_of, shift, pairs_in);
-    size_t bytes = 0;
-    if (!disc_ok(rocprim::radix_sort_keys(nullptr, bytes, pairs_in, pairs, np, 0u, 2 * shift, stream), "radix sort of the pairs (size)"))
-      return GTX_ERR_HIP;
-    void * tmp = pool.get<char>(bytes, "sort temporary");
-    if (!pool.fine || !disc_ok(rocprim::radix_sort_keys(tmp, bytes, pairs_in, pairs, np, 0u, 2 * shift, stream), "radix sort of the pairs"))
+    if (!sort_keys(pool, pairs_in, pairs, np, 2 * shift, "radix sort of the pairs", "sort temporary"))
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(gtx_disc_pair_heads_kernel, dim3(dblocks(np)), dim3(DTB), 0, stream, pairs, np, phead);
-    if (!disc_scan(pool, phead, rid1, np, true))
+    if (!inclusive_scan(pool, phead, rid1, np, rocprim::plus<uint32_t>(), "scan", "scan temporary"))
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(gtx_disc_runs_kernel, dim3(dblocks(np)), dim3(DTB), 0, stream, pairs, phead, rid1, np, shift, run_key, run_start, phase_first, meta);
   }
@@ -1426,7 +1349,7 @@ int disc_device_pass(const gtx_disc * d, hipStream_t stream, DiscPool & pool, co
     return GTX_ERR_HIP;
   hipLaunchKernelGGL(gtx_disc_walk_kernel, dim3(dblocks(ne)), dim3(DTB), 0, stream, in, meta, keys, vals, gstart, cov_delta, cov_down, phase_first, groups);
   hipLaunchKernelGGL(gtx_disc_sizes_kernel, dim3(dblocks(ne + 1)), dim3(DTB), 0, stream, meta, groups, run_key, shift, ne, words);
-  if (!disc_scan(pool, words, word_off, ne + 1, false))
+  if (!exclusive_sum(pool, words, word_off, ne + 1, "scan", "scan temporary"))
     return GTX_ERR_HIP;
   uint32_t total = 0;
   if (!disc_launched() || !disc_download(&total, word_off + ne, 4, stream))
@@ -1452,12 +1375,7 @@ int disc_device_args(char const * name, const gtx_disc * d, const uint8_t * d_pl
     return GTX_ERR_ARG;
   }
   (void)d_events; // (may be NULL when no event was made)
-  if (d->device < 0)
-  {
-    g_last_error = std::string(name) + ": the object was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
-  return hipSetDevice(d->device) == hipSuccess ? GTX_OK : GTX_ERR_HIP;
+  return device_ready(d->device, name, ": the object");
 }
 } // namespace
 
@@ -1470,9 +1388,9 @@ extern "C" int gtx_disc_first_pass_device(const gtx_disc * d, const uint8_t * d_
   if (rc != GTX_OK)
     return rc;
   hipStream_t const s = static_cast<hipStream_t>(stream);
-  DiscPool pool;
+  TempPool pool(s, MSG_PREFIX);
   DiscDeviceResult res;
-  rc = disc_device_pass(d, s, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
+  rc = disc_device_pass(d, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
   if (rc != GTX_OK)
     return rc;
   *n_words = res.n_words;
@@ -1499,9 +1417,9 @@ extern "C" int gtx_disc_first_pass_haplotypes_device(const gtx_disc * d, const u
   st.begin = d->region_begin;
   std::vector<uint32_t> w;
   {
-    DiscPool pool;
+    TempPool pool(hs, MSG_PREFIX);
     DiscDeviceResult res;
-    rc = disc_device_pass(d, hs, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
+    rc = disc_device_pass(d, pool, d_planes, plane_stride, d_reads, d_cigar, d_read_out, n_reads, d_events, d_counts, bucket_size, res);
     if (rc != GTX_OK)
       return rc;
     w.resize(res.n_words);

@@ -12,10 +12,7 @@
 //   hash tables                               slots claimed with atomicCAS on the count word, filled front to back
 //   hint tables                               one thread per key (neighbour verdict, filters), one per position (flags)
 // The per-key / per-position decisions are the text of index_build.hpp, shared with the host build.
-#include <cstring> // (rocPRIM's texture iterator calls memset on the host)
-
 #include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cstdio>
@@ -24,57 +21,14 @@
 
 #include "gtx_ctx.hpp"
 #include "gtx_devmem.hpp"
+#include "gtx_devprim.hpp"
 #include "index_build.hpp"
 
 namespace gtx
 {
 namespace
 {
-bool ok_hip(hipError_t e, char const * what)
-{
-  if (e == hipSuccess)
-    return true;
-  g_last_error = std::string("index build: ") + what + ": " + hipGetErrorString(e);
-  return false;
-}
-
-// device buffers of the build; the ones the kernels keep reading are handed to the context, the rest is freed
-struct Pool
-{
-  std::vector<void *> temps;
-  bool fine = true;
-  template <class T>
-  T * get(size_t n, char const * what, bool zero = false)
-  {
-    void * p = nullptr;
-    if (!fine)
-      return nullptr;
-    fine = ok_hip(gtx::dev_malloc(&p, (n ? n : 1) * sizeof(T)), what);
-    if (fine && zero)
-      fine = ok_hip(gtx::dev_zero_async(p, (n ? n : 1) * sizeof(T)), what); // (its first user is a later launch on the same stream)
-    if (p)
-      temps.push_back(p);
-    return static_cast<T *>(p);
-  }
-  template <class T>
-  T * keep(T * p, std::vector<void *> & owner) // ownership moves to the context
-  {
-    auto it = std::find(temps.begin(), temps.end(), static_cast<void *>(p));
-    if (it != temps.end())
-    {
-      temps.erase(it);
-      owner.push_back(p);
-    }
-    return p;
-  }
-  ~Pool()
-  {
-    if (!temps.empty())
-      (void)hipStreamSynchronize(gtx::tls_build_stream); // (on an error path kernels may still be writing to them; freed blocks are handed out again)
-    for (void * p : temps)
-      (void)gtx::dev_free(p);
-  }
-};
+constexpr char const * MSG_PREFIX = "index build: "; // of this file's HIP error messages (the build's pool carries it too)
 
 constexpr uint32_t TB = 256;
 inline uint32_t blocks_for(uint64_t n) { return static_cast<uint32_t>((n + TB - 1) / TB); }
@@ -492,55 +446,31 @@ __global__ void k_window_flags(GraphView g, HintKeys t, uint32_t const * nb, uin
 }
 
 template <class T>
-bool to_device(Pool & pool, T *& d, std::vector<T> const & h, char const * what)
+bool to_device(TempPool & pool, T *& d, std::vector<T> const & h, char const * what)
 {
   d = pool.get<T>(h.size(), what);
   // (asynchronous: `h` has to live until the stream has been waited for -- build_index_device's host vectors are declared in front of its pool)
-  return pool.fine && (h.empty() || ok_hip(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, gtx::tls_build_stream), what));
+  return pool.fine && (h.empty() || pool.ok(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, gtx::tls_build_stream), what));
 }
 
-// rocPRIM primitives with their temporary storage
-template <class K, class V>
-bool sort_pairs(Pool & pool, K const * kin, K * kout, V const * vin, V * vout, uint32_t n, unsigned bits)
-{
-  size_t bytes = 0;
-  if (!ok_hip(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0u, bits), "radix sort (size)"))
-    return false;
-  void * tmp = pool.get<uint8_t>(bytes, "radix sort storage");
-  return pool.fine && ok_hip(rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, 0u, bits, gtx::tls_build_stream), "radix sort");
-}
-
-bool exclusive_sum(Pool & pool, uint32_t const * in, uint32_t * out, uint32_t n)
-{
-  size_t bytes = 0;
-  if (!ok_hip(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<uint32_t>()), "scan (size)"))
-    return false;
-  void * tmp = pool.get<uint8_t>(bytes, "scan storage");
-  return pool.fine && ok_hip(rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), gtx::tls_build_stream), "scan");
-}
-
-bool running_max(Pool & pool, uint32_t const * in, uint32_t * out, uint32_t n)
-{
-  size_t bytes = 0;
-  if (!ok_hip(rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::maximum<uint32_t>()), "max scan (size)"))
-    return false;
-  void * tmp = pool.get<uint8_t>(bytes, "max scan storage");
-  return pool.fine && ok_hip(rocprim::inclusive_scan(tmp, bytes, in, out, n, rocprim::maximum<uint32_t>(), gtx::tls_build_stream), "max scan");
-}
+// the sorts' inputs as pointers to const.  sort_pairs takes its iterator types from the call, and rocPRIM's sort kernels carry them
+// in their names: with the plain pointers the buffers are held by, this file's device code would come out with other kernels.
+template <class T>
+T const * ro(T * p) { return p; }
 
 // begin index and size of every element's group, from its head flags
-bool groups_of(Pool & pool, uint32_t const * head, uint32_t n, uint32_t *& begin, uint32_t *& count)
+bool groups_of(TempPool & pool, uint32_t const * head, uint32_t n, uint32_t *& begin, uint32_t *& count)
 {
   uint32_t * seed = pool.get<uint32_t>(n, "group seeds");
   begin = pool.get<uint32_t>(n, "group begins");
-  count = pool.get<uint32_t>(n, "group counts", true);
+  count = pool.get<uint32_t>(n, "group counts", 0);
   if (!pool.fine)
     return false;
   hipLaunchKernelGGL(k_group_begin_seed, dim3(blocks_for(n)), dim3(TB), 0, gtx::tls_build_stream, head, n, seed);
-  if (!running_max(pool, seed, begin, n))
+  if (!inclusive_scan(pool, seed, begin, n, rocprim::maximum<uint32_t>(), "max scan", "max scan storage"))
     return false;
   hipLaunchKernelGGL(k_group_count, dim3(blocks_for(n)), dim3(TB), 0, gtx::tls_build_stream, begin, n, count);
-  return ok_hip(hipGetLastError(), "group kernels");
+  return pool.ok(hipGetLastError(), "group kernels");
 }
 } // namespace
 
@@ -555,7 +485,7 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   std::vector<HintWindow> win;
   std::vector<uint32_t> site_win;
   hipStream_t const bs = gtx::tls_build_stream;
-  Pool pool;
+  TempPool pool(bs, MSG_PREFIX);
   uint32_t const n_listed = static_cast<uint32_t>(em.size());
   uint64_t const n_run_kmers = runs.empty() ? 0ull : static_cast<uint64_t>(runs.back().dev_before) + runs.back().count;
   if (em.size() + n_run_kmers >= (1ull << 31))
@@ -584,8 +514,8 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
       h_keys[i] = em[i].key;
       h_labels[i] = em[i].label;
     }
-    if (E != 0 && (!ok_hip(hipMemcpyAsync(d_keys_in, h_keys.data(), E * sizeof(uint64_t), hipMemcpyHostToDevice, bs), "emitted keys") ||
-                   !ok_hip(hipMemcpyAsync(d_labels_in, h_labels.data(), E * sizeof(gtx_label), hipMemcpyHostToDevice, bs), "emitted labels")))
+    if (E != 0 && (!pool.ok(hipMemcpyAsync(d_keys_in, h_keys.data(), E * sizeof(uint64_t), hipMemcpyHostToDevice, bs), "emitted keys") ||
+                   !pool.ok(hipMemcpyAsync(d_labels_in, h_labels.data(), E * sizeof(gtx_label), hipMemcpyHostToDevice, bs), "emitted labels")))
       return GTX_ERR_HIP;
   }
   else
@@ -619,17 +549,17 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   {
     // ---- group by key, keeping the emission order inside a key
     hipLaunchKernelGGL(k_iota, dim3(blocks_for(E)), dim3(TB), 0, gtx::tls_build_stream, d_iota, E);
-    if (!sort_pairs(pool, d_keys_in, d_sorted, d_iota, d_perm, E, 64))
+    if (!sort_pairs(pool, ro(d_keys_in), d_sorted, ro(d_iota), d_perm, E, 64, "radix sort", "radix sort storage"))
       return GTX_ERR_HIP;
     uint32_t *d_head = pool.get<uint32_t>(E, "key heads"), *d_kidx = pool.get<uint32_t>(E, "key numbers");
     if (!pool.fine)
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(k_heads, dim3(blocks_for(E)), dim3(TB), 0, gtx::tls_build_stream, d_sorted, E, 0u, ~0ull, d_head);
-    if (!exclusive_sum(pool, d_head, d_kidx, E))
+    if (!exclusive_sum(pool, d_head, d_kidx, E, "scan", "scan storage"))
       return GTX_ERR_HIP;
     uint32_t last_idx = 0, last_head = 0;
-    if (!ok_hip(hipMemcpyAsync(&last_idx, d_kidx + (E - 1), 4, hipMemcpyDeviceToHost, bs), "key count") ||
-        !ok_hip(hipMemcpyAsync(&last_head, d_head + (E - 1), 4, hipMemcpyDeviceToHost, bs), "key count") || !ok_hip(hipStreamSynchronize(bs), "key count"))
+    if (!pool.ok(hipMemcpyAsync(&last_idx, d_kidx + (E - 1), 4, hipMemcpyDeviceToHost, bs), "key count") ||
+        !pool.ok(hipMemcpyAsync(&last_head, d_head + (E - 1), 4, hipMemcpyDeviceToHost, bs), "key count") || !pool.ok(hipStreamSynchronize(bs), "key count"))
       return GTX_ERR_HIP;
     n_keys = last_idx + last_head;
     d_keys = pool.get<uint64_t>(n_keys, "keys");
@@ -642,15 +572,15 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   else
   {
     d_keys = pool.get<uint64_t>(1, "keys");
-    d_key_off = pool.get<uint32_t>(1, "key offsets", true);
+    d_key_off = pool.get<uint32_t>(1, "key offsets", 0);
   }
   // ---- exact table
   uint32_t log2_cap = 2;
   while ((static_cast<uint64_t>(BUCKET_SLOTS) << log2_cap) < 2ull * n_keys + 1)
     ++log2_cap;
-  IndexSlot * d_slots = pool.get<IndexSlot>(static_cast<uint64_t>(BUCKET_SLOTS) << log2_cap, "index slots", true);
+  IndexSlot * d_slots = pool.get<IndexSlot>(static_cast<uint64_t>(BUCKET_SLOTS) << log2_cap, "index slots", 0);
   uint64_t * d_pk = pool.get<uint64_t>(n_keys, "plane keys");
-  uint32_t * d_several = pool.get<uint32_t>(1, "several-label counter", true);
+  uint32_t * d_several = pool.get<uint32_t>(1, "several-label counter", 0);
   if (!pool.fine)
     return GTX_ERR_HIP;
   if (n_keys)
@@ -660,7 +590,7 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   uint32_t hl = 2;
   while ((static_cast<uint64_t>(BUCKET_SLOTS) << hl) < 4ull * n_keys + 1)
     ++hl;
-  IndexSlot * d_hslots = pool.get<IndexSlot>(static_cast<uint64_t>(BUCKET_SLOTS) << hl, "half-key slots", true);
+  IndexSlot * d_hslots = pool.get<IndexSlot>(static_cast<uint64_t>(BUCKET_SLOTS) << hl, "half-key slots", 0);
   HalfEntry * d_hlist = pool.get<HalfEntry>(2ull * n_keys, "half-key buckets");
   uint32_t *d_lbegin = nullptr, *d_lcount = nullptr, *d_lsize = pool.get<uint32_t>(n_keys, "left sizes");
   uint32_t *d_rorder = pool.get<uint32_t>(n_keys, "right order"), *d_rbegin = pool.get<uint32_t>(n_keys, "right begins"),
@@ -684,7 +614,7 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(k_low_keys, dim3(blocks_for(n_keys)), dim3(TB), 0, gtx::tls_build_stream, d_keys, n_keys, d_low);
     hipLaunchKernelGGL(k_iota, dim3(blocks_for(n_keys)), dim3(TB), 0, gtx::tls_build_stream, d_kiota, n_keys);
-    if (!sort_pairs(pool, d_low, d_low_sorted, d_kiota, d_rorder, n_keys, 32))
+    if (!sort_pairs(pool, ro(d_low), d_low_sorted, ro(d_kiota), d_rorder, n_keys, 32, "radix sort", "radix sort storage"))
       return GTX_ERR_HIP;
     hipLaunchKernelGGL(k_heads32, dim3(blocks_for(n_keys)), dim3(TB), 0, gtx::tls_build_stream, d_low_sorted, n_keys, d_rhead);
     if (!groups_of(pool, d_rhead, n_keys, d_rgbegin, d_rcount))
@@ -700,16 +630,16 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   uint32_t const hint_first = R ? c.graph.ref_order[0] - 1 : 0; // order = 1-based contig position
   uint32_t const hint_n = (R == 0 || R - 1 >= HINT_NO_SITE) ? 0u : c.graph.ref_order[R - 1] + c.graph.ref_len[R - 1] - c.graph.ref_order[0];
   bool const hints = hint_n != 0;
-  uint32_t *d_f0 = pool.get<uint32_t>(hints ? (1ull << fl) : 1, "filter 0", true), *d_f1 = pool.get<uint32_t>(hints ? (1ull << fl) : 1, "filter 1", true);
+  uint32_t *d_f0 = pool.get<uint32_t>(hints ? (1ull << fl) : 1, "filter 0", 0), *d_f1 = pool.get<uint32_t>(hints ? (1ull << fl) : 1, "filter 1", 0);
   // (the allele windows continue the per-position tables behind win_base: gtx_flat.hpp)
   if (hints)
     hint_list_windows(c.graph, win, site_win);
   uint32_t const n_win = static_cast<uint32_t>(win.size()), win_base = hint_win_base(hint_n);
   uint64_t const hint_total = hint_total_positions(hint_n, n_win);
-  uint2_t * d_flags = pool.get<uint2_t>(hints ? hint_total : 1, "position flags", true);
+  uint2_t * d_flags = pool.get<uint2_t>(hints ? hint_total : 1, "position flags", 0);
   // (padded: the kernel loads 6 plane groups from any position without a bounds test)
-  uint32_t * d_refp = pool.get<uint32_t>(hints ? 4 * (static_cast<size_t>(hint_total) / 32 + 8) : 32, "reference planes", true);
-  uint2_t * d_tail = pool.get<uint2_t>(hints ? hint_total : 1, "tail sites", !hints || n_win != 0);
+  uint32_t * d_refp = pool.get<uint32_t>(hints ? 4 * (static_cast<size_t>(hint_total) / 32 + 8) : 32, "reference planes", 0);
+  uint2_t * d_tail = pool.get<uint2_t>(hints ? hint_total : 1, "tail sites", !hints || n_win != 0 ? 0 : -1);
   HintWindow * d_win = nullptr;
   uint32_t * d_site_win = nullptr;
   if (n_win && (!to_device(pool, d_win, win, "allele windows") || !to_device(pool, d_site_win, site_win, "windows of the sites")))
@@ -718,8 +648,8 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
     return GTX_ERR_HIP;
   if (hints)
   {
-    uint8_t *d_base = pool.get<uint8_t>(hint_total, "reference bases", n_win != 0), *d_room = pool.get<uint8_t>(hint_total, "node room", n_win != 0),
-            *d_back = pool.get<uint8_t>(hint_total, "node back", n_win != 0);
+    uint8_t *d_base = pool.get<uint8_t>(hint_total, "reference bases", n_win != 0 ? 0 : -1), *d_room = pool.get<uint8_t>(hint_total, "node room", n_win != 0 ? 0 : -1),
+            *d_back = pool.get<uint8_t>(hint_total, "node back", n_win != 0 ? 0 : -1);
     uint32_t * d_nb = pool.get<uint32_t>(n_keys, "neighbour labels");
     uint8_t * d_same = pool.get<uint8_t>(n_keys, "neighbour verdicts");
     if (!pool.fine)
@@ -748,8 +678,8 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
     }
   }
   uint32_t several = 0;
-  if (!ok_hip(hipGetLastError(), "kernels") || !ok_hip(hipMemcpyAsync(&several, d_several, 4, hipMemcpyDeviceToHost, bs), "several-label counter") ||
-      !ok_hip(hipStreamSynchronize(bs), "kernels"))
+  if (!pool.ok(hipGetLastError(), "kernels") || !pool.ok(hipMemcpyAsync(&several, d_several, 4, hipMemcpyDeviceToHost, bs), "several-label counter") ||
+      !pool.ok(hipStreamSynchronize(bs), "kernels"))
     return GTX_ERR_HIP;
   // ---- hand over
   ix.slots = pool.keep(d_slots, c.dev_allocs);
@@ -793,14 +723,14 @@ int download_index(gtx_ctx & c)
   std::lock_guard<std::mutex> lock(c.index_mutex);
   if (c.index_downloaded.load(std::memory_order_acquire))
     return GTX_OK;
-  if (!ok_hip(hipSetDevice(c.device), "hipSetDevice"))
+  if (!hip_ok(hipSetDevice(c.device), "hipSetDevice", MSG_PREFIX))
     return GTX_ERR_HIP;
   c.index.keys.resize(c.n_keys);
   c.index.key_off.resize(static_cast<size_t>(c.n_keys) + 1);
   c.index.labels.resize(c.n_labels);
-  if ((c.n_keys && !ok_hip(hipMemcpy(c.index.keys.data(), c.d_keys, static_cast<size_t>(c.n_keys) * 8, hipMemcpyDeviceToHost), "keys")) ||
-      !ok_hip(hipMemcpy(c.index.key_off.data(), c.d_key_off, (static_cast<size_t>(c.n_keys) + 1) * 4, hipMemcpyDeviceToHost), "key offsets") ||
-      (c.n_labels && !ok_hip(hipMemcpy(c.index.labels.data(), c.d_labels_sorted, static_cast<size_t>(c.n_labels) * sizeof(gtx_label), hipMemcpyDeviceToHost), "labels")))
+  if ((c.n_keys && !hip_ok(hipMemcpy(c.index.keys.data(), c.d_keys, static_cast<size_t>(c.n_keys) * 8, hipMemcpyDeviceToHost), "keys", MSG_PREFIX)) ||
+      !hip_ok(hipMemcpy(c.index.key_off.data(), c.d_key_off, (static_cast<size_t>(c.n_keys) + 1) * 4, hipMemcpyDeviceToHost), "key offsets", MSG_PREFIX) ||
+      (c.n_labels && !hip_ok(hipMemcpy(c.index.labels.data(), c.d_labels_sorted, static_cast<size_t>(c.n_labels) * sizeof(gtx_label), hipMemcpyDeviceToHost), "labels", MSG_PREFIX)))
     return GTX_ERR_HIP;
   if (c.n_keys == 0)
     c.index.key_off.assign(1, 0);
@@ -831,7 +761,7 @@ int download_hint_table(gtx_ctx const & c, int which, void * out, uint64_t cap_b
     return GTX_OK;
   if (cap_bytes < n)
     return GTX_ERR_CAPACITY;
-  if (n != 0 && (!ok_hip(hipSetDevice(c.device), "hipSetDevice") || !ok_hip(hipMemcpy(out, src, n, hipMemcpyDeviceToHost), "hint table")))
+  if (n != 0 && (!hip_ok(hipSetDevice(c.device), "hipSetDevice", MSG_PREFIX) || !hip_ok(hipMemcpy(out, src, n, hipMemcpyDeviceToHost), "hint table", MSG_PREFIX)))
     return GTX_ERR_HIP;
   return GTX_OK;
 }

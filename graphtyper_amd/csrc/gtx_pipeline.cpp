@@ -140,7 +140,7 @@ struct ThreadLoop
     if (!idle && hipStreamCreateWithFlags(&made, hipStreamNonBlocking) == hipSuccess)
     {
       std::lock_guard<std::mutex> lock(c->pipeline_mutex);
-      c->pipeline_streams_all.push_back(made);
+      c->pipeline_streams_all.emplace_back(made);
     }
     st.reset(idle ? idle : made);
   }
@@ -322,11 +322,8 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
     g_last_error = "gtx_pipeline_run: bad argument";
     return GTX_ERR_ARG;
   }
-  if (c->device < 0)
-  {
-    g_last_error = "context was created without a device (libgtx has no CPU path)";
-    return GTX_ERR_NO_DEVICE;
-  }
+  if (int const rc = gtx::device_ready(c->device, "context"))
+    return rc;
   auto const t_all = std::chrono::steady_clock::now();
   n_threads = std::min(n_threads, n_paths);
   std::vector<Worker> team(n_threads);

@@ -132,28 +132,23 @@ static int scores_alloc_impl(gtx_ctx * c, uint32_t n_samples, uint32_t conn_cap,
       g_last_error = "gtx_scores_alloc: bad argument";
       return GTX_ERR_ARG;
     }
-    if (c->device < 0)
-    {
-      g_last_error = "context was created without a device (libgtx has no CPU path)";
-      return GTX_ERR_NO_DEVICE;
-    }
+    if (int const rc = gtx::device_ready(c->device, "context"))
+      return rc;
     Sections const s = sections_of(*c, n_samples);
     // [u64 stats][u32: log_score, gt_cov, hap_u32, stat_u32, conn_near] = what is summed over ranks; then the
     // rank-local connection log (count words first)
     uint64_t const reduced = s.stat_u64 * 8 + s.u32_total() * 4;
     uint64_t const bytes = reduced + 2 * 4 + static_cast<uint64_t>(conn_cap) * 6 * 4;
-    void * p = nullptr;
-    if (hipSetDevice(c->device) != hipSuccess || gtx::dev_malloc(&p, bytes ? bytes : 8) != hipSuccess ||
-        (on_stream ? hipMemsetAsync(p, 0, bytes, static_cast<hipStream_t>(stream)) : gtx::dev_zero(p, bytes)) != hipSuccess)
+    gtx::DevPtr<> block; // (the caller's from the release below on: gtx_scores_free gives it back)
+    if (!gtx::alloc(block, bytes ? bytes : 8) ||
+        (on_stream ? hipMemsetAsync(block.get(), 0, bytes, static_cast<hipStream_t>(stream)) : gtx::dev_zero(block.get(), bytes)) != hipSuccess)
     {
-      if (p)
-        (void)gtx::dev_free(p);
       g_last_error = "gtx_scores_alloc: hipMalloc of " + std::to_string(bytes) + " bytes failed";
       return GTX_ERR_HIP;
     }
     std::memset(out, 0, sizeof(*out));
     out->n_samples = n_samples;
-    out->d_stat_u64 = static_cast<uint64_t *>(p);
+    out->d_stat_u64 = static_cast<uint64_t *>(block.release());
     uint32_t * u32 = reinterpret_cast<uint32_t *>(out->d_stat_u64 + s.stat_u64);
     out->d_log_score = u32;
     out->d_gt_cov = out->d_log_score + s.log_score;
@@ -271,11 +266,8 @@ extern "C"
       g_last_error = "gtx_scores_reduce: bad argument";
       return GTX_ERR_ARG;
     }
-    if (c->device < 0)
-    {
-      g_last_error = "context was created without a device (libgtx has no CPU path)";
-      return GTX_ERR_NO_DEVICE;
-    }
+    if (int const rc = gtx::device_ready(c->device, "context"))
+      return rc;
     if (!rccl_ready())
       return GTX_ERR_UNSUPPORTED;
     Rccl & r = rccl();
