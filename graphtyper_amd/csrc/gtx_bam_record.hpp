@@ -1,0 +1,108 @@
+// gtx_bam_record.hpp -- the BAM format as both of its readers see it (gtx_bam.cpp: gtx_reads_*; gtx_shrink.cpp: the pre-filter):
+// the header, the next record's block, the fixed 32 bytes of a record with the offsets of what follows them, the reference span
+// of a CIGAR.  (SAM spec 4.2)
+#pragma once
+#include "gtx_bgzf.hpp"
+
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace gtx
+{
+struct BamHeader
+{
+  std::string text; // as in the file: l_text bytes
+  std::vector<std::pair<std::string, int32_t>> refs; // name, length
+};
+
+// BAM_NOT_BAM: no magic, or no text length behind it; BAM_TRUNCATED: the file ends inside the text or the reference list (or a
+// name's length is none: not positive, or beyond 1 MiB -- no contig is called that, and the field must not size an allocation)
+enum BamHeaderRead { BAM_HEADER_OK, BAM_NOT_BAM, BAM_TRUNCATED };
+inline BamHeaderRead read_bam_header(Bgzf & fp, BamHeader & h)
+{
+  auto rd = [&](void * d, size_t n) { return fp.read(d, n) == static_cast<long>(n); };
+  char magic[4];
+  int32_t l_text = 0, n_ref = 0;
+  if (!rd(magic, 4) || std::memcmp(magic, "BAM\1", 4) != 0 || !rd(&l_text, 4) || l_text < 0)
+    return BAM_NOT_BAM;
+  h.text.assign(static_cast<size_t>(l_text), '\0');
+  if ((l_text && !rd(&h.text[0], static_cast<size_t>(l_text))) || !rd(&n_ref, 4) || n_ref < 0)
+    return BAM_TRUNCATED;
+  h.refs.clear();
+  for (int32_t i = 0; i < n_ref; ++i)
+  {
+    int32_t l_name = 0, l_ref = 0;
+    std::string name;
+    if (!rd(&l_name, 4) || l_name <= 0 || l_name > (1 << 20) || (name.resize(static_cast<size_t>(l_name)), !rd(&name[0], static_cast<size_t>(l_name))) ||
+        !rd(&l_ref, 4))
+      return BAM_TRUNCATED;
+    name.resize(std::strlen(name.c_str()));
+    h.refs.emplace_back(name, l_ref);
+  }
+  return BAM_HEADER_OK;
+}
+
+// the next record's block (what follows its block_size) into buf
+enum BamBlockRead { BAM_BLOCK_OK, BAM_BLOCK_END, BAM_BLOCK_DAMAGED };
+inline BamBlockRead read_bam_block(Bgzf & fp, std::vector<uint8_t> & buf)
+{
+  int32_t block = 0;
+  long const got = fp.read(&block, 4);
+  if (got == 0)
+    return BAM_BLOCK_END;
+  if (got != 4 || block < 32)
+    return BAM_BLOCK_DAMAGED;
+  buf.resize(static_cast<size_t>(block));
+  return fp.read(buf.data(), buf.size()) == static_cast<long>(buf.size()) ? BAM_BLOCK_OK : BAM_BLOCK_DAMAGED;
+}
+
+struct BamCore
+{
+  int32_t tid, pos, l_seq, mtid, mpos, tlen;
+  uint8_t l_read_name, mapq;
+  uint16_t n_cigar, flag;
+  size_t o_cigar, o_seq, o_qual, o_aux; // offsets in the block; the name is at 32
+};
+
+// false: the block is shorter than its own counts say (or l_seq is negative)
+inline bool parse_bam_core(std::vector<uint8_t> const & buf, BamCore & c)
+{
+  uint8_t const * p = buf.data();
+  std::memcpy(&c.tid, p, 4);
+  std::memcpy(&c.pos, p + 4, 4);
+  c.l_read_name = p[8];
+  c.mapq = p[9];
+  std::memcpy(&c.n_cigar, p + 12, 2);
+  std::memcpy(&c.flag, p + 14, 2);
+  std::memcpy(&c.l_seq, p + 16, 4);
+  std::memcpy(&c.mtid, p + 20, 4);
+  std::memcpy(&c.mpos, p + 24, 4);
+  std::memcpy(&c.tlen, p + 28, 4);
+  if (c.l_seq < 0)
+    return false;
+  c.o_cigar = 32 + static_cast<size_t>(c.l_read_name);
+  c.o_seq = c.o_cigar + 4ull * c.n_cigar;
+  c.o_qual = c.o_seq + (static_cast<size_t>(c.l_seq) + 1) / 2;
+  c.o_aux = c.o_qual + static_cast<size_t>(c.l_seq);
+  return c.o_aux <= buf.size();
+}
+
+// reference positions an alignment covers (bam_endpos: M, D, N, =, X consume the reference); cigar: n words of len << 4 | op,
+// at any alignment.  What a span of zero or an unmapped read counts as is the caller's rule.
+inline int64_t ref_span(void const * cigar, size_t n)
+{
+  int64_t span = 0;
+  for (size_t c = 0; c < n; ++c)
+  {
+    uint32_t w;
+    std::memcpy(&w, static_cast<uint8_t const *>(cigar) + 4 * c, 4);
+    uint32_t const op = w & 15u;
+    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8)
+      span += w >> 4;
+  }
+  return span;
+}
+} // namespace gtx

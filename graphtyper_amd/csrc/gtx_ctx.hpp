@@ -196,6 +196,8 @@ inline bool max_read_len_ok(gtx_params const & p)
 inline uint32_t max_read_len_of(gtx_params const & p) { return p.max_read_len ? p.max_read_len : GTX_MAX_READ; }
 // the length of the read the last gtx_reads_next refused with GTX_ERR_ARG because its seq_stride was too small, else 0 (gtx_bam.cpp)
 uint32_t reads_refused_len(gtx_reads const * r);
+// the SV table gtx_graph_from_files (gtx_files.cpp) leaves with the graph it built (gtx_graph.cpp)
+void graph_set_sv_table(gtx_graph * g, std::string table);
 // gtx_scores_alloc with the block zeroed on `stream` (no wait: for a caller whose first use of the block is on that stream)
 int scores_alloc_on(gtx_ctx * c, uint32_t n_samples, uint32_t conn_cap, gtx_score_buffers * out, uint64_t * reduced_bytes, void * stream);
 // zeroes the header word of the 2 * n_reads record slots on `stream` (slots recycled from one region to the next)

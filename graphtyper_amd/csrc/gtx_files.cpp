@@ -28,18 +28,7 @@
 
 #include "../../include/gtx.h"
 #include "gtx_ctx.hpp"
-
-namespace gtx
-{
-// gtx_tabix.cpp
-bool tabix_start(std::string const & vcf_path, std::string const & chrom, int64_t begin, int64_t end, bool & any, uint64_t & voffset);
-gzFile gz_open_at(std::string const & path, uint64_t voffset);
-} // namespace gtx
-
-namespace gtx
-{
-void graph_set_sv_table(gtx_graph * g, std::string table); // gtx_graph.cpp
-}
+#include "gtx_tabix.hpp"
 
 namespace
 {

@@ -1,6 +1,7 @@
 // gtx_inflate_dev.hip -- DEFLATE on the device: gtx_inflate_kernel (one wavefront per BGZF member, gtx_inflate_dev.hpp) and
-// the gtx_inflate_* entry points around it.  The BAM readers' device team (gtx_bam.cpp) goes through inflate_host_batch.
+// the gtx_inflate_* entry points around it.  The BAM readers' device team (gtx_bgzf.cpp) goes through inflate_host_batch.
 #include "../../include/gtx.h"
+#include "gtx_bgzf.hpp"
 #include "gtx_devmem.hpp"
 #include "gtx_host_loops.hpp"
 #include "gtx_inflate_dev.hpp"
@@ -187,40 +188,23 @@ extern "C" int gtx_inflate_bgzf(gtx_inflate * h, const void * in_v, uint64_t in_
   uint64_t at = 0, total = 0;
   while (at < in_len)
   {
-    // gzip header with the BC extra field (SAM spec 4.1), as the readers parse it (gtx_bam.cpp)
-    auto bad = [&](char const * what) {
-      gtx::g_last_error = "gtx_inflate_bgzf: member " + std::to_string(members.size()) + " at byte " + std::to_string(at) + ": " + what;
-      return GTX_ERR_IO;
-    };
-    if (in_len - at < 18 || in[at] != 31 || in[at + 1] != 139 || in[at + 2] != 8 || !(in[at + 3] & 4))
-      return bad("not a BGZF member");
-    uint64_t const xlen = in[at + 10] | (in[at + 11] << 8);
-    if (in_len - at < 12 + xlen)
-      return bad("truncated");
-    long bsize = -1;
-    for (uint64_t i = 0; i + 4 <= xlen;)
+    gtx::BgzfMember head;
+    char const * why = gtx::parse_bgzf_member(in + at, in_len - at, head);
+    if (!why && !head.whole)
+      why = "truncated";
+    if (why)
     {
-      uint8_t const * x = in + at + 12 + i;
-      uint64_t const slen = x[2] | (x[3] << 8);
-      if (x[0] == 'B' && x[1] == 'C' && slen == 2 && i + 6 <= xlen)
-        bsize = x[4] | (x[5] << 8);
-      i += 4 + slen;
+      gtx::g_last_error = "gtx_inflate_bgzf: member " + std::to_string(members.size()) + " at byte " + std::to_string(at) + ": " + why;
+      return GTX_ERR_IO;
     }
-    long const clen = bsize + 1 - 12 - static_cast<long>(xlen) - 8;
-    if (bsize < 0 || clen < 0)
-      return bad("no BC field");
-    if (in_len - at < static_cast<uint64_t>(bsize) + 1)
-      return bad("truncated");
     gtx_inflate_member m{};
-    m.in_off = at + 12 + xlen;
-    m.in_len = static_cast<uint32_t>(clen);
-    std::memcpy(&m.crc32, in + m.in_off + clen, 4);
-    std::memcpy(&m.out_len, in + m.in_off + clen + 4, 4);
-    if (m.out_len > 65536)
-      return bad("ISIZE beyond 65536");
+    m.in_off = at + head.hlen;
+    m.in_len = static_cast<uint32_t>(head.clen);
+    m.crc32 = head.crc32;
+    m.out_len = head.isize;
     m.out_off = total;
     total += m.out_len;
-    at += static_cast<uint64_t>(bsize) + 1;
+    at += head.bsize + 1ull;
     if (m.out_len) // (the end-of-file marker, or an empty member)
       members.push_back(m);
   }

@@ -1,5 +1,5 @@
 // gtx_inflate_host.hpp -- the device inflater as the library's own host code uses it (gtx_inflate_dev.hip; the BAM readers' device
-// team in gtx_bam.cpp).
+// team in gtx_bgzf.cpp).
 #pragma once
 #include "../../include/gtx.h"
 
@@ -12,7 +12,7 @@ namespace gtx
 int inflate_host_batch(gtx_inflate * h, uint8_t const * in, uint64_t in_size, gtx_inflate_member const * members, uint32_t n, uint8_t * out, uint64_t out_size,
                        uint32_t * status, bool check_crc);
 
-// The BAM readers (gtx_bam.cpp) are also built without the HIP runtime (the sanitizer drivers of tests/sanitize link the parsers
+// The BAM readers (gtx_bgzf.cpp) are also built without the HIP runtime (the sanitizer drivers of tests/sanitize link the parsers
 // alone), so they reach the device inflater through this table: gtx_inflate_dev.hip sets it when the library is loaded, and
 // where it is not linked in the readers answer GTX_ERR_NO_DEVICE.
 struct InflateDeviceOps
@@ -23,5 +23,5 @@ struct InflateDeviceOps
   void (*pinned_free)(void *);
   int (*batch)(gtx_inflate *, uint8_t const *, uint64_t, gtx_inflate_member const *, uint32_t, uint8_t *, uint64_t, uint32_t *, bool); // inflate_host_batch
 };
-extern InflateDeviceOps const * inflate_device_ops; // (gtx_bam.cpp)
+extern InflateDeviceOps const * inflate_device_ops; // (gtx_bgzf.cpp)
 } // namespace gtx

@@ -1,6 +1,7 @@
-// gtx_shrink.inl -- the read pre-filter in front of the path (part of gtx_bam.cpp: shares its BGZF reader and index look-ups).
+// gtx_shrink.cpp -- the read pre-filter in front of the path: gtx_bam_shrink, gtx_bam_shrink_multi (the BGZF reader and writer:
+// gtx_bgzf.hpp; the BAM header and records: gtx_bam_record.hpp; the index look-up: gtx_hts_index.hpp).
 //
-// gtx_bam_shrink replaces gyper::bamshrink / bamshrink_multi (/root/reference/src/utilities/bamshrink.cpp:1248-1371), whose
+// gtx_bam_shrink replaces gyper::bamshrink / bamshrink_multi (src/utilities/bamshrink.cpp:1248-1371), whose
 // work is qualityFilterSlice2 (:667-1045): of the records around an interval keep the pairs and single reads that pass the
 // mapping-quality / clipping / matching-bases / base-quality filters (:716-776), cut adapters off pairs whose fragment is
 // shorter than a read (:606-665), drop reads by their AS / XS / WS tags (:102-308), cut Ns off the ends (:523-584), cap the
@@ -12,6 +13,23 @@
 // waiting for their mate live in a hash map with the reference's name hash (:321-336; its iteration order decides which
 // stale mate is counted first), reads waiting to be written in a multimap keyed by begin position (equal keys stay in insertion
 // order, like the reference's multiset :312-316).
+#include "gtx_bam_record.hpp"
+#include "gtx_ctx.hpp"
+#include "gtx_hts_index.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <map>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace
+{
+using gtx::Bgzf;
 namespace shrink
 {
 struct Limits // bamshrink::Options (include/graphtyper/utilities/bamshrink.hpp:7-27)
@@ -566,10 +584,7 @@ private:
       ++st_.dropped_by_depth;
       return;
     }
-    long span = 0;
-    for (size_t c = 0; c < r.cigar.size(); ++c)
-      if (r.op(c) == OP_M || r.op(c) == OP_D || r.op(c) == OP_N || r.op(c) == OP_EQ || r.op(c) == OP_X)
-        span += r.cnt(c);
+    int64_t const span = gtx::ref_span(r.cigar.data(), r.cigar.size());
     uint16_t const bin = r.pos < 0 ? bam_bin(-1, 0) : bam_bin(r.pos, static_cast<int64_t>(r.pos) + (r.is(F_UNMAPPED) || span == 0 ? 1 : span));
     uint32_t const l_seq = r.hi - r.lo;
     uint8_t const l_name = static_cast<uint8_t>(r.name.size() + 1);
@@ -620,48 +635,36 @@ private:
   std::multimap<int32_t, Read> ready_;                      // read_set
 };
 
-// the next record of `fp` as a Read; 0 = end of the file, -1 = damaged
-inline int next_read(Bgzf & fp, std::vector<uint8_t> & buf, Read & r)
+// the next record of `fp` as a Read
+inline gtx::BamBlockRead next_read(Bgzf & fp, std::vector<uint8_t> & buf, Read & r)
 {
-  int32_t block = 0;
-  long const got = fp.read(&block, 4);
-  if (got == 0)
-    return 0;
-  if (got != 4 || block < 32)
-    return -1;
-  buf.resize(static_cast<size_t>(block));
-  if (fp.read(buf.data(), buf.size()) != static_cast<long>(buf.size()))
-    return -1;
+  gtx::BamBlockRead const got = gtx::read_bam_block(fp, buf);
+  if (got != gtx::BAM_BLOCK_OK)
+    return got;
+  gtx::BamCore c;
+  if (!gtx::parse_bam_core(buf, c))
+    return gtx::BAM_BLOCK_DAMAGED;
   uint8_t const * p = buf.data();
-  int32_t l_seq;
-  uint16_t n_cigar;
-  std::memcpy(&r.tid, p, 4);
-  std::memcpy(&r.pos, p + 4, 4);
-  uint8_t const l_name = p[8];
-  r.mapq = p[9];
-  std::memcpy(&n_cigar, p + 12, 2);
-  std::memcpy(&r.flag, p + 14, 2);
-  std::memcpy(&l_seq, p + 16, 4);
-  std::memcpy(&r.mtid, p + 20, 4);
-  std::memcpy(&r.mpos, p + 24, 4);
-  std::memcpy(&r.tlen, p + 28, 4);
-  size_t const o_cigar = 32 + static_cast<size_t>(l_name), o_seq = o_cigar + 4ull * n_cigar, o_qual = o_seq + (static_cast<size_t>(std::max(l_seq, 0)) + 1) / 2,
-               o_aux = o_qual + static_cast<size_t>(std::max(l_seq, 0));
-  if (l_seq < 0 || o_aux > buf.size())
-    return -1;
-  r.name.assign(reinterpret_cast<char const *>(p + 32), l_name ? l_name - 1u : 0u);
+  r.tid = c.tid;
+  r.pos = c.pos;
+  r.mapq = c.mapq;
+  r.flag = c.flag;
+  r.mtid = c.mtid;
+  r.mpos = c.mpos;
+  r.tlen = c.tlen;
+  r.name.assign(reinterpret_cast<char const *>(p + 32), c.l_read_name ? c.l_read_name - 1u : 0u);
   r.name.resize(std::strlen(r.name.c_str()));
-  r.cigar.resize(n_cigar);
-  if (n_cigar)
-    std::memcpy(r.cigar.data(), p + o_cigar, 4ull * n_cigar);
-  r.bases.resize(static_cast<size_t>(l_seq));
-  for (int32_t i = 0; i < l_seq; ++i)
-    r.bases[i] = (p[o_seq + i / 2] >> ((i & 1) ? 0 : 4)) & 15u;
-  r.quals.assign(p + o_qual, p + o_aux);
+  r.cigar.resize(c.n_cigar);
+  if (c.n_cigar)
+    std::memcpy(r.cigar.data(), p + c.o_cigar, 4ull * c.n_cigar);
+  r.bases.resize(static_cast<size_t>(c.l_seq));
+  for (int32_t i = 0; i < c.l_seq; ++i)
+    r.bases[i] = (p[c.o_seq + i / 2] >> ((i & 1) ? 0 : 4)) & 15u;
+  r.quals.assign(p + c.o_qual, p + c.o_aux);
   r.lo = 0;
-  r.hi = static_cast<uint32_t>(l_seq);
-  r.aux.assign(p + o_aux, p + buf.size());
-  return 1;
+  r.hi = static_cast<uint32_t>(c.l_seq);
+  r.aux.assign(p + c.o_aux, p + buf.size());
+  return gtx::BAM_BLOCK_OK;
 }
 
 // the header text of a one-interval run (:1304-1335): the @HD and @RG lines and the interval's own @SQ line
@@ -680,43 +683,16 @@ inline std::string one_contig_text(std::string const & text, std::string const &
   return out;
 }
 
-struct Header
-{
-  std::string text;
-  std::vector<std::pair<std::string, int32_t>> refs;
-};
+using Header = gtx::BamHeader;
 
+// the header with its text cut at the first NUL; false: not a BAM file, or one whose header ends early
 inline bool read_header(Bgzf & fp, Header & h, std::string & err, std::string const & path)
 {
-  char magic[4];
-  int32_t l_text = 0, n_ref = 0;
-  auto rd = [&](void * d, size_t n) { return fp.read(d, n) == static_cast<long>(n); };
-  if (!rd(magic, 4) || std::memcmp(magic, "BAM\1", 4) != 0 || !rd(&l_text, 4) || l_text < 0)
-  {
-    err = path + " is not a BAM file (CRAM is not read)";
-    return false;
-  }
-  h.text.assign(static_cast<size_t>(l_text), '\0');
-  if ((l_text && !rd(&h.text[0], static_cast<size_t>(l_text))) || !rd(&n_ref, 4) || n_ref < 0)
-  {
-    err = path + ": truncated header";
-    return false;
-  }
+  gtx::BamHeaderRead const got = gtx::read_bam_header(fp, h);
+  if (got != gtx::BAM_HEADER_OK)
+    err = path + (got == gtx::BAM_NOT_BAM ? " is not a BAM file (CRAM is not read)" : ": truncated header");
   h.text.resize(std::strlen(h.text.c_str()));
-  h.refs.clear();
-  for (int32_t i = 0; i < n_ref; ++i)
-  {
-    int32_t l_name = 0, l_ref = 0;
-    std::string name;
-    if (!rd(&l_name, 4) || l_name <= 0 || l_name > (1 << 20) || (name.resize(static_cast<size_t>(l_name)), !rd(&name[0], static_cast<size_t>(l_name))) || !rd(&l_ref, 4))
-    {
-      err = path + ": truncated header";
-      return false;
-    }
-    name.resize(std::strlen(name.c_str()));
-    h.refs.emplace_back(name, l_ref);
-  }
-  return true;
+  return got == gtx::BAM_HEADER_OK;
 }
 
 inline void append_header(Header const & h, std::vector<uint8_t> & out)
@@ -736,3 +712,263 @@ inline void append_header(Header const & h, std::vector<uint8_t> & out)
   }
 }
 } // namespace shrink
+} // namespace
+
+extern "C" void gtx_shrink_params_default(gtx_shrink_params * p)
+{
+  if (!p)
+    return;
+  *p = gtx_shrink_params{};
+  p->max_frag_len = 1000;        // options.hpp:63-69
+  p->min_num_matching = 55;
+  p->filter_mapq0 = 1;
+  p->no_filter_on_coverage = 0;  // options.hpp:50
+  p->min_read_len = 75;
+  p->min_read_len_low_mapq = 94;
+  p->min_unpaired_read_len = 94;
+  p->sam_flag_filter = 3840;     // options.hpp:90
+  p->as_filter_threshold = 40;
+  p->avg_cov_by_readlen = 0.0;   // unknown
+  p->change_read_names = 1;      // (release builds of the reference, bamshrink.cpp:24-28)
+  p->compress_level = 1;         // "wb1" (bamshrink.cpp:1263)
+}
+
+extern "C" int gtx_bam_shrink(const char * bam_in, const char * const * chroms, const int32_t * begins, const int32_t * ends, uint32_t n_intervals,
+                              const gtx_shrink_params * params, const char * bam_out, gtx_shrink_stats * stats)
+{
+  gtx_shrink_stats st{};
+  if (stats)
+    *stats = st;
+  if (!bam_in || !chroms || !begins || !ends || n_intervals == 0 || !bam_out)
+  {
+    gtx::g_last_error = "gtx_bam_shrink: bad argument (at least one interval is needed, bamshrink.cpp:1296-1300)";
+    return GTX_ERR_ARG;
+  }
+  gtx_shrink_params par;
+  if (params)
+    par = *params;
+  else
+    gtx_shrink_params_default(&par);
+  shrink::Limits lim;
+  lim.max_frag = par.max_frag_len;
+  lim.min_matching = par.min_num_matching;
+  lim.min_len = par.min_read_len;
+  lim.min_len_low_mapq = par.min_read_len_low_mapq;
+  lim.min_len_unpaired = par.min_unpaired_read_len;
+  lim.as_threshold = par.as_filter_threshold;
+  lim.drop_mapq0 = par.filter_mapq0 != 0;
+  lim.rename = par.change_read_names != 0;
+  lim.flag_filter = static_cast<uint32_t>(par.sam_flag_filter);
+  // bamshrink.cpp:1268-1271 and :710-711: without a coverage the default one caps the bins and nothing counts as "super high"
+  double const cov = par.avg_cov_by_readlen > 0.0 ? par.avg_cov_by_readlen : 0.30000001;
+  lim.deep_factor = par.avg_cov_by_readlen > 0.0 ? 2 : 1000;
+  lim.bin_cap = par.no_filter_on_coverage ? (std::numeric_limits<int>::max() / 10) : static_cast<long>(cov * 50.0 * 2.5);
+
+  std::string const path(bam_in);
+  shrink::Header head;
+  std::string err;
+  {
+    Bgzf fp;
+    if (!fp.open(path))
+    {
+      gtx::g_last_error = "could not open " + path;
+      return GTX_ERR_IO;
+    }
+    if (!shrink::read_header(fp, head, err, path))
+    {
+      gtx::g_last_error = err;
+      return GTX_ERR_UNSUPPORTED;
+    }
+  }
+  std::vector<int32_t> tids(n_intervals);
+  for (uint32_t i = 0; i < n_intervals; ++i)
+  {
+    std::string const chrom = chroms[i] ? chroms[i] : "";
+    auto it = std::find_if(head.refs.begin(), head.refs.end(), [&](auto const & r) { return r.first == chrom; });
+    if (it == head.refs.end() || begins[i] < 0 || ends[i] < begins[i])
+    {
+      gtx::g_last_error = path + ": no contig " + chrom + " (or an interval that ends in front of its begin)";
+      return GTX_ERR_ARG;
+    }
+    tids[i] = static_cast<int32_t>(it - head.refs.begin());
+  }
+  bool const one_contig = n_intervals == 1;
+  shrink::Header out_head = head;
+  if (one_contig) // only this contig stays in the header (bamshrink.cpp:1304-1335)
+  {
+    out_head.text = shrink::one_contig_text(head.text, head.refs[static_cast<size_t>(tids[0])].first);
+    out_head.refs.assign(1, head.refs[static_cast<size_t>(tids[0])]);
+  }
+  std::FILE * out = std::fopen(bam_out, "wb");
+  if (!out)
+  {
+    gtx::g_last_error = std::string("could not create ") + bam_out;
+    return GTX_ERR_IO;
+  }
+  std::vector<uint8_t> sink, packed;
+  auto flush = [&](bool last) -> bool
+  {
+    // whole 0xff00-byte members while more is coming; the rest stays in the sink
+    size_t const take = last ? sink.size() : sink.size() / 0xff00u * 0xff00u;
+    if (take == 0 && !last)
+      return true;
+    packed.resize(take + take / 8 + (take / 0xff00u + 2) * 64);
+    uint64_t n = 0;
+    if (gtx_bgzf_compress(sink.data(), take, par.compress_level, last ? 1 : 0, packed.data(), packed.size(), &n) != GTX_OK)
+      return false;
+    sink.erase(sink.begin(), sink.begin() + static_cast<long>(take));
+    return std::fwrite(packed.data(), 1, n, out) == n;
+  };
+  shrink::append_header(out_head, sink);
+  long read_num = 0;
+  int status = GTX_OK;
+  std::vector<uint8_t> buf;
+  for (uint32_t i = 0; i < n_intervals && status == GTX_OK; ++i)
+  {
+    // the records the reference asks its index for (bamshrink.cpp:681-699): those that overlap [first - pad, last + pad)
+    int64_t const pad = lim.max_frag - 100;
+    int64_t const from = std::max<int64_t>(static_cast<int64_t>(begins[i]) - pad, 0), to = static_cast<int64_t>(ends[i]) + pad;
+    Bgzf fp;
+    shrink::Header again;
+    if (!fp.open(path) || !shrink::read_header(fp, again, err, path))
+    {
+      gtx::g_last_error = "could not read " + path;
+      status = GTX_ERR_IO;
+      break;
+    }
+    bool any = true;
+    uint64_t voffset = 0;
+    if (gtx::bam_index_start(path, tids[i], from, to, any, voffset))
+    {
+      if (!any)
+        continue;
+      if (!fp.seek(voffset))
+      {
+        gtx::g_last_error = path + ": the index points outside the file";
+        status = GTX_ERR_IO;
+        break;
+      }
+    }
+    shrink::Slice slice(lim, begins[i], ends[i], one_contig, read_num, sink, st);
+    for (;;)
+    {
+      shrink::Read r;
+      gtx::BamBlockRead const got = shrink::next_read(fp, buf, r);
+      if (got == gtx::BAM_BLOCK_END)
+        break;
+      if (got == gtx::BAM_BLOCK_DAMAGED)
+      {
+        gtx::g_last_error = path + ": damaged BAM record";
+        status = GTX_ERR_IO;
+        break;
+      }
+      if (r.tid != tids[i])
+      {
+        if (r.tid > tids[i] || r.tid < 0)
+          break; // sorted file: behind the contig
+        continue;
+      }
+      if (r.pos >= to)
+        break;
+      int64_t const span = gtx::ref_span(r.cigar.data(), r.cigar.size());
+      if (static_cast<int64_t>(r.pos) + (span > 0 && !r.is(shrink::F_UNMAPPED) ? span : 1) <= from)
+        continue;
+      ++st.records_read;
+      slice.take(std::move(r));
+      if (sink.size() > (8u << 20) && !flush(false))
+      {
+        gtx::g_last_error = std::string("could not write ") + bam_out;
+        status = GTX_ERR_IO;
+        break;
+      }
+    }
+    if (status == GTX_OK)
+      slice.finish();
+  }
+  if (status == GTX_OK && !flush(true))
+  {
+    gtx::g_last_error = std::string("could not write ") + bam_out;
+    status = GTX_ERR_IO;
+  }
+  if (std::fclose(out) != 0 && status == GTX_OK)
+  {
+    gtx::g_last_error = std::string("could not write ") + bam_out;
+    status = GTX_ERR_IO;
+  }
+  if (status != GTX_OK)
+    std::remove(bam_out);
+  else if (stats)
+    *stats = st;
+  return status;
+}
+
+// bamshrink_multi (bamshrink.cpp:1352-1371) with readIntervals (:1047-1130): the intervals of a file -- lines of "contig first
+// last", 1-based, sorted -- where a neighbour that begins within 2 * max_frag_len of the one before is one interval with it
+// (otherwise the output could not stay sorted); then the filter over all of them into one file with the whole header.
+extern "C" int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const gtx_shrink_params * params, const char * bam_out,
+                                    gtx_shrink_stats * stats)
+{
+  if (!bam_in || !interval_file || !bam_out)
+  {
+    gtx::g_last_error = "gtx_bam_shrink_multi: bad argument";
+    return GTX_ERR_ARG;
+  }
+  gtx_shrink_params par;
+  if (params)
+    par = *params;
+  else
+    gtx_shrink_params_default(&par);
+  std::FILE * fp = std::fopen(interval_file, "r");
+  if (!fp)
+  {
+    gtx::g_last_error = std::string("Unable to locate interval file at: ") + interval_file;
+    return GTX_ERR_IO;
+  }
+  std::vector<std::string> names;
+  std::vector<int32_t> firsts, lasts;
+  char contig[1024];
+  long a = 0, b = 0;
+  int status = GTX_OK;
+  size_t n_lines = 0;
+  while (std::fscanf(fp, "%1023s %ld %ld", contig, &a, &b) == 3)
+  {
+    // (:1076-1086: a line other than the first counts only when something follows its last number -- the stream is asked for its
+    //  end before the interval is used, so the last line of a file that does not end in a newline is left out)
+    int const behind = std::fgetc(fp);
+    if (behind == EOF && n_lines > 0)
+      break;
+    if (behind != EOF)
+      std::ungetc(behind, fp);
+    ++n_lines;
+    int32_t const first = static_cast<int32_t>(a - 1), last = static_cast<int32_t>(b - 1);
+    if (!names.empty() && names.back() == contig)
+    {
+      if (first < firsts.back())
+      {
+        gtx::g_last_error = "The input intervals are not sorted.";
+        status = GTX_ERR_ARG;
+        break;
+      }
+      if (static_cast<long>(first) - lasts.back() <= 2l * par.max_frag_len)
+      {
+        lasts.back() = last; // (the reference takes the later interval's end, also when it is the smaller one)
+        continue;
+      }
+    }
+    names.emplace_back(contig);
+    firsts.push_back(first);
+    lasts.push_back(last);
+  }
+  std::fclose(fp);
+  if (status != GTX_OK)
+    return status;
+  if (names.empty())
+  {
+    gtx::g_last_error = std::string("The interval file \"") + interval_file + "\" contained no intervals!";
+    return GTX_ERR_ARG;
+  }
+  std::vector<char const *> chroms;
+  for (auto const & n : names)
+    chroms.push_back(n.c_str());
+  return gtx_bam_shrink(bam_in, chroms.data(), firsts.data(), lasts.data(), static_cast<uint32_t>(names.size()), &par, bam_out, stats);
+}

@@ -9,10 +9,11 @@
 // column 2, '#' comment lines, end from the REF allele's length or INFO/END) -- so any reader of the formats can use it;
 // it does not reproduce htslib's optional merging of sparse bins into their parents (byte equality with htslib's file is
 // not claimed and could not be checked here).
-#include "gtx_ctx.hpp"
-#include "gtx_inflate.hpp"
+#include "gtx_tabix.hpp"
 
-#include <zlib.h>
+#include "gtx_bgzf.hpp"
+#include "gtx_ctx.hpp"
+#include "gtx_hts_index.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -41,27 +42,6 @@ struct RefIndex
   uint64_t off_beg = UINT64_MAX, off_end = 0, n_records = 0;
   uint32_t last_bin = UINT32_MAX;
 };
-
-inline uint32_t bin_first(int level) { return static_cast<uint32_t>(((1ull << (3 * level)) - 1) / 7); }
-
-// hts_reg2bin: the smallest bin that holds [beg, end)
-inline uint32_t reg2bin(int64_t beg, int64_t end, int min_shift, int depth)
-{
-  --end;
-  int s = min_shift;
-  for (int l = depth; l > 0; --l, s += 3)
-    if ((beg >> s) == (end >> s))
-      return bin_first(l) + static_cast<uint32_t>(beg >> s);
-  return 0;
-}
-
-inline int bin_level(uint32_t bin)
-{
-  int l = 0;
-  while (bin >= bin_first(l + 1))
-    ++l;
-  return l;
-}
 
 // One BGZF member after the other, with the virtual offset of every byte handed out
 class MemberReader
@@ -120,63 +100,21 @@ private:
     for (;;)
     {
       long const here = std::ftell(fp_);
-      uint8_t h[18];
-      size_t const got = std::fread(h, 1, 18, fp_);
-      if (got == 0)
+      BgzfMember m;
+      MemberRead const got = read_bgzf_member(fp_, m, comp_);
+      if (got == MEMBER_END)
         return false;
-      if (got != 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4) || h[10] != 6 || h[11] != 0 || h[12] != 'B' || h[13] != 'C')
+      // (stricter than the readers: the members bgzip and gtx_bgzf_compress write, with BC as the only extra subfield)
+      if (got == MEMBER_BROKEN || m.xlen != 6 || m.bsize + 1 < 26)
       {
         bad_ = true; // not BGZF (plain gzip has no member sizes: it cannot be indexed)
         return false;
       }
-      size_t const bsize = (h[16] | (h[17] << 8)) + 1u;
-      if (bsize < 26)
-      {
-        bad_ = true;
-        return false;
-      }
-      comp_.resize(bsize - 18 + 8);
-      if (std::fread(comp_.data(), 1, bsize - 18, fp_) != bsize - 18)
-      {
-        bad_ = true;
-        return false;
-      }
-      uint32_t isize;
-      std::memcpy(&isize, comp_.data() + bsize - 18 - 4, 4);
-      next_off_ = here + static_cast<long>(bsize);
-      if (isize == 0)
+      next_off_ = here + static_cast<long>(m.bsize) + 1;
+      if (m.isize == 0)
         continue;
-      if (isize > 65536) // (a BGZF member holds at most 64 KB: a damaged ISIZE must not size an allocation)
-      {
-        bad_ = true;
-        return false;
-      }
-      data_.resize(isize);
-      size_t const clen = bsize - 18 - 8;
-      bool ok = inflate_raw(comp_.data(), clen, data_.data(), isize);
-      if (ok) // (the member's CRC32 holds the library's own decoder to the file: what does not match goes to zlib)
-      {
-        uint32_t want;
-        std::memcpy(&want, comp_.data() + clen, 4);
-        ok = crc32_of(data_.data(), isize) == want;
-      }
-      if (!ok)
-      {
-        z_stream z{};
-        if (inflateInit2(&z, -15) == Z_OK)
-        {
-          z.next_in = comp_.data();
-          z.avail_in = static_cast<uInt>(clen);
-          z.next_out = data_.data();
-          z.avail_out = isize;
-          ok = inflate(&z, Z_FINISH) == Z_STREAM_END && z.avail_out == 0;
-          inflateEnd(&z);
-          uint32_t want;
-          std::memcpy(&want, comp_.data() + clen, 4);
-          ok = ok && crc32_of(data_.data(), isize) == want;
-        }
-      }
-      if (!ok)
+      data_.resize(m.isize);
+      if (!inflate_bgzf_member(comp_.data(), static_cast<size_t>(m.clen), data_.data(), m.isize, true, true))
       {
         bad_ = true;
         return false;
@@ -212,27 +150,6 @@ bool read_gz(std::string const & path, std::string & out)
   gzclose(z);
   return n == 0;
 }
-
-struct Cursor
-{
-  std::string const & s;
-  size_t at = 0;
-  bool ok = true;
-  template <class T>
-  T get()
-  {
-    T v{};
-    if (at + sizeof(T) > s.size())
-    {
-      ok = false;
-      at = s.size();
-      return v;
-    }
-    std::memcpy(&v, s.data() + at, sizeof(T));
-    at += sizeof(T);
-    return v;
-  }
-};
 } // namespace
 
 // Where to start reading `vcf_path` for records of `chrom` that overlap [begin, end): the smallest chunk start among the
@@ -256,7 +173,7 @@ bool tabix_start(std::string const & vcf_path, std::string const & chrom, int64_
     if (::stat(vcf_path.c_str(), &sv) != 0 || ::stat((vcf_path + (csi ? ".csi" : ".tbi")).c_str(), &si) != 0 || si.st_mtime < sv.st_mtime)
       return false;
   }
-  Cursor c{raw};
+  IndexCursor c{raw.data(), raw.size()};
   char magic[4];
   for (char & m : magic)
     m = c.get<char>();
@@ -307,55 +224,7 @@ bool tabix_start(std::string const & vcf_path, std::string const & chrom, int64_
     return true; // a contig without records
   int64_t const max_pos = 1ll << std::min(62, min_shift + 3 * depth);
   int64_t const last = std::min<int64_t>(std::max<int64_t>(end, begin + 1), max_pos) - 1;
-  uint32_t const meta_bin = bin_first(depth + 1) + 1;
-  for (int32_t r = 0; c.ok && r <= tid; ++r)
-  {
-    int32_t const n_bin = c.get<int32_t>();
-    uint64_t best = UINT64_MAX, lower = 0;
-    int lower_level = -1;
-    for (int32_t b = 0; c.ok && b < n_bin; ++b)
-    {
-      uint32_t const bin = c.get<uint32_t>();
-      uint64_t const loffset = csi ? c.get<uint64_t>() : 0;
-      int32_t const n_chunk = c.get<int32_t>();
-      bool overlaps = false;
-      if (r == tid && bin != meta_bin && bin < meta_bin)
-      {
-        int const l = bin_level(bin);
-        int const shift = min_shift + 3 * (depth - l);
-        int64_t const kk = static_cast<int64_t>(bin - bin_first(l));
-        overlaps = kk >= (begin >> shift) && kk <= (last >> shift);
-        if (csi && kk == (begin >> shift) && l > lower_level)
-        {
-          lower_level = l;
-          lower = loffset;
-        }
-      }
-      for (int32_t k2 = 0; c.ok && k2 < n_chunk; ++k2)
-      {
-        uint64_t const cb = c.get<uint64_t>();
-        (void)c.get<uint64_t>();
-        if (overlaps && cb < best)
-          best = cb;
-      }
-    }
-    if (!csi)
-    {
-      int32_t const n_intv = c.get<int32_t>();
-      for (int32_t i = 0; c.ok && i < n_intv; ++i)
-      {
-        uint64_t const io = c.get<uint64_t>();
-        if (r == tid && i == (begin >> 14))
-          lower = io;
-      }
-    }
-    if (c.ok && r == tid && best != UINT64_MAX)
-    {
-      any = true;
-      voffset = std::max(best, lower);
-    }
-  }
-  return c.ok;
+  return index_start(c, IndexGeometry{min_shift, depth, csi}, tid, begin, last, any, voffset);
 }
 
 // A gzFile positioned at a virtual offset of a BGZF file (NULL: could not)
@@ -364,10 +233,12 @@ gzFile gz_open_at(std::string const & path, uint64_t voffset)
   int const fd = ::open(path.c_str(), O_RDONLY);
   if (fd < 0)
     return nullptr;
-  // (what the index points at has to be the start of a BGZF member: gzip magic, the extra field with the BC subfield)
-  uint8_t h[18];
-  if (::lseek(fd, static_cast<off_t>(voffset >> 16), SEEK_SET) < 0 || ::read(fd, h, 18) != 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4) ||
-      h[12] != 'B' || h[13] != 'C' || ::lseek(fd, static_cast<off_t>(voffset >> 16), SEEK_SET) < 0)
+  // (what the index points at has to be the start of a BGZF member, with BC in front of any other extra subfield)
+  off_t const at = static_cast<off_t>(voffset >> 16);
+  std::vector<uint8_t> head(12 + 65535); // (the longest header there is)
+  BgzfMember m;
+  ssize_t const got = ::pread(fd, head.data(), head.size(), at);
+  if (got < 0 || parse_bgzf_member(head.data(), static_cast<uint64_t>(got), m) || !m.bc_first || ::lseek(fd, at, SEEK_SET) < 0)
   {
     ::close(fd);
     return nullptr;

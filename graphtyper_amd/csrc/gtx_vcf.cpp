@@ -2559,90 +2559,3 @@ extern "C" int gtx_vcf_header(const gtx_vcf_header_request * rq, char * out, uin
     std::memcpy(out, s.data(), std::min<uint64_t>(cap, s.size()));
   return GTX_OK;
 }
-
-// ---- BGZF: the members htslib's bgzf_write makes (SAM spec 4.1): gzip members with the BC extra field, at most 0xff00 bytes of
-// input each, and the 28-byte empty member at the end of a file (what the reference's bgzf_stream writes its VCF through,
-// include/graphtyper/utilities/bgzf_stream.hpp).
-extern "C" int gtx_bgzf_compress(const void * in, uint64_t in_len, int level, int with_eof, void * out, uint64_t cap, uint64_t * out_len)
-{
-  if (!out_len || (in_len && !in) || (cap && !out))
-  {
-    gtx::g_last_error = "gtx_bgzf_compress: bad argument";
-    return GTX_ERR_ARG;
-  }
-  std::string res;
-  uint8_t const * p = static_cast<uint8_t const *>(in);
-  auto member = [&](uint8_t const * data, uint32_t n, std::string & res) -> bool
-  {
-    std::vector<uint8_t> buf(compressBound(n) + 64);
-    z_stream zs{};
-    if (deflateInit2(&zs, level < 0 ? Z_DEFAULT_COMPRESSION : std::min(level, 9), Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK)
-      return false;
-    zs.next_in = const_cast<Bytef *>(data);
-    zs.avail_in = n;
-    zs.next_out = buf.data();
-    zs.avail_out = static_cast<uInt>(buf.size());
-    int const rc = deflate(&zs, Z_FINISH);
-    uint32_t const clen = static_cast<uint32_t>(zs.total_out);
-    deflateEnd(&zs);
-    if (rc != Z_STREAM_END || clen + 26u > 0x10000u)
-      return false;
-    uint8_t head[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 0, 0};
-    uint16_t const bsize = static_cast<uint16_t>(clen + 25u);
-    head[16] = static_cast<uint8_t>(bsize & 255u);
-    head[17] = static_cast<uint8_t>(bsize >> 8);
-    res.append(reinterpret_cast<char const *>(head), 18);
-    res.append(reinterpret_cast<char const *>(buf.data()), clen);
-    uint32_t const tail[2] = {static_cast<uint32_t>(crc32(crc32(0L, Z_NULL, 0), data, n)), n};
-    res.append(reinterpret_cast<char const *>(tail), 8);
-    return true;
-  };
-  // members are independent: beyond a megabyte of input they are made on a few threads, each a run of consecutive members,
-  // and put together in order (the bytes are those of one thread)
-  uint64_t const n_members = (in_len + 0xff00u - 1) / 0xff00u;
-  unsigned const n_threads = n_members < 16 ? 1u : static_cast<unsigned>(std::min<uint64_t>(std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency() / 2)), n_members / 8));
-  std::vector<std::string> parts(std::max(1u, n_threads));
-  std::vector<char> failed(parts.size(), 0);
-  auto run = [&](unsigned k)
-  {
-    uint64_t const m0 = n_members * k / parts.size(), m1 = n_members * (k + 1) / parts.size();
-    for (uint64_t m = m0; m < m1 && !failed[k]; ++m)
-    {
-      uint64_t const at = m * 0xff00u;
-      if (!member(p + at, static_cast<uint32_t>(std::min<uint64_t>(0xff00u, in_len - at)), parts[k]))
-        failed[k] = 1;
-    }
-  };
-  if (parts.size() == 1)
-    run(0);
-  else
-  {
-    std::vector<std::thread> team;
-    for (unsigned k = 1; k < parts.size(); ++k)
-      team.emplace_back(run, k);
-    run(0);
-    for (auto & t : team)
-      t.join();
-  }
-  for (size_t k = 0; k < parts.size(); ++k)
-  {
-    if (failed[k])
-    {
-      gtx::g_last_error = "gtx_bgzf_compress: deflate failed";
-      return GTX_ERR_IO;
-    }
-    res += parts[k];
-  }
-  if (with_eof)
-  {
-    // the end-of-file marker is a fixed member (SAM spec 4.1.2), whatever the level: deflating nothing at level 0 gives a stored
-    // block and a member of 31 bytes, which htslib's bgzf_check_EOF does not take for the marker
-    static unsigned char const EOF_MEMBER[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    res.append(reinterpret_cast<char const *>(EOF_MEMBER), sizeof EOF_MEMBER);
-  }
-  *out_len = res.size();
-  if (res.size() > cap)
-    return out ? GTX_ERR_CAPACITY : GTX_OK;
-  std::memcpy(out, res.data(), res.size());
-  return GTX_OK;
-}

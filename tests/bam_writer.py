@@ -10,16 +10,17 @@ import zlib
 import numpy as np
 
 
-def bgzf(data, block=60000, deflate=None, with_eof=True):
-    """deflate: chunk -> raw DEFLATE stream, where the members are to be another encoder's than zlib's (its empty member is not
+def bgzf(data, block=60000, deflate=None, with_eof=True, extra=b""):
+    """extra: extra subfields in front of BC (tag, length, bytes: a reader has to walk them).
+    deflate: chunk -> raw DEFLATE stream, where the members are to be another encoder's than zlib's (its empty member is not
     the 28 bytes zlib's is: with_eof=False leaves it out)"""
     out = bytearray()
     for at in list(range(0, len(data), block)) + ([None] if with_eof else []):
         chunk = b"" if at is None else data[at:at + block]
         c = zlib.compressobj(6, zlib.DEFLATED, -15)
         comp = c.compress(chunk) + c.flush() if deflate is None else deflate(chunk)
-        bsize = len(comp) + 25  # total block size - 1
-        out += struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize)
+        bsize = len(comp) + 25 + len(extra)  # total block size - 1
+        out += struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, 6 + len(extra)) + extra + struct.pack("<BBHH", 66, 67, 2, bsize)
         out += comp + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk))
     return bytes(out)
 
@@ -51,18 +52,18 @@ def record(name, flag, tid, pos, mapq, cigar, mtid, mpos, tlen, codes, aux=(), q
     return struct.pack("<i", len(body)) + body
 
 
-def write_bam(path, refs, header_text, records, index=None, poison=False, csi=None, deflate=None):
+def write_bam(path, refs, header_text, records, index=None, poison=False, csi=None, deflate=None, extra=b""):
     """refs: [(name, length)]; records: bytes from record(), already in file order.
     index: [(tid, pos, end)] per record -> also writes path + ".bai" (SAM spec 5.2: bins, chunks, 16 kb linear index);
     poison: a BGZF member of garbage between the header and the records -- a reader that scans from the head fails on it,
     one that seeks through the index never sees it.
     csi = (min_shift, depth): the index goes to path + ".csi" instead (htslib's CSI: bins of a free geometry with their
     loffset, the whole index BGZF-compressed).
-    deflate: the encoder of the file's members (bgzf)."""
+    deflate, extra: the encoder and the extra subfields of the file's members (bgzf)."""
     head = b"BAM\1" + struct.pack("<i", len(header_text)) + header_text.encode() + struct.pack("<i", len(refs))
     for name, length in refs:
         head += struct.pack("<i", len(name) + 1) + name.encode() + b"\0" + struct.pack("<i", length)
-    out = bytearray(bgzf(head, deflate=deflate, with_eof=False))  # (without the end-of-file member)
+    out = bytearray(bgzf(head, deflate=deflate, with_eof=False, extra=extra))  # (without the end-of-file member)
     if poison:
         out += bgzf(b"\xff" * 300)[:-28]
     voffs = []
@@ -71,15 +72,15 @@ def write_bam(path, refs, header_text, records, index=None, poison=False, csi=No
     for r in records:
         if len(block) + len(r) > 60000 and block:
             pieces.append(bytes(block))
-            comp = bgzf(bytes(block), deflate=deflate, with_eof=False)
+            comp = bgzf(bytes(block), deflate=deflate, with_eof=False, extra=extra)
             out += comp
             block, block_start = bytearray(), len(out)
         voffs.append((block_start << 16) | len(block))
         block += r
     if block:
-        out += bgzf(bytes(block), deflate=deflate, with_eof=False)
+        out += bgzf(bytes(block), deflate=deflate, with_eof=False, extra=extra)
     end_voff = len(out) << 16
-    out += bgzf(b"", deflate=deflate)  # the end-of-file member
+    out += bgzf(b"", deflate=deflate, extra=extra)  # the end-of-file member
     open(path, "wb").write(bytes(out))
     if index is None:
         return

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fuzz of gtx_reads_* and gtx_bam_shrink (graphtyper_amd/csrc/gtx_bam.cpp, gtx_shrink.inl), not collected by pytest (tests/test_bam_ingest.py runs a few seeds of
+"""Fuzz of gtx_reads_* and gtx_bam_shrink (graphtyper_amd/csrc/gtx_bam.cpp, gtx_shrink.cpp), not collected by pytest (tests/test_bam_ingest.py runs a few seeds of
 it): corrupted BAM payloads (re-compressed, so the BGZF layer is intact and the record parser sees the damage), corrupted
 headers, truncated payloads / files, corrupted BGZF bytes.  Each case runs in a subprocess; anything but a clean exit with
 records or a GTX_ERR_* is a finding.

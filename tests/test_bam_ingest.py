@@ -3,6 +3,12 @@ tests/bam_writer.py -- the record stream must come out in the reference's order 
 packed bases inside a file, k-way merge over the files) with the reference's per-record facts (sample / read-group index
 from @RG and the RG tag, get_score_diff with its parsing quirks, cigar ends, packed bases verbatim), a region must return
 the records that overlap it, and the stream must drive the whole path: BAM -> gtx_stream -> align -> score -> calls == oracle."""
+import os
+import struct
+import subprocess
+import sys
+import zlib
+
 import numpy as np
 import pytest
 
@@ -305,3 +311,147 @@ def test_array_field_with_a_hostile_count_ends_the_aux_walk(tmp_path):
                  os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)
     out = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True, timeout=60)
     assert "without RG tag" in out.stderr, (out.stdout, out.stderr[-300:])
+
+
+# ---- the shared BGZF / index / record layer (gtx_bgzf.hpp, gtx_hts_index.hpp, gtx_bam_record.hpp): verdicts it must not lose ----
+
+def _small_bam(tmp_path, name, n_contigs=3, per_contig=40, seed=21, **kw):
+    """a few records on each of n_contigs contigs of 100 kb (one BGZF member of records per contig or so); -> path, refs, header, recs"""
+    rng = np.random.default_rng(seed)
+    refs = [("chr%d" % (k + 1), 100000) for k in range(n_contigs)]
+    recs = []
+    for tid in range(n_contigs):
+        for p in np.sort(rng.integers(0, 60000, size=per_contig)):  # (nothing beyond 60 000: a window without a record)
+            codes = rng.choice([1, 2, 4, 8], size=100).astype(np.uint8)
+            recs.append(dict(tid=tid, pos=int(p), codes=codes, flag=0, mapq=60, cigar=[("M", 60), ("D", 5), ("M", 40)], mtid=-1, mpos=-1, tlen=0,
+                             aux=[("AS", "C", 100)], rg=None, name="r%d" % len(recs)))
+    header = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
+    path = str(tmp_path / name)
+    blobs = [bw.record(r["name"], r["flag"], r["tid"], r["pos"], r["mapq"], r["cigar"], r["mtid"], r["mpos"], r["tlen"], r["codes"], r["aux"]) for r in recs]
+    bw.write_bam(path, refs, header, blobs, index=[(r["tid"], r["pos"], r["pos"] + 105) for r in recs], **kw)
+    return path, refs, header, recs
+
+
+def _in_region(recs, tid, lo, hi):
+    return _expected([recs], [[]], keep=lambda r: r["tid"] == tid and r["pos"] < hi and r["pos"] + 105 > lo)[0]
+
+
+def test_members_with_a_second_extra_subfield(tmp_path):
+    """BC behind another extra subfield (XLEN = 10): the readers walk the subfields -- whole file, region over the .bai and the
+    pre-filter give what they give for the plain file"""
+    plain, _, _, recs = _small_bam(tmp_path, "plain.bam")
+    extra, _, _, _ = _small_bam(tmp_path, "extra.bam", extra=b"XY\0\0")
+    assert open(extra, "rb").read()[10:18] == b"\x0a\0XY\0\0BC" and open(extra + ".bai", "rb").read() != open(plain + ".bai", "rb").read()
+    _check(gtx.Reads([extra]), _expected([recs], [[]])[0])
+    want = _in_region(recs, 1, 20000, 40000)
+    assert len(want) > 5
+    _check(gtx.Reads([extra], region="chr2:20001-40000"), want)
+    par = gtx.shrink_params(min_read_len=20, min_num_matching=10)
+    st = [gtx.bam_shrink(p, [("chr2", 100, 50000)], p + ".out", par) for p in (plain, extra)]
+    assert st[0] == st[1] and st[0]["records_written"] > 0
+    assert open(plain + ".out", "rb").read() == open(extra + ".out", "rb").read()
+
+
+def _header_bytes(name_len=None):
+    text = "@HD\tVN:1.6\n@SQ\tSN:chr1\tLN:1000\n"
+    head = b"BAM\1" + np.int32(len(text)).tobytes() + text.encode() + np.int32(2).tobytes()
+    for k, name in enumerate((b"chr1\0", b"chr2\0")):
+        head += np.int32(len(name) if name_len is None or k else name_len).tobytes() + name + np.int32(1000).tobytes()
+    return head
+
+
+@pytest.mark.parametrize("what,status,message", [("magic", 4, "is not a BAM file"), ("text", 7, "truncated header"), ("refs", 7, "truncated header"),
+                                                 ("name_length", 7, "truncated header")])
+def test_header_verdicts(tmp_path, what, status, message):
+    """not BAM -> GTX_ERR_UNSUPPORTED; cut inside the text or the reference list, or a contig name's length beyond 1 MiB ->
+    GTX_ERR_IO "truncated header"; the pre-filter answers GTX_ERR_UNSUPPORTED to each"""
+    head = _header_bytes((1 << 20) + 1 if what == "name_length" else None)
+    if what == "magic":
+        head = b"BAX\1" + head[4:]
+    elif what == "text":
+        head = head[:20]
+    elif what == "refs":
+        head = head[:-6]
+    path = str(tmp_path / "h.bam")
+    open(path, "wb").write(bw.bgzf(head))
+    with pytest.raises(gtx.GtxError) as e:
+        gtx.Reads([path])
+    assert e.value.status == status and message in str(e.value)
+    with pytest.raises(gtx.GtxError) as e:
+        gtx.bam_shrink(path, [("chr1", 1, 100)], path + ".out")
+    assert e.value.status == 4
+
+
+@pytest.mark.parametrize("csi", [None, (14, 5)])
+def test_an_index_cut_behind_the_second_contig(tmp_path, csi):
+    """a .bai / .csi that ends behind contig 2's part: contig 2 still starts from the index (the member of garbage behind the
+    header is never read, and a window without records is empty without a scan), contig 3 falls back to the scan -- which fails
+    on the garbage, and on the file without garbage gives the records of the whole index' run"""
+    ext = ".csi" if csi else ".bai"
+    clean, _, _, recs = _small_bam(tmp_path, "clean.bam", csi=csi)
+    path, _, _, _ = _small_bam(tmp_path, "poisoned.bam", csi=csi, poison=True)
+    whole = {p: open(p + ext, "rb").read() for p in (clean, path)}
+    for p in (clean, path):
+        raw = whole[p]
+        if csi:  # (the writer's index is one BGZF member and the end-of-file member)
+            raw = zlib.decompress(raw, 31)
+            at = 20
+        else:
+            at = 8
+        for _ in range(2):  # behind the bins (and the linear index) of contigs 1 and 2
+            n_bin, = struct.unpack_from("<i", raw, at)
+            at += 4
+            for _ in range(n_bin):
+                n_chunk, = struct.unpack_from("<i", raw, at + (12 if csi else 4))
+                at += (16 if csi else 8) + 16 * n_chunk
+            if not csi:
+                n_intv, = struct.unpack_from("<i", raw, at)
+                at += 4 + 8 * n_intv
+        assert at < len(raw) - 8
+        open(p + ext, "wb").write(bw.bgzf(raw[:at + 6]) if csi else raw[:at + 6])
+    want2, want3 = _in_region(recs, 1, 20000, 40000), _in_region(recs, 2, 20000, 40000)
+    assert len(want2) > 5 and len(want3) > 5
+    _check(gtx.Reads([path], region="chr2:20001-40000"), want2)
+    assert len(gtx.Reads([path], region="chr2:80001-90000").next(10)[0]) == 0
+    with pytest.raises(gtx.GtxError):
+        gtx.Reads([path], region="chr3:20001-40000")
+    _check(gtx.Reads([clean], region="chr2:20001-40000"), want2)
+    _check(gtx.Reads([clean], region="chr3:20001-40000"), want3)
+    open(clean + ext, "wb").write(whole[clean])
+    _check(gtx.Reads([clean], region="chr3:20001-40000"), want3)
+
+
+_SWITCH_CHILD = r'''
+import sys
+sys.path.insert(0, sys.argv[2])
+from graphtyper_amd import lib as gtx
+try:
+    r = gtx.Reads([sys.argv[1]])
+    n = 0
+    while True:
+        recs, seq = r.next(64)
+        if len(recs) == 0:
+            break
+        n += len(recs)
+    print("ok", n)
+except gtx.GtxError as e:
+    print("err", e.status)
+'''
+
+
+def test_the_readers_switches_in_child_processes(tmp_path):
+    """GTX_INFLATE=zlib reads what the own decoder reads; a member whose CRC32 is wrong is refused, and read with GTX_BGZF_CRC=0"""
+    good, _, _, recs = _small_bam(tmp_path, "good.bam", n_contigs=1)
+    raw = bytearray(open(good, "rb").read())
+    raw[-28 - 8] ^= 1  # the CRC32 of the last member with data (the end-of-file member has 28 bytes)
+    bad = str(tmp_path / "crc.bam")
+    open(bad, "wb").write(bytes(raw))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(path, **env):
+        e = {k: v for k, v in os.environ.items() if k not in ("GTX_INFLATE", "GTX_BGZF_CRC")}
+        e.update(env)
+        return subprocess.run([sys.executable, "-c", _SWITCH_CHILD, path, root], capture_output=True, text=True, env=e).stdout.strip()
+    assert run(good) == run(good, GTX_INFLATE="zlib") == "ok %d" % len(recs)
+    assert run(bad) == run(bad, GTX_INFLATE="zlib") == "err 7"
+    assert run(bad, GTX_BGZF_CRC="0") == run(bad, GTX_BGZF_CRC="0", GTX_INFLATE="zlib") == "ok %d" % len(recs)

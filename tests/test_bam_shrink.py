@@ -1,4 +1,4 @@
-"""The read pre-filter (gtx_bam_shrink, graphtyper_amd/csrc/gtx_shrink.inl) against the oracle's restatement of the reference's
+"""The read pre-filter (gtx_bam_shrink, graphtyper_amd/csrc/gtx_shrink.cpp) against the oracle's restatement of the reference's
 bamshrink (oracle/gto_shrink.hpp <- /root/reference/src/utilities/bamshrink.cpp:64-1045): the record stream of the output file,
 byte for byte, on random coordinate-sorted BAM files that reach every branch (pairs, single reads, unmapped mates, mates on
 other contigs, adapters, soft / hard clips, indels, Ns at the ends, AS / XS / WS scores in every integer type, full bins)."""

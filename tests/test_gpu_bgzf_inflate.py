@@ -128,6 +128,31 @@ def test_bgzf_buffers_come_back(tmp_path):
     inflater.close()
 
 
+def test_members_as_the_one_header_parser_sees_them():
+    """gtx_inflate_bgzf parses members with the readers' parser (gtx_bgzf.hpp): a member of 1 byte, one of 300 bytes with another
+    extra subfield in front of BC and the end-of-file member come back as zlib's bytes; what is not a member is refused, by name,
+    before anything is launched"""
+    one, some = b"x", bytes(range(256)) + b"graphtyper " * 4
+    assert len(some) == 300
+    first, second = bw.bgzf(one, with_eof=False), bw.bgzf(some, with_eof=False, extra=b"XY\0\0")
+    buf = first + second + bw.bgzf(b"")
+    assert second[10:18] == b"\x0a\0XY\0\0BC"
+    want = b"".join(zlib.decompressobj(31).decompress(buf[at:]) for at in (0, len(first), len(first) + len(second)))
+    inflater = gtx.Inflater(0)
+    assert inflater.bgzf(buf) == want == one + some
+    huge = bytearray(first)
+    huge[-4:] = (65537).to_bytes(4, "little")
+    for data, why in ((first + second[:10], "member 1 at byte %d: not a BGZF member" % len(first)),  # cut in the header: in front of XLEN,
+                      (first + second[:20], "member 1 at byte %d: truncated" % len(first)),          # ... and inside the extra field
+                      (first + second[:-9], "member 1 at byte %d: truncated" % len(first)),          # cut in the data
+                      (first[:12] + b"BX" + first[14:] + second, "member 0 at byte 0: no BC field"),
+                      (bytes(huge) + second, "member 0 at byte 0: ISIZE beyond 65536")):
+        with pytest.raises(gtx.GtxError) as e:
+            inflater.bgzf(data)
+        assert e.value.status == 7 and str(e.value).endswith("gtx_inflate_bgzf: " + why), str(e.value)
+    inflater.close()
+
+
 def _member_starts(raw):
     at, out = 0, []
     while at < len(raw):

@@ -5,6 +5,8 @@ region query through the index (bins -> chunks -> records) returns exactly the r
 import gzip
 import os
 import struct
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -222,3 +224,130 @@ def test_files_that_cannot_be_indexed(tmp_path):
         gtx.tabix_build(str(tmp_path / "missing.vcf.gz"))
     with pytest.raises(gtx.GtxError):
         gtx.tabix_start(gz, "chrA", 0, 10)  # no index beside it
+
+
+def test_members_with_a_second_extra_subfield(tmp_path):
+    """BC behind another extra subfield (XLEN = 10): gtx_tabix_build indexes only the members bgzip writes and refuses the file;
+    gtx_graph_from_files still scans it, with no index beside it and with a stale one"""
+    rng = np.random.default_rng(12)
+    ref = "".join(rng.choice(list("ACGT"), 20_000))
+    fa = str(tmp_path / "r.fa")
+    open(fa, "w").write(">chr1\n" + "\n".join(ref[i:i + 60] for i in range(0, len(ref), 60)) + "\n")
+    lines = ["chr1\t%d\t.\t%s\t%s\t.\t.\t.\n" % (p, ref[p - 1], "ACGT"[("ACGT".index(ref[p - 1]) + 1) % 4])
+             for p in sorted(set(int(x) for x in rng.integers(1000, 19_000, 200)))]
+    data = (HEADER + "".join(lines)).encode()
+    plain, vz = str(tmp_path / "clean.vcf"), str(tmp_path / "v.vcf.gz")
+    open(plain, "wb").write(data)
+    region = "chr1:5001-15000"
+    want = gtx.graph_from_files(fa, plain, region)
+    assert len(want[0]["var_order"]) > 50
+    open(vz, "wb").write(bw.bgzf(data, block=3000))
+    gtx.tabix_build(vz)
+    os.utime(vz + ".tbi", (1_000_000_000, 1_000_000_000))  # (older than the file that follows)
+    members = bw.bgzf(data, block=3000, extra=b"XY\0\0")
+    assert members[10:18] == b"\x0a\0XY\0\0BC"
+    open(vz, "wb").write(members)
+    for stale in (True, False):
+        got = gtx.graph_from_files(fa, vz, region)
+        assert got[1] == want[1] and all(np.array_equal(got[0][k], want[0][k]) for k in want[0])
+        if stale:
+            os.remove(vz + ".tbi")
+    with pytest.raises(gtx.GtxError) as e:
+        gtx.tabix_build(vz)
+    assert e.value.status == 7 and "is not a readable BGZF file" in str(e.value) and not os.path.exists(vz + ".tbi")
+
+
+def test_an_index_cut_behind_the_second_contig(tmp_path):
+    """a .tbi that ends behind contig 2's part answers for contigs 1 and 2 as the whole one does -- a window without records: none --
+    and is no index for contig 3"""
+    rng = np.random.default_rng(13)
+    text, lines, recs = make_vcf(rng, 300, contigs=(("chrA", 100_000), ("chrB", 100_000), ("chrC", 100_000)))
+    path = str(tmp_path / "v.vcf.gz")
+    write_bgzf(path, text, rng)
+    gtx.tabix_build(path)
+    queries = [(name, b, b + 20_000) for name in ("chrA", "chrB", "chrC") for b in (0, 40_000, 70_000)]
+    whole = [gtx.tabix_start(path, *q) for q in queries]
+    assert sum(v is not None for v in whole) >= 6 and gtx.tabix_start(path, "chrB", 2_000_000, 2_100_000) is None
+    raw = gzip.decompress(open(path + ".tbi", "rb").read())
+    at = 36 + struct.unpack_from("<i", raw, 32)[0]
+    for _ in range(2):  # behind the bins and the linear index of chrA and chrB
+        n_bin, = struct.unpack_from("<i", raw, at)
+        at += 4
+        for _ in range(n_bin):
+            at += 8 + 16 * struct.unpack_from("<i", raw, at + 4)[0]
+        at += 4 + 8 * struct.unpack_from("<i", raw, at)[0]
+    assert at < len(raw) - 8
+    open(path + ".tbi", "wb").write(bw.bgzf(raw[:at + 6]))
+    for q, v in zip(queries, whole):
+        if q[0] == "chrC":
+            with pytest.raises(gtx.GtxError):
+                gtx.tabix_start(path, *q)
+        else:
+            assert gtx.tabix_start(path, *q) == v
+    assert gtx.tabix_start(path, "chrB", 2_000_000, 2_100_000) is None
+
+
+def test_graphs_over_an_index_cut_behind_the_second_contig(tmp_path):
+    """gtx_graph_from_files with such a .tbi: contig 2 is read through it, contig 3 by the scan it falls back to -- the graphs are
+    those of the whole index either way"""
+    rng = np.random.default_rng(14)
+    names = ("chrA", "chrB", "chrC")
+    refs = {n: "".join(rng.choice(list("ACGT"), 30_000)) for n in names}
+    fa = str(tmp_path / "r.fa")
+    open(fa, "w").write("".join(">%s\n" % n + "\n".join(refs[n][i:i + 60] for i in range(0, 30_000, 60)) + "\n" for n in names))
+    lines = ["%s\t%d\t.\t%s\t%s\t.\t.\t.\n" % (n, p, refs[n][p - 1], "ACGT"[("ACGT".index(refs[n][p - 1]) + 1) % 4])
+             for n in names for p in sorted(set(int(x) for x in rng.integers(1000, 29_000, 150)))]
+    vz = str(tmp_path / "v.vcf.gz")
+    open(vz, "wb").write(bw.bgzf((HEADER + "".join(lines)).encode(), block=2000))
+    gtx.tabix_build(vz)
+    regions = ("chrB:10001-20000", "chrC:10001-20000")
+    want = [gtx.graph_from_files(fa, vz, r) for r in regions]
+    assert all(len(w[0]["var_order"]) > 20 for w in want)
+    raw = gzip.decompress(open(vz + ".tbi", "rb").read())
+    at = 36 + struct.unpack_from("<i", raw, 32)[0]
+    for _ in range(2):
+        n_bin, = struct.unpack_from("<i", raw, at)
+        at += 4
+        for _ in range(n_bin):
+            at += 8 + 16 * struct.unpack_from("<i", raw, at + 4)[0]
+        at += 4 + 8 * struct.unpack_from("<i", raw, at)[0]
+    open(vz + ".tbi", "wb").write(bw.bgzf(raw[:at + 6]))
+    assert gtx.tabix_start(vz, "chrB", 10_000, 20_000) is not None
+    with pytest.raises(gtx.GtxError):
+        gtx.tabix_start(vz, "chrC", 10_000, 20_000)
+    for r, w in zip(regions, want):
+        got = gtx.graph_from_files(fa, vz, r)
+        assert got[1] == w[1] and all(np.array_equal(got[0][k], w[0][k]) for k in w[0])
+
+
+_BUILD_CHILD = r'''
+import sys
+sys.path.insert(0, sys.argv[2])
+from graphtyper_amd import lib as gtx
+try:
+    gtx.tabix_build(sys.argv[1])
+    print("ok")
+except gtx.GtxError as e:
+    print("err", e.status, "not a readable BGZF file" in str(e))
+'''
+
+
+def test_a_wrong_crc_is_refused_whatever_the_readers_switch_says(tmp_path):
+    """gtx_tabix_build compares every member's CRC32: GTX_BGZF_CRC=0 is the BAM readers' switch, not its own"""
+    rng = np.random.default_rng(15)
+    text, _, _ = make_vcf(rng, 50)
+    raw = bytearray(bw.bgzf(text.encode(), block=65536))
+    assert len(raw) > 28 + 26
+    raw[-28 - 8] ^= 1  # the CRC32 of the one member with data (the end-of-file member has 28 bytes)
+    good, bad = str(tmp_path / "good.vcf.gz"), str(tmp_path / "crc.vcf.gz")
+    open(good, "wb").write(bw.bgzf(text.encode(), block=65536))
+    open(bad, "wb").write(bytes(raw))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(path, **env):
+        e = {k: v for k, v in os.environ.items() if k != "GTX_BGZF_CRC"}
+        e.update(env)
+        return subprocess.run([sys.executable, "-c", _BUILD_CHILD, path, root], capture_output=True, text=True, env=e).stdout.strip()
+    assert run(good, GTX_BGZF_CRC="0") == "ok"
+    assert run(bad) == run(bad, GTX_BGZF_CRC="0") == "err 7 True"
+    assert not os.path.exists(bad + ".tbi")
