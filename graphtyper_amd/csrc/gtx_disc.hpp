@@ -1,0 +1,17 @@
+// gtx_disc.hpp -- the discovery object of include/gtx.h, for the translation units that hold its entry points (gtx_discover.hip:
+// the first pass; gtx_realign.hip: the realignment to the indels).
+#pragma once
+#include <cstdint>
+#include <string>
+
+#include "gtx_devmem.hpp"
+
+struct gtx_disc
+{
+  int device = -1;
+  int64_t region_begin = 0;
+  std::string reference; // region's bases as given (upper case letters)
+  gtx::DevPtr<uint32_t> d_refp; // (gtx_disc_destroy waits for the device before the two blocks go back to the cache)
+  uint32_t ref_groups = 0;
+  gtx::DevPtr<uint8_t> d_refc; // the letters themselves (the span of an indel compares them as the host does)
+};

@@ -82,6 +82,11 @@ struct WaveHip
     }
     return x;
   }
+  // every lane's value moves one lane up; lane 0 receives `first` (one DPP move: wave_shr:1 leaves lane 0 with the old value)
+  static __device__ inline void shift_up(PerLane<uint32_t> const & in, uint32_t first, PerLane<uint32_t> & out)
+  {
+    out.v = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(first), static_cast<int>(in.v), 0x138, 0xF, 0xF, false));
+  }
   static __device__ inline void atomic_or_u64(uint64_t * p, uint64_t v) { atomicOr(reinterpret_cast<unsigned long long *>(p), static_cast<unsigned long long>(v)); }
   static __device__ inline unsigned long long clock() { return clock64(); }
   static __device__ inline void atomic_add_u32(uint32_t * p, uint32_t v) { atomicAdd(p, v); }

@@ -33,7 +33,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_shrink_params_default", "gtx_bam_shrink", "gtx_inflate_raw", "gtx_tabix_build", "gtx_tabix_start", "gtx_pipeline_run", "gtx_regions_run", "gtx_regions_free", "gtx_bam_shrink_multi", "gtx_disc_first_pass_haplotypes", "gtx_disc_merge",
            "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged",
            "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts",
-           "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device"]
+           "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device",
+           "gtx_disc_realign_batch", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide"]
 
 
 class GraphView(C.Structure):
@@ -112,6 +113,16 @@ assert DISC_READ.itemsize == 16 and DISC_EVENT.itemsize == 20 and DISC_READ_OUT.
 LABEL = np.dtype([("start_index", np.uint32), ("end_index", np.uint32), ("variant_id", np.uint32)], align=True)
 assert READ_META.itemsize == 20 and REC_META.itemsize == 16 and SCORE_ITEM.itemsize == 40 and STREAM_RECORD.itemsize == 56 \
     and SAMPLE_CALL.itemsize == 12
+
+
+REALIGN_PAIR = np.dtype([("read", np.uint32), ("target", np.uint32)], align=True)
+REALIGN_RESULT = np.dtype([("score", np.int32), ("clip_begin", np.uint16), ("clip_end", np.uint16), ("target_begin", np.uint16),
+                           ("target_end", np.uint16), ("status", np.uint32)], align=True)
+REALIGN_EVENT = np.dtype([("pos", np.uint32), ("len", np.uint16), ("type", np.uint8), ("reserved", np.uint8), ("seq_off", np.uint32)], align=True)
+REALIGN_DECISION = np.dtype([("pos", np.int64), ("pos_end", np.int64), ("outcome", np.uint32), ("num_clipped_begin", np.uint32),
+                             ("num_clipped_end", np.uint32), ("num_ins_begin", np.uint32)], align=True)
+REALIGN_OK, REALIGN_BAD_PAIR, REALIGN_TOO_LONG = 0, 1, 2
+REALIGN_NO_PADDING, REALIGN_BETTER, REALIGN_SAME_OVERLAPPING, REALIGN_SAME, REALIGN_WORSE = 0, 1, 2, 3, 4
 
 
 def build(force=False):
@@ -209,6 +220,12 @@ def lib():
                                                  C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.gtx_disc_first_pass_haplotypes_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                             C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.gtx_disc_realign_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                             C.c_uint32, C.c_void_p, C.c_void_p]
+        L.gtx_disc_realign_wants.argtypes = [C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, C.c_int64, C.c_uint32]
+        L.gtx_disc_realign_target.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        L.gtx_disc_realign_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []
@@ -484,6 +501,51 @@ def disc_first_pass_device(handle, d_planes, plane_stride, d_reads, d_cigar, d_r
             continue
         check(rc)
         return words[:n_words.value]
+
+
+def disc_realign_target(handle, max_read_size, events):
+    """gtx_disc_realign_target.  events: [(pos, 'I' | 'D', letters)], events[0] the indel being realigned to (a deletion's letters
+    count by their number only) -> (the window's letters as bytes, ref_pos int32 array, begin_padded, applied bits)"""
+    L = lib()
+    ev = np.zeros(len(events), REALIGN_EVENT)
+    letters = b""
+    for i, (pos, kind, seq) in enumerate(events):
+        ev[i] = (pos, len(seq), ord(kind), 0, len(letters))
+        letters += seq.encode() if isinstance(seq, str) else bytes(seq)
+    cap = 2 * (int(max_read_size) + 100) + len(letters)
+    seq, ref_pos = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.int32)
+    n, begin, applied = C.c_uint32(), C.c_int64(), C.c_uint64()
+    check(L.gtx_disc_realign_target(handle, max_read_size, _p(ev), len(ev), letters, _p(seq), _p(ref_pos), cap, C.byref(n), C.byref(begin), C.byref(applied)))
+    return seq[:n.value].tobytes(), ref_pos[:n.value].copy(), int(begin.value), int(applied.value)
+
+
+def disc_realign_decide(result, read_len, ref_pos, begin_padded, region_begin, old_score, indel_pos):
+    """gtx_disc_realign_decide over one REALIGN_RESULT record -> a REALIGN_DECISION record"""
+    res = np.array([result], REALIGN_RESULT)
+    ref_pos = np.ascontiguousarray(ref_pos, np.int32)
+    out = np.zeros(1, REALIGN_DECISION)
+    check(lib().gtx_disc_realign_decide(_p(res), read_len, _p(ref_pos), len(ref_pos), begin_padded, region_begin, old_score, indel_pos, _p(out)))
+    return out[0]
+
+
+def disc_realign_batch(handle, planes, plane_stride, lens, n_reads, target_seq, target_off, n_targets, pairs, n_pairs, out=None, stream=None):
+    """gtx_disc_realign_batch.  Every array is a device pointer (an integer: the call is then asynchronous on `stream`, `out` must be
+    given and is returned as it is) or a numpy array (all of them: they go through torch tensors on cuda:0, the call waits and the
+    results come back as a REALIGN_RESULT array)."""
+    L = lib()
+    arrays = (planes, lens, target_seq, target_off, pairs)
+    if not any(isinstance(a, np.ndarray) for a in arrays):
+        check(L.gtx_disc_realign_batch(handle, planes, plane_stride, lens, n_reads, target_seq, target_off, n_targets, pairs, n_pairs, out, stream))
+        return out
+    import torch
+    dev = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to("cuda:0") if a.size else torch.zeros(16, dtype=torch.uint8, device="cuda:0")
+           for a in arrays]
+    d_out = torch.zeros(max(n_pairs, 1) * REALIGN_RESULT.itemsize, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    check(L.gtx_disc_realign_batch(handle, dev[0].data_ptr(), plane_stride, dev[1].data_ptr(), n_reads, dev[2].data_ptr(), dev[3].data_ptr(), n_targets,
+                                   dev[4].data_ptr(), n_pairs, d_out.data_ptr(), stream))
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy().view(REALIGN_RESULT)[:n_pairs].copy()
 
 
 def pack_nibbles(codes, stride=None):

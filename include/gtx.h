@@ -1025,8 +1025,10 @@ int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const 
  * counts between the events of a read (caller.cpp:777-822), the coverage difference arrays, and the two support filters
  * (EventSupport::has_good_support src/typer/event.cpp:226-256 for SNPs; good / realignment support of indels,
  * caller.cpp:990-1186) -- on the host over downloaded arrays (gtx_disc_first_pass) or on the device (gtx_disc_first_pass_device) --
- * and, below, the haplotypes of the surviving events and the merge of the files' results.  Not built: the realignment of reads
- * to the indels (paw::pairwise_alignment, a dependency that is absent from the reference tree) and the second pass behind it.
+ * and, below, the haplotypes of the surviving events and the merge of the files' results, and the pieces of the realignment of
+ * reads to the indels (gtx_disc_realign_*, at the end of this header: the aligner, the haplotype windows, the per-pair decisions).
+ * Not built: the sequential driver of the realignment, which feeds a read's new state into the next indel
+ * (replace_indel_events, the buckets), the second pass behind it and the variant records.
  *   gtx_disc_create        the region's reference (upper-case letters; reference[0] = contig position region_begin, 0-based) on `device`
  *   gtx_disc_events_batch  device: the events of n_reads reads in stream order.  d_planes: the reads as plane rows (gtx_pack_planes),
  *                          d_qual: their base qualities (qual_stride bytes per read), d_reads / d_cigar: the bam1_t fields and the raw
@@ -1089,7 +1091,7 @@ int gtx_disc_first_pass(const gtx_disc *, const gtx_disc_read * reads, const uin
  * n_events, per event its "ever" and "always" sets (count + events each).
  * gtx_disc_merge: two such results as one -- merge_haplotypes2 (:64-165) and the union of the files' indels
  * (streamlined_discovery, :2853-2903); `into` may be empty; files are merged in their order.  What the reference does next --
- * realignment of reads to the indels (paw::pairwise_alignment, absent from its tree) -- is not built. */
+ * realign_to_indels -- is built as its pieces (gtx_disc_realign_*, below); the loop over the indels that strings them is the caller's. */
 int gtx_disc_first_pass_haplotypes(const gtx_disc *, const gtx_disc_read * reads, const uint32_t * cigar, const gtx_disc_read_out * read_out,
                                    uint32_t n_reads, const gtx_disc_event * events, uint64_t n_events, const uint8_t * seq, uint32_t seq_stride,
                                    uint32_t bucket_size, int32_t file_index, uint32_t * out, uint64_t cap, uint64_t * n_words);
@@ -1117,6 +1119,99 @@ int gtx_disc_first_pass_haplotypes_device(const gtx_disc *, const uint8_t * d_pl
                                           const uint32_t * d_cigar, const gtx_disc_read_out * d_read_out, uint32_t n_reads, const gtx_disc_event * d_events,
                                           const uint32_t * d_counts, uint32_t bucket_size, int32_t file_index, uint32_t * out, uint64_t cap,
                                           uint64_t * n_words, void * stream);
+
+/* ---- realignment of reads to indel haplotypes: the pieces of realign_to_indels (src/typer/caller.cpp:1855-2171).  The reference
+ * aligns every read that may overlap a candidate indel to a window of the region's reference with the indel (and the read's own
+ * indels) applied, with paw::pairwise_alignment, and keeps, counts or discards the read's new place by the score alone.  Here:
+ * gtx_disc_realign_wants (which reads, :1941-1958), gtx_disc_realign_target (the window, :1890-1907 and :1968-2002 through
+ * apply_indel_event, src/typer/event.cpp:293-396), gtx_disc_realign_batch (the alignments, on the device) and
+ * gtx_disc_realign_decide (what becomes of one read, :2025-2153).  The loop over the indels, in which a read's new state enters
+ * the next indel's round, is the caller's.
+ *
+ * The alignment.  Query q[1..m] (a read, 4-bit BAM codes) against target t[1..n] (a window, letters mapped through htslib's
+ * seq_nt16_table); s(a, b) = +1 when a == b, a == 15 or b == 15 (an N on either side scores as a match, caller.cpp:2359), else -4;
+ * gap open 7, gap extend 1, clip 5 (include/graphtyper/constants.hpp.in:49-53); both ends of the target free, clipping on
+ * (caller.cpp:1865-1870).  Cells outside 1..m x 1..n are -inf:
+ *   start(i)   = 0 if i == 1 else -5                    origin (db = j-1, cb = i-1)
+ *   S(i,j)     = s(q_i,t_j) + max(start(i), H(i-1,j-1))
+ *   E(i,j)     = max(H(i,j-1) - 7, E(i,j-1) - 1)
+ *   F(i,j)     = max(H(i-1,j) - 7, F(i-1,j) - 1)
+ *   H(i,j)     = max(S, E, F)
+ *   total(i,j) = S(i,j) - (5 if i < m else 0)
+ * Every value carries its origin (db, cb) unchanged; a max prefers the higher score, then the smaller db, then the smaller cb.  The
+ * result is the (i, j) with the highest total score; among equal scores the smaller j, then the smaller i.  score = that total,
+ * clip_begin = cb, clip_end = i (query bases [cb, i) are aligned), target_begin = db, target_end = j (target bases [db, j)).  An
+ * alignment begins and ends with a pair of bases; there is no traceback.
+ * THE TIE-BREAK IS THIS LIBRARY'S OWN: among equally good alignments paw's choice of end points is unknown.  NOBODY HAS COMPARED
+ * THE SCORE WITH paw's EITHER: paw is absent from the reference's tree and cannot be built; the score is the optimum of the model
+ * the reference's text states, which is all that can be said.
+ *   gtx_disc_realign_batch  device, asynchronous on `stream`: n_pairs alignments, one wavefront each.  d_planes / plane_stride: the
+ *                           reads as plane rows (gtx_pack_planes), d_lens[r]: read r's length; d_target_seq: the windows' letters one
+ *                           behind the other, window w at [d_target_off[w], d_target_off[w + 1]); d_pairs: (read, target) indices;
+ *                           d_out[p]: the result of pair p.  status GTX_REALIGN_BAD_PAIR: the pair names a read or a window that is
+ *                           not there, or an empty one, or a window whose offsets are not in order; GTX_REALIGN_TOO_LONG: a read of
+ *                           more than GTX_MAX_READ bases (or more than its plane row holds), a window of more than
+ *                           GTX_REALIGN_MAX_TARGET letters -- nothing of such a pair is loaded, its other fields are 0.  A gtx_disc
+ *                           made with device -1: GTX_ERR_NO_DEVICE; n_pairs == 0: GTX_OK.
+ *   gtx_disc_realign_wants  host: 1 when realign_to_indels aligns a read at [pos, pos_end] (contig positions) with these clip
+ *                           counts to an indel at indel_pos whose EventSupport::span is `span`, else 0 (:1941-1958; pos < 0: 0).
+ *   gtx_disc_realign_target host (device -1 will do): the window around events[0], the indel being realigned to --
+ *                           begin_padded = max(0, pos - max_read_size - 2 * 50 - region_begin), end = pos + max_read_size + 2 * 50 -
+ *                           region_begin or the region's end -- with events[0], then events[1..] (the read's own indels that have
+ *                           realignment support, :1968-2002) applied in turn by apply_indel_event's rules: the search for the
+ *                           position, ref_pos <= 0 and positions behind the window refused, the purity test over +-3, the
+ *                           deletion's end test, the insertion's ref_positions values (its `len` entries hold the index pos + 1).
+ *                           event_seq: the letters of the insertions (seq_off).  seq / ref_pos receive *n entries (cap too small:
+ *                           GTX_ERR_CAPACITY with *n = the number wanted), *applied bit e: events[e] was applied.  Bit 0 clear: the
+ *                           reference skips the indel (`continue`); the window is then the plain one and no later event is tried.
+ *                           At most 64 events; a window that begins behind the region: GTX_ERR_ARG.
+ *   gtx_disc_realign_decide host: :2025-2153 over one result with status GTX_REALIGN_OK.  n: the window's length.  NO_PADDING
+ *                           (target_begin == 0 || target_end == n; the read is skipped), BETTER (score > old_score; out's pos,
+ *                           pos_end, num_clipped_begin, num_clipped_end = read_len - clip_end and num_ins_begin are the read's new
+ *                           state, :2136-2153), WORSE (READ_ANTI_SUPPORT), SAME_OVERLAPPING (READ_MULTI_SUPPORT: equal score and
+ *                           ref_pos[target_begin] + begin_padded <= indel_pos <= ref_pos[target_end] + begin_padded, as the text
+ *                           has it, :2086-2087) or SAME. */
+#define GTX_REALIGN_MAX_TARGET 2048u
+#define GTX_REALIGN_OK 0u
+#define GTX_REALIGN_BAD_PAIR 1u
+#define GTX_REALIGN_TOO_LONG 2u
+typedef struct gtx_disc_realign_pair
+{
+  uint32_t read, target;
+} gtx_disc_realign_pair;
+typedef struct gtx_disc_realign_result
+{
+  int32_t score;
+  uint16_t clip_begin, clip_end, target_begin, target_end;
+  uint32_t status;
+} gtx_disc_realign_result;
+typedef struct gtx_disc_realign_event
+{
+  uint32_t pos; /* Event::pos: contig position, 0-based */
+  uint16_t len; /* Event::sequence.size() */
+  uint8_t type; /* 'I', 'D' */
+  uint8_t reserved;
+  uint32_t seq_off; /* 'I': its first letter in event_seq */
+} gtx_disc_realign_event;
+#define GTX_REALIGN_NO_PADDING 0u
+#define GTX_REALIGN_BETTER 1u
+#define GTX_REALIGN_SAME_OVERLAPPING 2u
+#define GTX_REALIGN_SAME 3u
+#define GTX_REALIGN_WORSE 4u
+typedef struct gtx_disc_realign_decision
+{
+  int64_t pos, pos_end; /* BETTER: contig positions */
+  uint32_t outcome;
+  uint32_t num_clipped_begin, num_clipped_end, num_ins_begin; /* BETTER */
+} gtx_disc_realign_decision;
+int gtx_disc_realign_batch(gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const uint16_t * d_lens, uint32_t n_reads, const char * d_target_seq,
+                           const uint32_t * d_target_off /* n_targets + 1 */, uint32_t n_targets, const gtx_disc_realign_pair * d_pairs, uint32_t n_pairs,
+                           gtx_disc_realign_result * d_out, void * stream);
+int gtx_disc_realign_wants(int64_t pos, int64_t pos_end, uint32_t num_clipped_begin, uint32_t num_clipped_end, int64_t indel_pos, uint32_t span);
+int gtx_disc_realign_target(const gtx_disc *, uint32_t max_read_size, const gtx_disc_realign_event * events, uint32_t n_events, const char * event_seq,
+                            char * seq, int32_t * ref_pos, uint32_t cap, uint32_t * n, int64_t * begin_padded, uint64_t * applied);
+int gtx_disc_realign_decide(const gtx_disc_realign_result * result, uint32_t read_len, const int32_t * ref_pos, uint32_t n, int64_t begin_padded,
+                            int64_t region_begin, int64_t old_score, int64_t indel_pos, gtx_disc_realign_decision * out);
 
 #ifdef __cplusplus
 }
