@@ -15,7 +15,7 @@
 #include <memory>
 #include <vector>
 
-#include "../../graphtyper_amd/csrc/gtx_realign_dev.hpp"
+#include "gtx_realign_dev.hpp" // from the Makefile's CSRC
 
 using namespace gtx;
 

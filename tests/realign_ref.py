@@ -14,11 +14,17 @@ CODE_LETTER = "=ACMGRSVTWYHKDBN"
 
 
 def nt16(letter):
-    """htslib's seq_nt16_table over letters and '='; anything else is N"""
+    """htslib's seq_nt16_table over letters (either case) and '='; anything else is N.  letter: a one-letter str, or a byte's
+    value (what iterating over bytes gives): a byte that is no ASCII character is no letter"""
+    if isinstance(letter, int):
+        if not 0 <= letter < 128:
+            return 15
+        letter = chr(letter)
     return NT16.get(letter.upper(), 15)
 
 
 def codes_of(text):
+    """text: str or bytes"""
     return tuple(nt16(c) for c in text)
 
 
@@ -76,6 +82,22 @@ def result(reads, targets, pair):
     if len(reads[r]) > MAX_READ or len(targets[w]) > MAX_TARGET:
         return (0, 0, 0, 0, 0, TOO_LONG)
     return align(tuple(reads[r]), codes_of(targets[w])) + (OK,)
+
+
+def result_in_arena(reads, arena, off, pair):
+    """the same for windows given as the entry point takes them: `arena` (bytes) holds the letters, window w is
+    arena[off[w]:off[w + 1]], len(off) - 1 windows, off[-1] the arena's size.  A window whose offsets are not in order, or whose
+    end lies behind off[-1], is a bad pair."""
+    r, w = pair
+    n_targets = len(off) - 1
+    if r >= len(reads) or w >= n_targets or len(reads[r]) == 0:
+        return (0, 0, 0, 0, 0, BAD_PAIR)
+    t0, t1 = int(off[w]), int(off[w + 1])
+    if t1 <= t0 or t1 > int(off[n_targets]):
+        return (0, 0, 0, 0, 0, BAD_PAIR)
+    if len(reads[r]) > MAX_READ or t1 - t0 > MAX_TARGET:
+        return (0, 0, 0, 0, 0, TOO_LONG)
+    return align(tuple(reads[r]), codes_of(bytes(arena[t0:t1]))) + (OK,)
 
 
 # ---- the reference's text around the aligner -------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import realign_cases as rc
+import realign_ref as rr
 from graphtyper_amd import lib as gtx
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,27 +22,32 @@ def emu_realign(tmp_path_factory):
     return out
 
 
-def run_emu(emu, tmp_path, reads, targets, pairs):
-    planes, plane_stride, lens, seq, off, pr = rc.arrays(reads, targets, pairs)
+def run_emu(emu, tmp_path, arrays):
+    """arrays: what rc.arrays returns"""
     case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    with open(case, "wb") as f:
-        f.write(np.array([plane_stride, len(reads), len(targets), len(pr), len(seq)], np.uint32).tobytes())
-        f.write(planes.tobytes())
-        f.write(lens.tobytes() + b"\0\0" * (len(lens) & 1))
-        f.write(off.tobytes())
-        f.write(seq.tobytes() + b"\0" * (-len(seq) % 4))
-        f.write(pr.tobytes())
+    rc.write_case(case, *arrays)
     subprocess.run([emu, case, out], check=True, stdout=subprocess.DEVNULL, timeout=600)
     return rc.as_tuples(np.fromfile(out, gtx.REALIGN_RESULT))
 
 
-@pytest.mark.parametrize("name", sorted(rc.SETS))
+@pytest.mark.parametrize("name", sorted(rc.SETS) + sorted(rc.ENTRY))
 def test_every_field_equals_the_restatement(emu_realign, tmp_path, name):
-    reads, targets, pairs = rc.get(name)
-    got, want = run_emu(emu_realign, tmp_path, reads, targets, pairs), rc.expected(name)
+    """the pair sets, and the cases of the entry point's other paths: rows wider than the reads, set bits behind a read's last
+    base, offsets made by hand, letters in lower case and bytes that are no letters"""
+    arrays, want = rc.case(name)
+    got = run_emu(emu_realign, tmp_path, arrays)
     assert len(got) == len(want)
-    wrong = [(i, pairs[i], got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
+    wrong = [(i, tuple(arrays[5][i]), got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
     assert wrong == [], wrong[:5]
+
+
+def test_a_pair_and_its_reversal_score_alike(emu_realign, tmp_path):
+    """the model is symmetric under reversal: a check of reads over 64 bases that does not go through the restatement"""
+    reads, _, pairs = rc.get("reversed_pairs")
+    got = run_emu(emu_realign, tmp_path, rc.case("reversed_pairs")[0])
+    assert len(got) == 2 * 2 * len(rc.M_SIZES) * len(rc.REVERSED_N) and all(g[5] == 0 for g in got)
+    assert [(pairs[k], got[k], got[k + 1]) for k in range(0, len(got), 2) if got[k][0] != got[k + 1][0]] == []
+    assert sum(len(reads[p[0]]) > 64 for p in pairs) >= len(pairs) // 2
 
 
 def test_the_sets_hold_what_they_are_for():
@@ -57,3 +63,16 @@ def test_the_sets_hold_what_they_are_for():
     n = len(rc.get("no_padding")[1][0])
     assert all(w[3] == 0 or w[4] == n for w in rc.expected("no_padding")[:5])
     assert len(rc.get("simulated")[2]) == 300
+    assert (len(rc.get("exhaustive_ac")[2]), len(rc.get("exhaustive_acn")[2])) == (7812, 14400)
+    n = 2048
+    assert [w[:5] for w in rc.expected("limits")] == [(256, 0, 256, n - 256, n), (256, 0, 256, 0, 256), (1, 0, 1, n - 1, n)]
+    # the hand-made offsets: bad windows between good ones, and two windows that share letters
+    want = rc.case("offsets_by_hand")[1]
+    assert [w[5] for w in want[::3]] == [0, 1, 0, 1, 1, 1, 0, 0]
+
+
+def test_the_outcomes_the_pairs_with_window_records_reach():
+    """which outcomes of the decision simulated() and no_padding reach with old_score one below, at and one above the new score (by the
+    restatement): test_gpu_realign.py carries the device's results through gtx_disc_realign_decide over the same pairs"""
+    assert rc.outcomes("simulated") == {rr.BETTER, rr.SAME_OVERLAPPING, rr.SAME, rr.WORSE}  # (its windows are padded well)
+    assert rc.outcomes("no_padding") == {rr.NO_PADDING, rr.BETTER, rr.SAME, rr.WORSE}
