@@ -30,113 +30,13 @@
 #include "gtx_devmem.hpp"
 #include "gtx_devprim.hpp"
 #include "gtx_disc.hpp"
+#include "gtx_disc_events_dev.hpp"
 #include "gtx_disc_support.hpp"
+#include "wave_hip.hpp"
 
 namespace
 {
 using namespace gtx;
-
-// 32 codes from bit offset `o` of a plane array of `groups` groups (zeros behind its end), plane b
-__device__ inline uint32_t plane_bits(uint32_t const * planes, uint32_t groups, uint32_t o, uint32_t b)
-{
-  uint32_t const g = o >> 5, s = o & 31u;
-  uint32_t const lo = g < groups ? planes[4 * g + b] : 0u, hi = g + 1 < groups ? planes[4 * (g + 1) + b] : 0u;
-  return s == 0 ? lo : (lo >> s) | (hi << (32 - s));
-}
-
-struct Bits32
-{
-  uint32_t p0, p1, p2, p3;
-  __device__ uint32_t onehot() const
-  {
-    uint32_t const odd = p0 ^ p1 ^ p2 ^ p3, three = (p0 & p1 & (p2 | p3)) | (p2 & p3 & (p0 | p1));
-    return odd & ~three;
-  }
-};
-
-__device__ inline Bits32 load32(uint32_t const * planes, uint32_t groups, uint32_t o)
-{
-  return Bits32{plane_bits(planes, groups, o, 0), plane_bits(planes, groups, o, 1), plane_bits(planes, groups, o, 2), plane_bits(planes, groups, o, 3)};
-}
-
-// all of the `n` bases from offset o are A / C / G / T
-__device__ inline bool all_acgt(uint32_t const * planes, uint32_t groups, uint32_t o, uint32_t n)
-{
-  for (uint32_t k = 0; k < n; k += 32)
-  {
-    uint32_t const m = n - k >= 32 ? 0xFFFFFFFFu : (1u << (n - k)) - 1u;
-    if ((load32(planes, groups, o + k).onehot() & m) != m)
-      return false;
-  }
-  return true;
-}
-
-// One walk over a read's CIGAR (caller.cpp:583-775).  EMIT = false counts the events, EMIT = true writes them to out[0..).
-// Returns the number of events; pos_end = region-relative end of the alignment (min(ref_offset, REF_SIZE - 1)).
-template <bool EMIT>
-__device__ uint32_t walk(uint32_t const * refp, uint32_t ref_groups, long REF_SIZE, long region_begin, uint32_t const * row, uint32_t row_groups,
-                         uint8_t const * qual, gtx_disc_read const & r, uint32_t const * cigar, uint32_t read_index, gtx_disc_event * out, long & pos_end)
-{
-  uint32_t n = 0;
-  long read_offset = 0, ref_offset = static_cast<long>(r.pos) - region_begin;
-  long const l_qseq = r.l_qseq;
-  auto put = [&](uint32_t pos, uint8_t type, uint16_t len, uint32_t seq, uint8_t hq, uint16_t dist)
-  {
-    if (EMIT)
-      out[n] = gtx_disc_event{read_index, pos, seq, len, type, hq, dist, 0};
-    ++n;
-  };
-  for (uint32_t i = 0; i < r.n_cigar; ++i)
-  {
-    uint32_t const word = cigar[i];
-    long const count = word >> 4;
-    uint32_t const op = word & 15u;
-    if (ref_offset >= REF_SIZE)
-      break;
-    if (op == 0 || op == 7 || op == 8) // M = X
-    {
-      long const span = std::min<long>(count, std::min(REF_SIZE - ref_offset, std::max<long>(l_qseq - read_offset, 0)));
-      for (long k = 0; k < span; k += 32)
-      {
-        uint32_t const m = span - k >= 32 ? 0xFFFFFFFFu : (1u << (span - k)) - 1u;
-        Bits32 const a = load32(row, row_groups, static_cast<uint32_t>(read_offset + k)), g = load32(refp, ref_groups, static_cast<uint32_t>(ref_offset + k));
-        uint32_t diff = ((a.p0 ^ g.p0) | (a.p1 ^ g.p1) | (a.p2 ^ g.p2) | (a.p3 ^ g.p3)) & a.onehot() & g.onehot() & m;
-        while (diff)
-        {
-          uint32_t const j = static_cast<uint32_t>(__builtin_ctz(diff));
-          diff &= diff - 1u;
-          long const read_pos = read_offset + k + j;
-          uint32_t const code = ((a.p0 >> j) & 1u) | (((a.p1 >> j) & 1u) << 1) | (((a.p2 >> j) & 1u) << 2) | (((a.p3 >> j) & 1u) << 3);
-          char const base = code == 1 ? 'A' : code == 2 ? 'C' : code == 4 ? 'G' : 'T';
-          long const dist = std::min(read_pos, l_qseq - 1 - read_pos);
-          put(static_cast<uint32_t>(ref_offset + k + j + region_begin), 'X', 1, static_cast<uint32_t>(base), EMIT && qual[read_pos] >= 25 ? 1 : 0,
-              static_cast<uint16_t>(std::min<long>(dist, 0xFFFF)));
-        }
-      }
-      read_offset += count;
-      ref_offset += count;
-    }
-    else if (op == 1) // I
-    {
-      long const b = std::min(read_offset, l_qseq), e = std::min(read_offset + count, l_qseq);
-      if (b == e)
-        continue; // (caller.cpp:698-699: the read offset stays)
-      if (all_acgt(row, row_groups, static_cast<uint32_t>(b), static_cast<uint32_t>(e - b)))
-        put(static_cast<uint32_t>(region_begin + ref_offset), 'I', static_cast<uint16_t>(e - b), static_cast<uint32_t>(b), 1, 0);
-      read_offset += count;
-    }
-    else if (op == 2) // D
-    {
-      if (ref_offset + count < REF_SIZE && all_acgt(refp, ref_groups, static_cast<uint32_t>(ref_offset), static_cast<uint32_t>(count)))
-        put(static_cast<uint32_t>(region_begin + ref_offset), 'D', static_cast<uint16_t>(std::min<long>(count, 0xFFFF)), static_cast<uint32_t>(ref_offset), 1, 0);
-      ref_offset += count;
-    }
-    else if (op == 4) // S
-      read_offset += count;
-  }
-  pos_end = std::min(ref_offset, REF_SIZE - 1);
-  return n;
-}
 
 __global__ __launch_bounds__(256) void gtx_disc_events_kernel(uint32_t const * __restrict__ refp, uint32_t ref_groups, long REF_SIZE, long region_begin,
                                                               uint8_t const * __restrict__ rows, uint32_t plane_stride, uint8_t const * __restrict__ qual,
@@ -144,55 +44,9 @@ __global__ __launch_bounds__(256) void gtx_disc_events_kernel(uint32_t const * _
                                                               uint32_t const * __restrict__ cigar, uint32_t n_reads, gtx_disc_event * __restrict__ events,
                                                               uint32_t event_cap, uint32_t * counts, gtx_disc_read_out * __restrict__ read_out)
 {
-  uint32_t const i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
-  bool const live = i < n_reads;
-  gtx_disc_read r{};
-  uint32_t n = 0, state = GTX_DISC_SKIPPED;
-  long pos_end = 0;
-  uint32_t const * row = nullptr;
-  if (live)
-  {
-    r = reads[i];
-    row = reinterpret_cast<uint32_t const *>(rows + static_cast<uint64_t>(i) * plane_stride);
-    // caller.cpp:517-561: reads without a cigar or in front of the region are passed over; a read that starts at or behind the
-    // region's end ends the pass
-    if (r.n_cigar != 0 && r.pos >= region_begin)
-    {
-      if (static_cast<long>(r.pos) - region_begin >= REF_SIZE)
-        state = GTX_DISC_END;
-      else
-      {
-        state = GTX_DISC_COUNTED;
-        n = walk<false>(refp, ref_groups, REF_SIZE, region_begin, row, plane_stride / PLANE_GROUP_BYTES, qual + static_cast<uint64_t>(i) * qual_stride, r,
-                        cigar + r.cigar_off, i, nullptr, pos_end);
-      }
-    }
-  }
-  // one contiguous piece of the output per wavefront
-  uint32_t x = n;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1)
-  {
-    uint32_t const y = __shfl_up(x, d);
-    if (lane >= static_cast<uint32_t>(d))
-      x += y;
-  }
-  uint32_t const total = __shfl(x, 63);
-  uint32_t base = 0;
-  if (lane == 0 && total)
-    base = atomicAdd(counts, total);
-  base = __shfl(base, 0);
-  uint32_t const first = base + x - n;
-  if (live)
-  {
-    bool const fits = static_cast<uint64_t>(first) + n <= event_cap;
-    if (n && fits)
-      (void)walk<true>(refp, ref_groups, REF_SIZE, region_begin, row, plane_stride / PLANE_GROUP_BYTES, qual + static_cast<uint64_t>(i) * qual_stride, r,
-                       cigar + r.cigar_off, i, events + first, pos_end);
-    if (n && !fits)
-      atomicAdd(counts + 1, n);
-    read_out[i] = gtx_disc_read_out{first, n, static_cast<int32_t>(pos_end), state};
-  }
+  disc_events_wave<WaveHip>(DiscBatch{refp, ref_groups, REF_SIZE, region_begin, rows, plane_stride, qual, qual_stride, reads, cigar, n_reads, events, event_cap,
+                                      counts, read_out},
+                            blockIdx.x * blockDim.x + (threadIdx.x & ~63u));
 }
 } // namespace
 
@@ -205,7 +59,7 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
   }
   *out = nullptr;
   if (device == -1) // like gtx_ctx_create's -1: an object for the host stages only (the bookkeeping over events a device made elsewhere);
-  {                 // gtx_disc_events_batch refuses it -- there is no CPU path for the walk over the CIGARs
+  {                 // gtx_disc_events_batch refuses it -- the library has no CPU path for the walk over the CIGARs (tests/emu_disc_events runs its text)
     auto h = std::make_unique<gtx_disc>();
     h->device = -1;
     h->region_begin = region_begin;
@@ -223,16 +77,9 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
   d->device = device;
   d->region_begin = region_begin;
   d->reference.assign(reference, reference_len);
-  // the region as bit planes of BAM codes (anything but A / C / G / T: N)
-  d->ref_groups = static_cast<uint32_t>((reference_len + 31) / 32) + 2;
+  d->ref_groups = disc_ref_groups(reference_len);
   std::vector<uint32_t> planes(static_cast<size_t>(d->ref_groups) * 4, 0);
-  for (uint64_t i = 0; i < reference_len; ++i)
-  {
-    char const c = reference[i];
-    uint32_t const code = c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 4u : c == 'T' ? 8u : 15u;
-    for (uint32_t b = 0; b < 4; ++b)
-      planes[4 * (i >> 5) + b] |= ((code >> b) & 1u) << (i & 31u);
-  }
+  disc_ref_planes(reference, reference_len, planes.data());
   if (hipSetDevice(device) != hipSuccess || !alloc(d->d_refp, planes.size() * 4) ||
       hipMemcpy(d->d_refp.get(), planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess || !alloc(d->d_refc, reference_len) ||
       hipMemcpy(d->d_refc.get(), reference, reference_len, hipMemcpyHostToDevice) != hipSuccess)

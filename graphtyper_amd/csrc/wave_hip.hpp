@@ -91,6 +91,14 @@ struct WaveHip
   static __device__ inline unsigned long long clock() { return clock64(); }
   static __device__ inline void atomic_add_u32(uint32_t * p, uint32_t v) { atomicAdd(p, v); }
   static __device__ inline void atomic_add_u64(unsigned long long * p, unsigned long long v) { atomicAdd(p, v); }
+  // the leader takes `n` (wave-uniform) units from a device counter; every lane gets the old value
+  static __device__ inline uint32_t claim_u32(uint32_t * p, uint32_t n)
+  {
+    uint32_t base = 0;
+    if (leader())
+      base = atomicAdd(p, n);
+    return __shfl(base, 0);
+  }
   // next free slot of a log every lane appends to (fetch-and-increment).  The lanes that are here together ask with one
   // atomic: a single device counter sustains ~90 M returning atomics a second, a dense graph wants more log entries.
   static __device__ inline uint32_t atomic_claim_u32(uint32_t * p)

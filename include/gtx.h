@@ -1059,7 +1059,9 @@ typedef struct gtx_disc_event
   uint32_t read;         /* index of the read in its batch */
   uint32_t pos;          /* Event::pos: contig position, 0-based */
   uint32_t seq;          /* 'X': the read's base (ASCII); 'I': offset of the first inserted base in the read; 'D': offset of the first deleted base in the region */
-  uint16_t len;          /* Event::sequence.size() */
+  uint16_t len;          /* Event::sequence.size().  A STATED LIMIT THAT DEPARTS FROM THE REFERENCE: a deletion of more than 65 535 bases
+                          * is no event (the reference makes one with all of its bases); the walk moves over it as over a deletion
+                          * that covers a base other than A/C/G/T.  At exactly 65 535 bases it is an event. */
   uint8_t type;          /* 'X', 'I', 'D' */
   uint8_t hq;            /* 'X': base quality >= 25; indels: 1 */
   uint16_t max_distance; /* 'X': min(read_pos, l_qseq - 1 - read_pos) */

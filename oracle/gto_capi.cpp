@@ -824,6 +824,49 @@ extern "C"
     }
   }
 
+  // gto_first_pass over a region given with its length -- its bytes may be anything, a 0 among them -- with the walk's own events and
+  // read states (gto_first_pass_full's ev_out / ro_out).  Returns the number of events, -2 when ev_cap is too small, -1 on an error;
+  // *n_words: the words of gto_first_pass (written to `out` when they fit `cap`).
+  long gto_first_pass_events(char const * reference, long reference_len, long region_begin, long n, int32_t const * pos, uint16_t const * flag,
+                             uint8_t const * mapq, uint32_t const * cigar, uint32_t const * cigar_off, uint8_t const * codes, uint8_t const * qual,
+                             uint32_t const * code_off, void * ev_out, long ev_cap, void * ro_out, uint32_t * out, long cap, long * n_words)
+  {
+    try
+    {
+      static char const NT16[] = "=ACMGRSVTWYHKDBN";
+      std::vector<gto::disc::Read> reads(static_cast<std::size_t>(n));
+      for (long i = 0; i < n; ++i)
+      {
+        gto::disc::Read & r = reads[i];
+        r.pos = pos[i];
+        r.flag = flag[i];
+        r.mapq = mapq[i];
+        r.cigar.assign(cigar + cigar_off[i], cigar + cigar_off[i + 1]);
+        for (uint32_t k = code_off[i]; k < code_off[i + 1]; ++k)
+          r.sequence.push_back(NT16[codes[k] & 15]);
+        r.qual.assign(qual + code_off[i], qual + code_off[i + 1]);
+      }
+      gto::disc::FirstPass fp;
+      fp.run(reads, std::string(reference, static_cast<std::size_t>(reference_len)), region_begin, 50);
+      if (static_cast<long>(fp.raw_events.size()) > ev_cap)
+        return -2;
+      if (!fp.raw_events.empty())
+        std::memcpy(ev_out, fp.raw_events.data(), fp.raw_events.size() * sizeof(fp.raw_events[0]));
+      if (n)
+        std::memcpy(ro_out, fp.read_outs.data(), fp.read_outs.size() * sizeof(fp.read_outs[0]));
+      std::vector<uint32_t> const s = fp.dump();
+      *n_words = static_cast<long>(s.size());
+      if (*n_words <= cap && !s.empty())
+        std::memcpy(out, s.data(), s.size() * 4);
+      return static_cast<long>(fp.raw_events.size());
+    }
+    catch (std::exception const & e)
+    {
+      g_error = e.what();
+      return -1;
+    }
+  }
+
   // merge_haplotypes2 + the union of the indels over two such word streams (the first may be empty: nothing merged yet)
   long gto_disc_merge(uint32_t const * into, long n_into, uint32_t const * from, long n_from, uint32_t * out, long cap)
   {

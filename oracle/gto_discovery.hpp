@@ -290,7 +290,9 @@ struct FirstPass
         }
         case 'D':
         {
-          if (ref_offset + cigar_count >= REF_SIZE)
+          // A STATED LIMIT THAT DEPARTS FROM THE REFERENCE (include/gtx.h: gtx_disc_event.len has 16 bits): a deletion of more than
+          // 65 535 bases is no event; the reference makes one with all of its bases (make_deletion_event).  The offset moves.
+          if (ref_offset + cigar_count >= REF_SIZE || cigar_count > 0xFFFF)
           {
             ref_offset += cigar_count;
             break;

@@ -52,3 +52,32 @@ def test_bad_arguments_are_refused_before_anything_is_touched():
         args[at] = bad
         assert call(*args) == 1, at  # GTX_ERR_ARG
     L.gtx_disc_destroy(h)
+
+
+def test_the_events_batch_checks_its_arguments_before_it_asks_for_the_device():
+    """gtx_disc_events_batch: GTX_ERR_ARG is decided before the device is asked for, so an object made for device -1 still gets it for a
+    plane_stride of 0 or of no whole plane groups, for misaligned planes and for a null array with n_reads > 0; with all arguments
+    right and no reads the answer is the no-device status"""
+    L = gtx.lib()
+    h = C.c_void_p()
+    gtx.check(L.gtx_disc_create(b"ACGTACGT", 8, 0, -1, C.byref(h)))
+    d = np.zeros(64, np.uint32)
+    at = d.ctypes.data
+    assert at % 4 == 0
+    good = [h, at, 16, at, 32, at, at, 1, at, 4, at, at, None]  # planes, stride, qual, stride, reads, cigar, n_reads, events, cap, counts, read_out, stream
+    bad = [(2, 0), (2, 8), (2, 24), (1, at + 1), (1, at + 2), (0, None)] + [(k, None) for k in (1, 3, 5, 6, 8, 10, 11)]
+    for k, value in bad:
+        args = list(good)
+        args[k] = value
+        assert L.gtx_disc_events_batch(*args) == 1, (k, value)  # GTX_ERR_ARG
+        assert b"gtx_disc_events_batch: bad argument" in L.gtx_last_error()
+    for n_reads in (1, 0):
+        args = list(good)
+        args[7] = n_reads
+        assert L.gtx_disc_events_batch(*args) == 2  # GTX_ERR_NO_DEVICE
+    none = [h, None, 16, None, 0, None, None, 0, None, 0, None, None, None]  # no reads: no array is needed
+    assert L.gtx_disc_events_batch(*none) == 2
+    args = list(good)
+    args[8], args[9] = None, 0  # no event buffer for an event_cap of 0 is no bad argument
+    assert L.gtx_disc_events_batch(*args) == 2
+    L.gtx_disc_destroy(h)
