@@ -547,7 +547,12 @@ int gtx_ctx_profile_log(gtx_ctx *, uint64_t * out, uint64_t cap, uint64_t * n);
 /* Per (sample, haplotype) genotype call on the device: replaces get_haplotype_phred (src/typer/vcf.cpp:47-82) and the
  * SampleCall the reference builds from it in Vcf::add_haplotype (src/typer/vcf.cpp:1507-1530; constructor, get_gt_call and
  * get_gq of src/typer/sample_call.cpp:34-131).  Reads the accumulators of gtx_score_batch as they are (unsaturated sums;
- * the clamps of gtx_scores_finalize are applied on the fly).
+ * the clamps of gtx_scores_finalize are applied on the fly: every d_gt_cov word stops at 0xFFFF, each of d_hap_u32[1..3] at
+ * 0xFF on its own, the two depth sums at 0xFFFF; d_hap_u32[0], max_log_score and the replay mark, is not read).
+ * Precondition: every d_log_score word is below 0x10000, which is what the reference's uint16_t rows can hold.  Nothing is
+ * clamped there: a cell that gtx_score_batch has driven past explain_to_score's guard has to go through gtx_scores_replay
+ * (or gtx_scores_replay_apply) first, which brings it back under the limit; with a larger word the cell's PL, GT and GQ are
+ * not the reference's.  The accumulators are read only; n_samples = 0 is GTX_OK and writes nothing.
  *   d_phred [n_samples * total_tri]  uint8   PL of every genotype, layout of d_log_score
  *   d_calls [n_samples * n_hap]      gtx_sample_call, index sample * n_hap + hap */
 typedef struct gtx_sample_call

@@ -739,6 +739,32 @@ extern "C"
     out[2] = parked;
   }
 
+  // Test infrastructure, no counterpart in the reference: the HapSample of every (haplotype, sample) set by hand, so that
+  // sample_calls() can be asked about states no read set of a test's size leaves behind (tests/calls_cases.py).  The arrays have the
+  // reference's own widths -- what a HapSample can hold -- and run haplotype by haplotype, within a haplotype sample by sample (the
+  // order of gto_calls_dump): log_score num * (num + 1) / 2 entries per cell, gt_coverage num entries per cell, the three depth
+  // counters one entry per cell.  max_log_score follows the row.  Connections and site statistics stay as they are.  The product
+  // must not use this.  Returns the number of cells.
+  long gto_genotyper_set_hap_samples(void * p, uint16_t const * log_score, uint16_t const * gt_coverage, uint8_t const * ambiguous_depth,
+                                     uint8_t const * ambiguous_depth_alt, uint8_t const * alt_proper_pair_depth)
+  {
+    long cell = 0;
+    for (auto & hap : static_cast<GenoHandle *>(p)->g->writer.haplotypes)
+      for (auto & hs : hap.hap_samples)
+      {
+        hs.log_score.assign(log_score, log_score + hs.log_score.size());
+        log_score += hs.log_score.size();
+        hs.gt_coverage.assign(gt_coverage, gt_coverage + hs.gt_coverage.size());
+        gt_coverage += hs.gt_coverage.size();
+        hs.max_log_score = *std::max_element(hs.log_score.begin(), hs.log_score.end());
+        hs.ambiguous_depth = ambiguous_depth[cell];
+        hs.ambiguous_depth_alt = ambiguous_depth_alt[cell];
+        hs.alt_proper_pair_depth = alt_proper_pair_depth[cell];
+        ++cell;
+      }
+    return cell;
+  }
+
   // ---- discovery, first pass (gto_discovery.hpp): reads as arrays -> the canonical word stream of the surviving events
   // codes: 4-bit BAM codes of all reads back to back (code_off[n + 1]), qual the same shape, cigar: raw BAM words (cigar_off[n + 1])
   long gto_first_pass(char const * reference, long region_begin, long bucket_size, long n, int32_t const * pos, uint16_t const * flag,

@@ -250,6 +250,16 @@ class OracleGenotyper:
         L.gto_calls_dump(C.c_void_p(self.g), _p(out), C.c_long(n))
         return out[:n]
 
+    def set_hap_samples(self, log_score, gt_coverage, ambiguous_depth, ambiguous_depth_alt, alt_proper_pair_depth):
+        """gto_genotyper_set_hap_samples: every HapSample set by hand, from arrays of the reference's own widths (u16 / u8) that run
+        haplotype by haplotype, within a haplotype sample by sample; returns the number of cells"""
+        L = lib()
+        L.gto_genotyper_set_hap_samples.restype = C.c_long
+        L.gto_genotyper_set_hap_samples.argtypes = [C.c_void_p] * 6
+        a = [np.ascontiguousarray(log_score, np.uint16), np.ascontiguousarray(gt_coverage, np.uint16)] + \
+            [np.ascontiguousarray(x, np.uint8) for x in (ambiguous_depth, ambiguous_depth_alt, alt_proper_pair_depth)]
+        return int(L.gto_genotyper_set_hap_samples(C.c_void_p(self.g), *[_p(x) for x in a]))
+
     def phase_flags(self):
         """rows (hap1, allele1, hap2, allele2, flags) of the `ph` map (gto_phase_flags)"""
         L = lib()

@@ -39,3 +39,29 @@ def test_header_is_plain_c(tmp_path):
                    'return gtx_strerror(0) == 0; }\n')
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c",
                            str(src), "-o", str(tmp_path / "use_gtx.o")])
+
+
+def test_calls_batch_refuses_null_arguments_and_a_context_without_a_device():
+    """gtx_calls_batch: each NULL argument and each NULL accumulator pointer is GTX_ERR_ARG, a device=-1 context GTX_ERR_NO_DEVICE --
+    all of it decided before anything is launched, so no device is needed to see it"""
+    import ctypes as C
+
+    import numpy as np
+
+    import calls_cases as cc
+    L = gtx.lib()
+    ctx = cc.host_ctx("shapes")
+    ls, cov, cu = np.zeros(ctx.total_tri, np.uint32), np.zeros(ctx.total_allele, np.uint32), np.zeros(ctx.n_hap * 4, np.uint32)
+    phred, calls = np.zeros(ctx.total_tri, np.uint8), np.zeros(ctx.n_hap, gtx.SAMPLE_CALL)
+    ptrs = [a.ctypes.data for a in (ls, cov, cu)]
+
+    def buffers(missing=None):
+        return gtx.ScoreBuffers(1, *[None if k == missing else p for k, p in enumerate(ptrs)], None, None, None, None, 0, None, None, 0)
+
+    args = [ctx.h, C.byref(buffers()), phred.ctypes.data, calls.ctypes.data]
+    for k in range(4):
+        assert L.gtx_calls_batch(*[None if j == k else a for j, a in enumerate(args)], None) == 1  # GTX_ERR_ARG
+    for k in range(3):
+        assert L.gtx_calls_batch(ctx.h, C.byref(buffers(missing=k)), phred.ctypes.data, calls.ctypes.data, None) == 1
+    assert L.gtx_calls_batch(*args, None) == 2  # GTX_ERR_NO_DEVICE
+    assert not phred.any() and not calls.view(np.uint8).any()
