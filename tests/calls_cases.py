@@ -401,6 +401,19 @@ def read_result(path, case):
     return raw[:n].copy(), raw[n:].view(gtx.SAMPLE_CALL).copy()
 
 
+def through(run, case):
+    """a case through tests/emu_calls; run(write, read): emu_programs.run with a program and a directory -> (phred, calls)"""
+    return run(lambda path: write_case(path, case), lambda path: read_result(path, case))
+
+
+def judge(name, run):
+    """None when the program behind `run` gives the set `name` as the restatement does, else how it differs"""
+    for case, want in zip(cases(name), expected(name)):
+        if differences(case, want, through(run, case)):
+            return "differs from the restatement"
+    return None
+
+
 # ---- the fact tests: from the expected values, that a set reaches what it is for ------------------------------------------------
 def _cells_with(case, want, kind):
     """(note, phred row, call) of the cells whose note starts with `kind`"""

@@ -645,14 +645,19 @@ LAUNCHES.update(capacity_total=(257, "total", (0, 0), 1), capacity_total_minus_1
                 capacity_0=(257, "0", (0, 0), 1), counters_7_3=(130, "7 + total", (7, 3), 1), two_launches=(130, "2 * total", (0, 0), 2))
 
 
-def judge(name, runner):
-    """runner(part, event_cap, counts, launches) -> (counts, read_out, events).  None when the set or launch-level case `name` comes
-    out as the restatement says, else what differs"""
+def through(run, part, event_cap, counts=(0, 0), launches=1):
+    """a part through tests/emu_disc_events; run(write, read): emu_programs.run with a program and a directory -> (counts, read_out,
+    events)"""
+    return run(lambda path: write_case(path, part, arrays(part), event_cap, counts, launches), lambda path: read_result(path, len(part.reads), event_cap))
+
+
+def judge(name, run):
+    """None when the program behind `run` gives the set or launch-level case `name` as the restatement says, else what differs"""
     try:
         if name in SETS:
             for k, (part, want) in enumerate(zip(parts(name), expected(name))):
                 total = total_events(want)
-                counts, read_out, events = runner(part, total, (0, 0), 1)
+                counts, read_out, events = through(run, part, total)
                 got = per_read(read_out, events)
                 wrong = [i for i in range(len(want)) if got[i] != want[i]]
                 if wrong:
@@ -663,7 +668,7 @@ def judge(name, runner):
         part, want = tiling_part(n_reads), tiling_expected(n_reads)
         total = total_events(want)
         event_cap = eval(cap, dict(total=total))
-        counts, read_out, events = runner(part, event_cap, before, launches)
+        counts, read_out, events = through(run, part, event_cap, before, launches)
         check_launch(want, counts, read_out, events, event_cap, (before[0] + (launches - 1) * total, before[1]))
         return None
     except AssertionError as e:

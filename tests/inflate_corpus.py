@@ -2,11 +2,11 @@
 (test_gpu_bgzf_inflate.py): the corpus of test_inflate.py -- the same generator, seeds and draws -- plus sizes and codes that
 corpus meets only by chance, the hand-made streams, and the damage test_inflate.py applies.  The yardstick is zlib."""
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 
+import emu_programs
 from test_inflate import _data, _deflate
 
 OK, BAD_STREAM, SHORT, LONG, CRC, BAD_MEMBER = range(6)
@@ -136,16 +136,15 @@ def max_code_bits(stream):
     return max(lens)
 
 
-def run_emu(driver, tmp_path, members, in_blob, mode, check_crc=True, out_size=0, fill=0x5A, timeout=600):
+def run_emu(driver, tmp_path, members, in_blob, mode, check_crc=True, out_size=0, fill=0x5A):
     """members: [(in_off, in_len, out_off, out_len, crc32)].  Returns (statuses, output bytes) of tests/emu_inflate."""
-    case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    with open(case, "wb") as f:
-        f.write(struct.pack("<6I", mode, len(members), int(check_crc), len(in_blob), out_size, fill))
-        for m in members:
-            f.write(struct.pack("<5I", *m))
-        f.write(in_blob)
-    subprocess.run([driver, case, out], check=True, timeout=timeout)
-    raw = open(out, "rb").read()
+    def write(path):
+        with open(path, "wb") as f:
+            f.write(struct.pack("<6I", mode, len(members), int(check_crc), len(in_blob), out_size, fill))
+            for m in members:
+                f.write(struct.pack("<5I", *m))
+            f.write(in_blob)
+    raw = emu_programs.run(driver, tmp_path, write, lambda path: open(path, "rb").read())
     return np.frombuffer(raw[:4 * len(members)], np.uint32), raw[4 * len(members):]
 
 

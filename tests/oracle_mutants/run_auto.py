@@ -11,17 +11,14 @@ import argparse
 import json
 import os
 import re
-import shutil
-import subprocess
 import sys
-import tempfile
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-import run_audit  # noqa: E402
+import run_audit  # noqa: E402  (puts tests/ on the path)
+import mutation_audit  # noqa: E402
 
 # (file, first line marker, last line marker): the text between the first line that holds `first` and the first line after it that
 # holds `last` -- the unpinned functions, by what they restate
@@ -86,32 +83,16 @@ def mutants_of(path_rel):
 
 
 def run_one(m):
-    tmp = tempfile.mkdtemp(prefix="gto_auto_")
-    try:
-        work = os.path.join(tmp, "oracle")
-        shutil.copytree(os.path.join(ROOT, "oracle"), work, ignore=shutil.ignore_patterns("*.so", "_ref"))
+    def change(work):
         path = os.path.join(work, m["file"])
         lines = open(path).read().split("\n")
         l = lines[m["line"] - 1]
         assert l[m["col"]:m["col"] + len(m["find"])] == m["find"], m
         lines[m["line"] - 1] = l[:m["col"]] + m["replace"] + l[m["col"] + len(m["find"]):]
         open(path, "w").write("\n".join(lines))
-        so = os.path.join(tmp, "libgto_mutant.so")
-        cc = subprocess.run(["g++", "-std=c++17", "-O1", "-fPIC", "-w", "-shared", "-o", so, os.path.join(work, "gto_capi.cpp")], capture_output=True, text=True)
-        if cc.returncode != 0:
-            return dict(m, status="does not compile")
-        env = dict(os.environ, GTO_LIB=so)
-        try:
-            t = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider"] + run_audit.KILL_SUITE, cwd=ROOT, env=env, capture_output=True,
-                               text=True, timeout=300)
-        except subprocess.TimeoutExpired:
-            return dict(m, status="killed", by="timeout (a loop that no longer ends)")
-        if t.returncode == 0:
-            return dict(m, status="SURVIVED")
-        killers = [x.split(" ")[1] for x in t.stdout.splitlines() if x.startswith("FAILED ") or x.startswith("ERROR ")]
-        return dict(m, status="killed", by=(killers[:1] or ["crash"])[0])
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+
+    status, by = run_audit.changed_oracle(change)
+    return dict(m, status=status, by=by) if status == "killed" else dict(m, status=status)
 
 
 def main():
@@ -139,16 +120,15 @@ def main():
             print(m["id"], m["func"], "|", m["text"])
         print(len(mutants), "mutants")
         return
-    base = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider"] + run_audit.KILL_SUITE, cwd=ROOT, capture_output=True, text=True)
-    if base.returncode != 0:
-        raise SystemExit("the kill suite fails on the unmodified oracle:\n" + base.stdout[-2000:])
+    wrong = run_audit.suite_passes()
+    if wrong is not None:
+        raise SystemExit("the kill suite fails on the unmodified oracle: %s" % wrong)
     t0 = time.time()
     results = []
-    with ThreadPoolExecutor(a.j) as pool:
-        for k, r in enumerate(pool.map(run_one, mutants)):
-            results.append(r)
-            if (k + 1) % 50 == 0:
-                sys.stderr.write("%d / %d  (%.0f s)\n" % (k + 1, len(mutants), time.time() - t0))
+    for k, r in enumerate(mutation_audit.each(run_one, mutants, a.j)):
+        results.append(r)
+        if (k + 1) % 50 == 0:
+            sys.stderr.write("%d / %d  (%.0f s)\n" % (k + 1, len(mutants), time.time() - t0))
     by_file = {}
     for r in results:
         d = by_file.setdefault(r["file"], {}).setdefault(r["func"], dict(mutants=0, killed=0, survived=0, does_not_compile=0))
@@ -175,14 +155,12 @@ def main():
         full["killed"] = sum(c["killed"] for f in full["per_function"].values() for c in f.values())
         full["survived"] = len(full["survivors"])
         full["kill_suite"] = run_audit.KILL_SUITE
-        json.dump(full, open(os.path.join(HERE, "audit_auto.json"), "w"), indent=1)
-        open(os.path.join(HERE, "audit_auto.json"), "a").write("\n")
+        mutation_audit.write_record(os.path.join(HERE, "audit_auto.json"), full)
         print("merged into audit_auto.json: %d killed, %d survived" % (full["killed"], full["survived"]))
     name = "audit_auto.json" if a.every == 1 and not a.limit and not a.lines and not a.ids and len(a.file) == 3 else "audit_auto_partial.json"
     if a.merge:
         name = "audit_auto_partial.json"
-    json.dump(out, open(os.path.join(HERE, name), "w"), indent=1)
-    open(os.path.join(HERE, name), "a").write("\n")
+    mutation_audit.write_record(os.path.join(HERE, name), out)
     print("%d mutants: %d killed, %d survived, %d do not compile  (%.0f s) -> %s" % (out["total"], out["killed"], out["survived"], out["does_not_compile"], time.time() - t0, name))
 
 

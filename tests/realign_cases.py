@@ -484,3 +484,16 @@ def write_case(path, planes, plane_stride, lens, seq, off, pr):
         f.write(off.tobytes())
         f.write(seq.tobytes() + b"\0" * (-len(seq) % 4))
         f.write(pr.tobytes())
+
+
+def through(run, arrays):
+    """what arrays() returns through tests/emu_realign; run(write, read): emu_programs.run with a program and a directory -> the
+    results as tuples"""
+    from graphtyper_amd import lib as gtx
+    return run(lambda path: write_case(path, *arrays), lambda path: as_tuples(np.fromfile(path, gtx.REALIGN_RESULT)))
+
+
+def judge(name, run):
+    """None when the program behind `run` gives the pair set or entry-point case `name` as the restatement does, else how it differs"""
+    arrays, want = case(name)
+    return None if through(run, arrays) == want else "differs from the restatement"

@@ -4,35 +4,26 @@ hand) and the kernel's own text (call_cell, graphtyper_amd/csrc/score_core.hpp) 
 exactly the arrays' sizes under AddressSanitizer / UBSan (tests/emu_calls).  All values are integers; there is no tolerance.
 The device: test_gpu_calls.py.  What the sets notice: test_calls_mutants.py."""
 import decimal
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
 import calls_cases as cc
 import calls_ref as ref
+import emu_programs
 import harness
 import scenarios
 from graphtyper_amd import lib as gtx
 from oracle_lib import Oracle
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
 @pytest.fixture(scope="session")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("emu_calls") / "emu_calls")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_calls"), "-s", "OUT=" + out])
-    return out
+    return emu_programs.build("emu_calls", tmp_path_factory.mktemp("emu_calls"))
 
 
 def run_emu(exe, tmp_path, case):
-    path, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    cc.write_case(path, case)
-    run = subprocess.run([exe, path, out], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=600)
-    assert run.returncode == 0 and run.stderr == b"", run.stderr[-2000:].decode(errors="replace")  # (no sanitizer report)
-    return cc.read_result(out, case)
+    return cc.through(functools.partial(emu_programs.run, exe, tmp_path), case)  # (no sanitizer report, or emu_programs.Died)
 
 
 def test_the_double_product_rounds_like_the_exact_one():

@@ -5,31 +5,23 @@ n_events, pos_end and the events [first_event, first_event + n_events) in order,
 no tolerance.  Every read runs over heap blocks of exactly its sizes, the event buffer has exactly event_cap entries, and there
 is no sanitizer report.  Then the launch-level conditions that need no device: the tiling of the event buffer, its capacity,
 counters that are not zero at entry.  The device: test_gpu_disc_events.py."""
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
 import disc_event_cases as dc
 import disc_events_ref as ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
+import emu_programs
 
 
 @pytest.fixture(scope="session")
 def emu(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("emu_disc_events") / "emu_disc_events")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_disc_events"), "-s", "OUT=" + out])
-    return out
+    return emu_programs.build("emu_disc_events", tmp_path_factory.mktemp("emu_disc_events"))
 
 
 def run_emu(exe, tmp_path, part, event_cap, counts=(0, 0), launches=1):
-    a = dc.arrays(part)
-    case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    dc.write_case(case, part, a, event_cap, counts, launches)
-    subprocess.run([exe, case, out], check=True, stdout=subprocess.DEVNULL, timeout=600)
-    return dc.read_result(out, len(part.reads), event_cap)
+    return dc.through(functools.partial(emu_programs.run, exe, tmp_path), part, event_cap, counts, launches)
 
 
 @pytest.mark.parametrize("name", sorted(dc.SETS))

@@ -4,24 +4,19 @@ corpus is inflated -- none refused, none left out --, its bytes are zlib's and i
 streams are refused or give what zlib gives, without a sanitizer report and within the driver's time limit.  Every member's
 stream and output lie in heap blocks of exactly their sizes.  The device: test_gpu_bgzf_inflate.py."""
 import ctypes as C
-import os
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import emu_programs
 import inflate_corpus as ic
 from graphtyper_amd import lib as gtx
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="session")
 def emu_inflate(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("emu_inflate") / "emu_inflate")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_inflate"), "-s", "OUT=" + out])
-    return out
+    return emu_programs.build("emu_inflate", tmp_path_factory.mktemp("emu_inflate"))
 
 
 def _check_valid(emu, tmp_path, pairs):

@@ -16,6 +16,7 @@ import pytest
 
 import bam_writer as bw
 import deflate_maker as dm
+import emu_programs
 import inflate_corpus as ic
 from graphtyper_amd import lib as gtx
 
@@ -50,8 +51,7 @@ def corpus():
 def drivers(tmp_path_factory):
     """(the emulation of the device decoder, the host decoder's driver), both under ASan / UBSan"""
     d = tmp_path_factory.mktemp("inflate_drivers")
-    emu, host = str(d / "emu_inflate"), str(d / "inflate_driver")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_inflate"), "-s", "OUT=" + emu])
+    emu, host = emu_programs.build("emu_inflate", d), str(d / "inflate_driver")
     subprocess.check_call(["make", "-C", os.path.join(HERE, "sanitize"), "-s", "INFLATE_OUT=" + host, host])
     return emu, host
 

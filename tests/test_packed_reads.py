@@ -3,16 +3,14 @@ against a numpy restatement of the layout, and the unpacking of gtx_packed_kerne
 host emulation under AddressSanitizer (tests/emu_packed) -- against gtx_pack_planes, on well-formed and malformed lists.  The
 device: test_gpu_packed_reads.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_programs
 import scenarios
 from graphtyper_amd import lib as gtx
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ERR_ARG, ERR_NO_DEVICE, ERR_CAPACITY = 1, 2, 5
 LENGTHS = [1, 31, 32, 33, 63, 150, 151, 250, 256, 300, 1000]
 
@@ -24,9 +22,7 @@ def _built():
 
 @pytest.fixture(scope="session")
 def emu_packed(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("emu_packed") / "emu_packed")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_packed"), "-s", "OUT=" + out])
-    return out
+    return emu_programs.build("emu_packed", tmp_path_factory.mktemp("emu_packed"))
 
 
 def tight(length):
@@ -45,16 +41,14 @@ def emulate(exe, tmp_path, rows, exc_start, exc, n_exc, plane_stride):
     """gtx_packed_kernel over (rows, exc_start, exc[:n_exc]) on the host, under ASan: [n, plane_stride] plane rows"""
     rows = np.ascontiguousarray(rows, np.uint8)
     n, packed_stride = rows.shape
-    case, out = tmp_path / "case.bin", tmp_path / "out.bin"
-    with open(case, "wb") as f:
-        f.write(np.array([n, packed_stride, plane_stride, n_exc], np.uint32).tobytes())
-        f.write(rows.tobytes())
-        f.write(np.ascontiguousarray(exc_start, np.uint32).tobytes())
-        f.write(np.ascontiguousarray(exc[:n_exc], np.uint16).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, str(case), str(out)], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return np.fromfile(out, np.uint8).reshape(n, plane_stride)
+
+    def write(path):
+        with open(path, "wb") as f:
+            f.write(np.array([n, packed_stride, plane_stride, n_exc], np.uint32).tobytes())
+            f.write(rows.tobytes())
+            f.write(np.ascontiguousarray(exc_start, np.uint32).tobytes())
+            f.write(np.ascontiguousarray(exc[:n_exc], np.uint16).tobytes())
+    return emu_programs.run(exe, tmp_path, write, lambda path: np.fromfile(path, np.uint8).reshape(n, plane_stride))
 
 
 def masked_codes(planes, lengths):

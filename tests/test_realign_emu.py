@@ -2,32 +2,23 @@
 AddressSanitizer / UBSan (tests/emu_realign), against the plain restatement of the alignment's definition (tests/realign_ref.py):
 every field of every result is equal -- all values are integers, there is no tolerance -- and there is no sanitizer report.
 Every pair within the limits runs over heap blocks of exactly its sizes.  The device: test_gpu_realign.py."""
-import os
-import subprocess
+import functools
 
-import numpy as np
 import pytest
 
+import emu_programs
 import realign_cases as rc
 import realign_ref as rr
-from graphtyper_amd import lib as gtx
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="session")
 def emu_realign(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("emu_realign") / "emu_realign")
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu_realign"), "-s", "OUT=" + out])
-    return out
+    return emu_programs.build("emu_realign", tmp_path_factory.mktemp("emu_realign"))
 
 
 def run_emu(emu, tmp_path, arrays):
     """arrays: what rc.arrays returns"""
-    case, out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    rc.write_case(case, *arrays)
-    subprocess.run([emu, case, out], check=True, stdout=subprocess.DEVNULL, timeout=600)
-    return rc.as_tuples(np.fromfile(out, gtx.REALIGN_RESULT))
+    return rc.through(functools.partial(emu_programs.run, emu, tmp_path), arrays)
 
 
 @pytest.mark.parametrize("name", sorted(rc.SETS) + sorted(rc.ENTRY))

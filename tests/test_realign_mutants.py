@@ -3,59 +3,16 @@ of mutants.json, each noticed by a pair set or an entry-point case of tests/real
 must survive; and a sample is re-run here (build tests/emu_realign against the changed header -- a plain host build of a
 stand-alone program -- and run the case recorded as its killer) so that the record cannot go stale silently.  The full audit:
 python tests/realign_mutants/run_audit.py."""
-import importlib.util
-import json
-import os
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _run_audit():
-    """tests/realign_mutants/run_audit.py under a name of its own (tests/oracle_mutants has a run_audit too)"""
-    spec = importlib.util.spec_from_file_location("realign_run_audit", os.path.join(HERE, "realign_mutants", "run_audit.py"))
-    module = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(module)
-    return module
-
+import mutation_audit
+import realign_cases as rc
+from realign_mutants.run_audit import AUDIT
 
 SAMPLE = ("lane_best_ge", "rows_behind_the_read_pay_nothing", "offsets_out_of_order_pass")
 
 
-def _load():
-    mutants = json.load(open(os.path.join(HERE, "realign_mutants", "mutants.json")))
-    audit = json.load(open(os.path.join(HERE, "realign_mutants", "audit.json")))
-    return mutants, audit
-
-
 def test_the_audit_covers_the_mutants_and_they_die():
-    import realign_cases as rc
-    mutants, audit = _load()
-    res = {r["id"]: r for r in audit["results"]}
-    assert set(res) == {m["id"] for m in mutants} and len(res) == len(mutants) >= 25
-    assert sorted(audit["cases"]) == sorted(list(rc.SETS) + list(rc.ENTRY))  # the audit ran what the tests run
-    text = open(os.path.join(os.path.dirname(HERE), "graphtyper_amd", "csrc", "gtx_realign_dev.hpp")).read()
-    survivors = 0
-    for m in mutants:
-        assert text.count(m["find"]) == 1, "mutant %s no longer applies" % m["id"]
-        assert m["replace"] != m["find"]
-        if m.get("expect") == "survives":
-            assert res[m["id"]]["status"] == "SURVIVED" and m.get("why"), m["id"]
-            survivors += 1
-        else:
-            assert res[m["id"]]["status"] in ("killed", "does not compile"), "mutant %s is not noticed by any case" % m["id"]
-            assert res[m["id"]]["status"] != "killed" or res[m["id"]]["by"] in audit["cases"]
-        assert "build" not in m or m.get("why_build"), m["id"]  # a mutant built with a sanitizer says why it needs one
-    assert audit["total"] == len(mutants) and audit["killed"] == len(mutants) - survivors and survivors <= 4
+    mutation_audit.check_record(AUDIT, cases=list(rc.SETS) + list(rc.ENTRY), floor=25, survivors_ok=lambda n: n <= 4)
 
 
 def test_a_sample_of_the_mutants_is_killed_again():
-    run_audit = _run_audit()
-    mutants, audit = _load()
-    res = {r["id"]: r for r in audit["results"]}
-    killers = [res[mid]["by"] for mid in SAMPLE]
-    assert len(set(killers)) == len(SAMPLE)  # (three different cases)
-    for mid, killer in zip(SAMPLE, killers):
-        r = run_audit.run_one(next(x for x in mutants if x["id"] == mid), [killer])  # (only the recorded killer: a few seconds per mutant)
-        assert r["status"] == "killed" and r["by"] == killer, (mid, r)
-    # ... and the unmodified header, built the same way, passes those very cases
-    assert run_audit.unmodified_passes(killers) is None
+    mutation_audit.check_sample(AUDIT.here, SAMPLE, AUDIT.run_one, AUDIT.unmodified_passes)
