@@ -432,7 +432,8 @@ typedef struct gtx_score_buffers
   uint64_t * d_stat_u64;
   uint32_t * d_stat_u32;
   uint32_t * d_conn_log;
-  uint32_t * d_conn_count; /* [2]: entries appended, entries dropped because conn_cap was reached */
+  uint32_t * d_conn_count; /* [2]: [0] entries claimed -- min([0], conn_cap) of them were appended --, [1] entries dropped because conn_cap
+                            * was reached ([0] - [1] = appended; [0] keeps counting past conn_cap) */
   uint32_t conn_cap;
   uint32_t * d_conn_near;
   /* SV calling (gtx_params::is_sv_graph), optional: the reference-depth track of ReferenceDepth::add_genotype_paths
@@ -445,6 +446,14 @@ typedef struct gtx_score_buffers
   uint32_t ref_depth_len;
 } gtx_score_buffers;
 
+/* What the scorer relies on in d_items and d_records (gtx_align_batch and gtx_stream_push keep it; a caller that makes either by
+ * hand has to): align_index names a read of d_records, sample < acc->n_samples; a record's paths lie within its rec_words words (or in
+ * the arena, GTX_ST_EXTERNAL); every site index of a path is below n_hap and every allele of its mask below the site's hap_cnum --
+ * they index the accumulators unchecked; GTX_REC_HAS_VARIANTS is set exactly when some path carries a site (the first stage reads
+ * that bit, or its copy in d_task_flags, alone: an item none of whose records carries it adds nothing); longest_path_length is the
+ * largest read_end_index - read_start_index + 1 of the record's paths and equals l_qseq only where every path's does (it decides
+ * "clipped", the paths decide "fully aligned": the reference asserts they are one fact, vcf_writer.cpp:509-512); a record without
+ * paths has longest_path_length 0.  n_items = 0 is GTX_OK and touches nothing. */
 int gtx_score_batch(gtx_ctx *, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records,
                     uint32_t rec_words, const gtx_score_buffers * acc, void * stream);
 /* ... with the side array of gtx_align_batch_flags (bytes 2 * align_index + orientation relative to d_task_flags, i.e. the

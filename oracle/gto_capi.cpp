@@ -765,6 +765,119 @@ extern "C"
     return cell;
   }
 
+  // Test infrastructure, no counterpart in the reference: score items over HAND-MADE alignment results, so that the scoring can be
+  // asked about paths no aligner leaves behind a test's reads (tests/score_cases.py).  Items and records are in the library's formats
+  // (include/gtx.h: gtx_score_item, 40 bytes each; the record words of gtx_align_batch, record (read, orientation) at
+  // (2 * read + orientation) * rec_words; big_records: the arena of records with GTX_ST_EXTERNAL, may be NULL).  The GenotypePaths of
+  // each orientation are built from the words -- paths, var_order from the haplotype's order, nums from the masks,
+  // longest_path_length, read_length; the reverse orientation of a read with GTX_FLAG_FORWARD_ONLY is empty -- and go through exactly
+  // what Genotyper::genotype_only runs behind align_read, on the item's meta fields: update_unpaired_read_paths, or update_paths +
+  // get_better_paths, then writer.update_haplotype_scores_geno; a leftover item goes the way finish() takes it.  The product must not
+  // use this.  Returns the number of items, -1 on an error.
+  long gto_genotyper_push_paths(void * p, void const * items, long n_items, uint32_t const * records, uint32_t rec_words, uint32_t const * big_records,
+                                int is_segment_calling)
+  {
+    try
+    {
+      struct Meta
+      {
+        uint32_t align_index;
+        uint16_t flag;
+        uint8_t mapq, score_diff;
+        int32_t pos, isize;
+      };
+      struct Item
+      {
+        Meta first, second;
+        uint32_t sample, kind;
+      };
+      static_assert(sizeof(Item) == 40, "gtx_score_item");
+      Genotyper & G = *static_cast<GenoHandle *>(p)->g;
+      G.writer.par.is_segment_calling = is_segment_calling != 0;
+      auto geno_of = [&](uint32_t const * rec)
+      {
+        uint32_t const n_paths = rec[0] & 0xFFFFu, status = rec[0] >> 16, words = (rec[1] & 0x40000000u) ? 80u : 2u;
+        GenotypePaths gp(0, (rec[1] >> 16) & 0x3FFFu);
+        gp.longest_path_length = rec[1] & 0xFFFFu;
+        uint32_t const * w = (status & 16u) ? big_records + rec[2] : rec + 2;
+        for (uint32_t i = 0; i < n_paths; ++i)
+        {
+          Path path;
+          path.start = w[0];
+          path.end = w[1];
+          path.read_start_index = static_cast<uint16_t>(w[2] & 0xFFFFu);
+          path.read_end_index = static_cast<uint16_t>(w[2] >> 16);
+          path.mismatches = static_cast<uint16_t>(w[3] & 0xFFFFu);
+          uint32_t const n_var = w[3] >> 16;
+          w += 4;
+          for (uint32_t k = 0; k < n_var; ++k, w += 1 + words)
+          {
+            path.var_order.push_back(G.writer.haplotypes.at(w[0]).id);
+            std::set<uint16_t> nums;
+            for (uint32_t a = 0; a < 32 * words; ++a)
+              if ((w[1 + a / 32] >> (a % 32)) & 1u)
+                nums.insert(static_cast<uint16_t>(a));
+            path.nums.push_back(std::move(nums));
+          }
+          gp.paths.push_back(std::move(path));
+        }
+        return gp;
+      };
+      auto both = [&](Meta const & m)
+      {
+        uint32_t const * rec = records + static_cast<uint64_t>(m.align_index) * 2 * rec_words;
+        GenotypePaths fwd = geno_of(rec);
+        GenotypePaths rev = (m.flag & 0x8000u) ? GenotypePaths(0, fwd.read_length) : geno_of(rec + rec_words);
+        return std::pair<GenotypePaths, GenotypePaths>(std::move(fwd), std::move(rev));
+      };
+      auto record_of = [](Meta const & m, uint32_t sample)
+      {
+        ReadRecord r;
+        r.flag = static_cast<uint16_t>(m.flag & 0x7FFFu);
+        r.mapq = m.mapq;
+        r.score_diff = m.score_diff;
+        r.pos = m.pos;
+        r.isize = m.isize;
+        r.sample = static_cast<int>(sample);
+        return r;
+      };
+      Item const * it = static_cast<Item const *>(items);
+      for (long i = 0; i < n_items; ++i, ++it)
+      {
+        auto gp1 = both(it->first);
+        ReadRecord const r1 = record_of(it->first, it->sample);
+        if (it->second.align_index == INVALID_ID)
+        {
+          if (GenotypePaths * sel = update_unpaired_read_paths(gp1, r1))
+            G.writer.update_haplotype_scores_geno(*sel, r1.sample);
+          continue;
+        }
+        update_paths(gp1, r1);
+        if (it->kind & 1u) // Genotyper::finish()
+        {
+          std::pair<GenotypePaths, GenotypePaths> copy(gp1);
+          copy.first.flags ^= (IS_FIRST_IN_PAIR | IS_SEQ_REVERSED);
+          copy.second.flags ^= (IS_FIRST_IN_PAIR | IS_SEQ_REVERSED);
+          auto better = get_better_paths(gp1, copy);
+          if (better.first)
+            G.writer.update_haplotype_scores_geno(*better.first, r1.sample);
+          continue;
+        }
+        auto gp2 = both(it->second);
+        update_paths(gp2, record_of(it->second, it->sample));
+        auto better = get_better_paths(gp1, gp2);
+        if (better.first)
+          G.writer.update_haplotype_scores_geno(better, r1.sample);
+      }
+      return n_items;
+    }
+    catch (std::exception const & e)
+    {
+      g_error = e.what();
+      return -1;
+    }
+  }
+
   // ---- discovery, first pass (gto_discovery.hpp): reads as arrays -> the canonical word stream of the surviving events
   // codes: 4-bit BAM codes of all reads back to back (code_off[n + 1]), qual the same shape, cigar: raw BAM words (cigar_off[n + 1])
   long gto_first_pass(char const * reference, long region_begin, long bucket_size, long n, int32_t const * pos, uint16_t const * flag,

@@ -260,6 +260,19 @@ class OracleGenotyper:
             [np.ascontiguousarray(x, np.uint8) for x in (ambiguous_depth, ambiguous_depth_alt, alt_proper_pair_depth)]
         return int(L.gto_genotyper_set_hap_samples(C.c_void_p(self.g), *[_p(x) for x in a]))
 
+    def push_paths(self, items, records, rec_words, big_records=None, is_segment_calling=False):
+        """gto_genotyper_push_paths: score items (gtx.SCORE_ITEM) over hand-made records in the library's record format -- the
+        GenotypePaths are built from the words and go through what genotype_only runs behind align_read"""
+        L = lib()
+        L.gto_genotyper_push_paths.restype = C.c_long
+        L.gto_genotyper_push_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int]
+        items = np.ascontiguousarray(items)
+        assert items.dtype.itemsize == 40
+        records = np.ascontiguousarray(records, np.uint32)
+        big = None if big_records is None else np.ascontiguousarray(big_records, np.uint32)
+        if L.gto_genotyper_push_paths(C.c_void_p(self.g), _p(items), len(items), _p(records), rec_words, _p(big), int(is_segment_calling)) != len(items):
+            raise RuntimeError(L.gto_last_error().decode())
+
     def phase_flags(self):
         """rows (hap1, allele1, hap2, allele2, flags) of the `ph` map (gto_phase_flags)"""
         L = lib()
