@@ -3018,21 +3018,8 @@ static int replay_collect(gtx_ctx * c, ScoreRequest const & r, std::vector<Repla
   std::vector<uint32_t> cells(4 * n_cells);
   if (!hip_ok(hipMemcpy(cells.data(), acc->d_hap_u32, cells.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "cells"))
     return GTX_ERR_HIP;
-  std::vector<uint32_t> marked((n_cells + 31) / 32, 0u);
-  uint64_t n_marked = 0;
-  for (uint64_t cell = 0; cell < n_cells; ++cell)
-  {
-    uint32_t const m = cells[4 * cell];
-    if ((m & GTX_CELL_REPLAYED) || m < SATURATION_GUARD)
-      continue;
-    if (g.ref_nvar[cell % g.n_hap] > 64) // (the log keeps 64-bit explain sets)
-    {
-      ++unsupported;
-      continue;
-    }
-    marked[cell >> 5] |= 1u << (cell & 31u);
-    ++n_marked;
-  }
+  std::vector<uint32_t> marked;
+  uint64_t const n_marked = mark_cells_at_guard(g, cells.data(), n_cells, marked, unsupported);
   if (n_marked == 0 || n_items == 0)
     return GTX_OK;
   ScratchHold hold{*c, scratch_acquire(*c, st), st, false};

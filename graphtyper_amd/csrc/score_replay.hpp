@@ -25,6 +25,32 @@ struct ReplayedCell
   std::vector<uint32_t> log_score; // the cell's genotype triangle
 };
 
+// Which cells have to be replayed.  hap_u32: the four words of every cell (word 0: max_log_score and the mark), n_cells = n_samples *
+// n_hap.  marked: a bitmap of (n_cells + 31) / 32 words, bit cell & 31 of word cell >> 5 set for every cell whose sum stands at the
+// guard and was not replayed yet; unsupported: such cells on a site of more than 64 alleles (the log keeps 64-bit explain sets), left
+// out of the bitmap.  Returns the number of marked cells.
+inline uint64_t mark_cells_at_guard(HostGraph const & g, uint32_t const * hap_u32, uint64_t n_cells, std::vector<uint32_t> & marked,
+                                    uint64_t & unsupported)
+{
+  marked.assign((n_cells + 31) / 32, 0u);
+  unsupported = 0;
+  uint64_t n_marked = 0;
+  for (uint64_t cell = 0; cell < n_cells; ++cell)
+  {
+    uint32_t const m = hap_u32[4 * cell];
+    if ((m & GTX_CELL_REPLAYED) || m < SATURATION_GUARD)
+      continue;
+    if (g.ref_nvar[cell % g.n_hap] > 64)
+    {
+      ++unsupported;
+      continue;
+    }
+    marked[cell >> 5] |= 1u << (cell & 31u);
+    ++n_marked;
+  }
+  return n_marked;
+}
+
 // log: the entries of the marked cells in any order.  n_hap, ref_nvar: the graph's sites.
 inline std::vector<ReplayedCell> replay_cells(HostGraph const & g, std::vector<ReplayEntry> & log)
 {

@@ -759,7 +759,13 @@ int gtx_comm_destroy(void * comm);
  * Call it after the last gtx_score_batch of a region (single process: with reads sharded over several GPUs the call order
  * is spread over the ranks) and before gtx_calls_batch / downloading.  n_replayed: cells replayed; n_unsupported: cells at
  * the guard that lie on a site of more than 64 alleles (left as they are, reported by gtx_scores_finalize).  Synchronises
- * with `stream`. */
+ * with `stream`.
+ * What the tests pin (tests/replay_cases.py): "at the guard" is a sum of 0xFFFF - 8 = 65 527 or more -- a cell at exactly 65 527 is
+ * replayed (every call of it is accepted: the row stays, the mark is set), one at 65 526 is not touched; a replayed cell carries
+ * bit 31 in d_hap_u32[cell * 4] and a second call leaves it alone; nothing but that word and the cell's d_log_score row is
+ * written; a cell at the guard that none of the items touches keeps its sum and no mark, and gtx_scores_finalize reports it; a
+ * site of exactly 64 alleles is replayed (bits 31, 32 and 63 of the explain set included), one of more than 64 is not (tested on a
+ * site of 100 alleles). */
 int gtx_scores_replay(gtx_ctx *, const gtx_score_item * d_items, uint32_t n_items, const uint32_t * d_records, uint32_t rec_words,
                       const gtx_score_buffers * acc, void * stream, uint64_t * n_replayed, uint64_t * n_unsupported);
 /* ... over the records of gtx_align_batch_planes_compact (a pair's mate without a variant site has its record there) */
@@ -775,7 +781,10 @@ int gtx_scores_replay_compact(gtx_ctx *, const gtx_score_item * d_items, uint32_
  * small); d_compact / d_task_flags: NULL, or the dense records of gtx_align_batch_planes_compact.  The hosts exchange the logs
  * (they are plain data: an all-gather of bytes), and gtx_scores_replay_apply -- on the rank(s) that go on to gtx_calls_batch --
  * replays the entries of ALL ranks in call order and stores the exact rows into its block, as gtx_scores_replay does for one
- * process.  Both synchronise with `stream`. */
+ * process.  Both synchronise with `stream`.  item_base + the item's index has to fit 32 bits (`item` is the sort key; it is not
+ * checked).  gtx_scores_replay_log writes nothing to `acc`; cap = 0 with out = NULL asks for the count alone.
+ * gtx_scores_replay_apply takes the entries in any order; one that names a cell the block does not have (cell >= n_samples *
+ * n_hap) or a cell on a site of more than 64 alleles is GTX_ERR_ARG, and nothing is written. */
 typedef struct gtx_replay_entry
 {
   uint32_t item, cell;       /* place in the region's item sequence; sample * n_hap + haplotype */

@@ -697,16 +697,9 @@ extern "C"
     Emu & e = *static_cast<Emu *>(p);
     GraphView const g = e.graph.view();
     uint64_t const n_cells = static_cast<uint64_t>(acc->n_samples) * e.graph.n_hap;
-    std::vector<uint32_t> marked((n_cells + 31) / 32, 0u);
-    uint64_t n_marked = 0;
-    for (uint64_t cell = 0; cell < n_cells; ++cell)
-    {
-      uint32_t const m = acc->d_hap_u32[4 * cell];
-      if ((m & GTX_CELL_REPLAYED) || m < SATURATION_GUARD || e.graph.ref_nvar[cell % e.graph.n_hap] > 64)
-        continue;
-      marked[cell >> 5] |= 1u << (cell & 31u);
-      ++n_marked;
-    }
+    std::vector<uint32_t> marked;
+    uint64_t unsupported = 0;
+    uint64_t const n_marked = mark_cells_at_guard(e.graph, acc->d_hap_u32, n_cells, marked, unsupported);
     if (n_marked == 0)
       return 0;
     std::vector<ReplayEntry> log(1u << 22);
@@ -729,11 +722,17 @@ extern "C"
     a.replay_cap = static_cast<uint32_t>(log.size());
     ScoreParams par{static_cast<uint32_t>(e.params.is_sv_graph != 0), static_cast<uint32_t>(e.params.hq_reads != 0),
                     static_cast<uint32_t>(e.params.is_segment_calling != 0), 0};
-    std::vector<RecentHap> large(2 * SCORE_MAX_HAPS_BIG);
+    // the tables of the second scoring pass, as the library's replay takes them: the wide ones on a graph with a site of more than 64 alleles
+    bool has_wide_sites = false;
+    for (uint32_t n : e.graph.ref_nvar)
+      has_wide_sites = has_wide_sites || n > 64;
+    std::vector<RecentHap> large(has_wide_sites ? 0 : 2 * SCORE_MAX_HAPS_BIG);
+    std::vector<RecentHapWide> wide_tables(has_wide_sites ? 2 * SCORE_MAX_HAPS_WIDE : 0);
     for (uint32_t i = 0; i < n_items; ++i)
     {
       a.replay_item = i;
-      if (!score_item<WaveEmu>(g, par, items[i], records, rec_words, a, large.data(), large.data() + SCORE_MAX_HAPS_BIG, SCORE_MAX_HAPS_BIG))
+      if (has_wide_sites ? !score_item<WaveEmu>(g, par, items[i], records, rec_words, a, wide_tables.data(), wide_tables.data() + SCORE_MAX_HAPS_WIDE, SCORE_MAX_HAPS_WIDE)
+                         : !score_item<WaveEmu>(g, par, items[i], records, rec_words, a, large.data(), large.data() + SCORE_MAX_HAPS_BIG, SCORE_MAX_HAPS_BIG))
         return -1;
     }
     if (count > log.size() || static_cast<long>(count) > cap)

@@ -69,7 +69,7 @@ class EmuBackend:
             raise RuntimeError(err.value.decode())
 
     def __del__(self):
-        if getattr(self, "h", None):
+        if getattr(self, "h", None) and C is not None:  # (at interpreter exit the module's globals may be gone already)
             self.L.emu_free(C.c_void_p(self.h))
             self.h = None
 
@@ -118,11 +118,11 @@ class EmuBackend:
         assert n >= 0
         return int(n)
 
-    def score_replay_log(self, items, records, acc, item_base=0, rec_words=REC_WORDS):
+    def score_replay_log(self, items, records, acc, item_base=0, rec_words=REC_WORDS, cap=1 << 20):
         """gtx_scores_replay_log on host arrays: this rank's entries (gtx.REPLAY_ENTRY) for the cells at the guard of `acc`"""
         items = np.ascontiguousarray(items, gtx.SCORE_ITEM)
         buf = acc.buffers([_p(a) for a in acc.arrays()])
-        out = np.zeros(1 << 20, gtx.REPLAY_ENTRY)
+        out = np.zeros(cap, gtx.REPLAY_ENTRY)
         self.L.emu_score_replay_log.restype = C.c_long
         n = self.L.emu_score_replay_log(C.c_void_p(self.h), _p(items), C.c_uint32(len(items)), _p(records), C.c_uint32(rec_words), C.byref(buf),
                                         C.c_uint32(item_base), _p(out), C.c_long(len(out)))

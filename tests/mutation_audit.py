@@ -69,12 +69,20 @@ class KernelAudit:
     """the audit of one kernel's text.  here: the directory of mutants.json and audit.json; header: the file under
     graphtyper_amd/csrc that is changed; emu: its emulation's directory under tests/; cases: the case module -- judge(name, run)
     -> None or how the case differs, with run(write, read) of emu_programs.run --; order: the cases, the cheap ones first, so that
-    a mutant's recorded killer is quick to run again; covers: the names the tests run, every one of which `order` has to hold"""
+    a mutant's recorded killer is quick to run again; covers: the names the tests run, every one of which `order` has to hold;
+    also: further headers of the emulation that a mutant may name as its "header" (all of them are copied beside the changed one)"""
 
-    def __init__(self, here, header, emu, cases, order, covers):
+    def __init__(self, here, header, emu, cases, order, covers, also=()):
         assert sorted(order) == sorted(covers), sorted(set(order) ^ set(covers))
         self.here, self.emu, self.cases, self.order = here, emu, cases, list(order)
         self.header = os.path.join(ROOT, "graphtyper_amd", "csrc", header)
+        self.also = [os.path.join(ROOT, "graphtyper_amd", "csrc", h) for h in also]
+
+    def header_of(self, mutant):
+        """the file a mutant changes: the audit's header, or the one of `also` it names"""
+        path = os.path.join(os.path.dirname(self.header), mutant.get("header", os.path.basename(self.header)))
+        assert path in [self.header] + self.also, path
+        return path
 
     def build(self, csrc, out, san=""):
         """the emulation against the header in `csrc`, into the directory `out` -> (program, None), or (None, the compiler's last words)"""
@@ -97,8 +105,9 @@ class KernelAudit:
 
     def run_one(self, mutant, names=None):
         with tempfile.TemporaryDirectory(prefix="gtx_%s_mutant_" % self.emu) as tmp:
-            with open(os.path.join(tmp, os.path.basename(self.header)), "w") as f:
-                f.write(changed(open(self.header).read(), mutant))
+            for path in [self.header] + self.also:
+                with open(os.path.join(tmp, os.path.basename(path)), "w") as f:
+                    f.write(changed(open(path).read(), mutant) if path == self.header_of(mutant) else open(path).read())
             exe, error = self.build(tmp, tmp, mutant.get("build", ""))
             if error is not None:
                 return dict(id=mutant["id"], status="does not compile", detail=error)
@@ -139,9 +148,9 @@ def check_record(audit, cases, floor, survivors_ok, required=frozenset()):
     res = {r["id"]: r for r in record["results"]}
     assert set(res) == {m["id"] for m in mutants} >= set(required) and len(res) == len(mutants) >= floor
     assert sorted(record["cases"]) == sorted(cases)  # the audit ran what the tests run
-    text = open(audit.header).read()
     survivors = 0
     for m in mutants:
+        text = open(audit.header_of(m)).read()
         assert text.count(m["find"]) == 1, "mutant %s no longer applies" % m["id"]
         assert m["replace"] != m["find"]
         if m.get("expect") == "survives":

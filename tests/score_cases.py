@@ -7,7 +7,8 @@ The graph (gtx.graph_from_records): sites 0..19 lie 8 positions apart and have 2
 site 20 has 7 alleles, site 21 has 64, sites 22..25 are SNPs at 700, 795 (3 alleles), 800 and 1000: 23 is the last near site of 22
 and 24 the first far one.  A record's positions only have to satisfy what the scorer reads of them (the reference reach of a path's
 two ends against the order of its sites), so a path is placed around its sites, not aligned to the sequence.
-No set brings a cell's max_log_score to 0xFFFF - 8 (the guard of explain_to_score: gtx_scores_replay is not part of this)."""
+No set here brings a cell's max_log_score to 0xFFFF - 8 (the guard of explain_to_score): the item orders that do, and gtx_scores_replay
+over them, are tests/replay_cases.py."""
 import collections
 from fractions import Fraction
 import functools
@@ -935,8 +936,9 @@ def oracle_scores(case, items):
 
 
 # ---- case files of tests/emu_score --------------------------------------------------------------------------------------------------
-def write_case(path, case, items, cap, compact=None):
-    """see tests/emu_score/emu_score.cpp.  compact: the compact reads' forward records in d_compact (None: where the case has any)"""
+def write_case(path, case, items, cap, compact=None, log_cap=0):
+    """see tests/emu_score/emu_score.cpp.  compact: the compact reads' forward records in d_compact (None: where the case has any);
+    log_cap: the first log block of tests/emu_replay"""
     ctx = ctx_of(case)
     f = facts_of(case)
     g = ctx.g
@@ -949,7 +951,7 @@ def write_case(path, case, items, cap, compact=None):
     with open(path, "wb") as fh:
         fh.write(struct.pack("<16I", n_ref, f.n_hap, len(f.special_ref_reach), case.n_samples, case.rec_words, case.n_reads, len(items), cap,
                              int(case.near), int(case.par.is_sv_graph), int(case.par.hq_reads), int(case.par.is_segment_calling), int(compact), len(big),
-                             int(max(f.hap_cnum) > 64), 0))
+                             int(max(f.hap_cnum) > 64), log_cap))
         fh.write(struct.pack("<3Q", f.total_tri, f.total_allele, f.total_near))
         for name in ("ref_order", "ref_len", "ref_nvar"):
             fh.write(np.ascontiguousarray(g[name], np.uint32).tobytes())
@@ -962,7 +964,8 @@ def write_case(path, case, items, cap, compact=None):
         fh.write(big.tobytes())
 
 
-def read_result(path, case, cap):
+def read_result(path, case, cap, more=None):
+    """more: what parses the bytes behind emu_score's own (tests/emu_replay writes some) -> Got.more"""
     f = facts_of(case)
     raw = np.fromfile(path, np.uint8)
     sizes = ref.Sums(f, case.n_samples).sizes()
@@ -978,7 +981,10 @@ def read_result(path, case, cap):
     at += cap * 24
     arrays["conn_count"] = raw[at:at + 8].view(np.uint32).copy()
     arrays["errors"] = int(raw[at + 8:at + 12].view(np.uint32)[0])
-    assert at + 12 == len(raw)
+    if more is None:
+        assert at + 12 == len(raw)
+    else:
+        arrays["more"] = more(raw[at + 12:])
     return Got(**arrays)
 
 

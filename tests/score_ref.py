@@ -13,7 +13,7 @@ it), which it is there to judge.
   push_to_haplotype_scores          src/typer/vcf_writer.cpp:503-676
   Haplotype::add_coverage           src/graph/haplotype.cpp:180-227
   *_to_stats, coverage_to_gts       src/graph/haplotype.cpp:229-361
-  Haplotype::explain_to_score       src/graph/haplotype.cpp:462-585       (without the guard at :561: sums below it are what is compared)
+  Haplotype::explain_to_score       src/graph/haplotype.cpp:462-585       (score(): without the guard at :560; replay(): the guard, call by call)
   Graph::get_ref_reach_pos          src/graph/graph.cpp:1784-1795
   the leftover read                 src/utilities/hts_parallel_reader.cpp:719-745
 
@@ -27,7 +27,7 @@ Contract of a record (what the aligner leaves and a hand-made record has to keep
 asserts at :512 that "the longest path is the read" and "every path is the read" are one fact; a record where they differ is refused here); every site index is below
 n_hap and every allele of a mask below the site's number of alleles; bit 31 of word 1 says whether some path carries a site (a
 record that has sites and does not say so adds nothing: the scorer's first stage reads that bit alone).
-Out of scope: gtx_scores_replay*, the reference-depth track of SV calling, records with GTX_REC_WIDE sets only through
+Out of scope: the reference-depth track of SV calling, records with GTX_REC_WIDE sets only through
 big_records()."""
 import collections
 from fractions import Fraction
@@ -409,7 +409,7 @@ def score(facts, par, records, rec_words, items, n_samples, multiplicity=None, b
         first, second = _Meta(it["first"]), _Meta(it["second"])
         sample, kind = int(it["sample"]), int(it["kind"])
         note = dict(kind="single" if second.align_index == INVALID else "leftover" if kind & ITEM_LEFTOVER else "pair", which=None, rule=None,
-                    trivial=False, reads=[])
+                    trivial=False, reads=[], sample=sample)
         sums.items.append(note)
         assert sample < n_samples
         if k == 0:
@@ -492,3 +492,61 @@ def score(facts, par, records, rec_words, items, n_samples, multiplicity=None, b
             for h2, b2 in targets:
                 sums.connection(sample, h1, b1, h2, b2, 1, k, near)
     return sums
+
+
+# ---- the guard, call by call -------------------------------------------------------------------------------------------------------
+SATURATION_GUARD = 0xFFFF - 8   # explain_to_score refuses a call when max_log_score >= 0xFFFF - epsilon, and epsilon <= 8
+Replayed = collections.namedtuple("Replayed", "head rows marked unsupported log beyond")
+
+
+def replay(sums, sequence, item_base=0):
+    """Haplotype::explain_to_score with its guard (haplotype.cpp:560-584) over the items `sequence` -- indices into the distinct items
+    that `sums` = score(...) was made of, with multiplicity = how often each occurs in the sequence -- in the order the reference makes
+    the calls: item by item; within an item the first read of the better pair, then the second (vcf_writer.cpp:170-184; the one-read
+    overload :88-141 and the leftover read make one call per site); within a read one call per site, each on a cell of its own.
+      head[cell]    max_log_score with the guard, cell = sample * n_hap + site, for every cell that was added to
+      rows[cell]    the guarded genotype triangle (entry y (y + 1) / 2 + x) of every marked cell
+      marked        the cells whose unguarded sum is >= 0xFFFF - 8 on a site of at most 64 alleles; unsupported: those on a larger site
+      log           (item + item_base, cell, order, epsilon, mask) of every call on a marked cell: order = which read of the item
+      beyond[cell]  (max_log_score, triangle) with the guard of every unsupported cell: what the reference has there (not in the log)
+    A cell whose unguarded sum stays below 0xFFFF - 8 never had a call refused: max_log_score only grows, so before every call it was
+    below 0xFFFF - 8 <= 0xFFFF - epsilon; its guarded values are the sums of score() and it is not walked."""
+    f = sums.facts
+    nh = f.n_hap
+    head = {i // 4: v for i, v in sums.hap_u32.items() if i % 4 == 0}
+    at_guard = {cell for cell, v in head.items() if v >= SATURATION_GUARD}
+    marked = {cell for cell in at_guard if f.hap_cnum[cell % nh] <= 64}
+    calls = []  # per distinct item: its calls on marked cells (cell, order, epsilon, mask, addends of the triangle)
+    for note in sums.items:
+        mine = []
+        for order, read in enumerate(note["reads"]):
+            for x in read["sites"]:
+                cell = note["sample"] * nh + x["site"]
+                if cell not in at_guard:
+                    continue
+                eps, explains, adds, i = x["eps"], x["explains"], [], 0
+                for y in range(f.hap_cnum[x["site"]]):           # haplotype.cpp:566-583
+                    for xx in range(y + 1):
+                        if xx in explains and y in explains:
+                            adds.append((i, eps))
+                        elif xx in explains or y in explains:
+                            adds.append((i, eps - 1))
+                        i += 1
+                mine.append((cell, order, eps, sum(1 << a for a in explains), adds))
+        calls.append(mine)
+    state = {cell: [0, [0] * (f.hap_cnum[cell % nh] * (f.hap_cnum[cell % nh] + 1) // 2)] for cell in at_guard}
+    log = []
+    for pos, d in enumerate(sequence):
+        for cell, order, eps, mask, adds in calls[d]:
+            if cell in marked:
+                log.append((pos + item_base, cell, order, eps, mask))
+            st = state[cell]
+            if st[0] < 0xFFFF - eps:                             # haplotype.cpp:560
+                st[0] += eps
+                row = st[1]
+                for i, v in adds:
+                    row[i] += v
+    for cell in marked:
+        head[cell] = state[cell][0]
+    return Replayed(head, {cell: state[cell][1] for cell in marked}, marked, at_guard - marked, log,
+                    {cell: tuple(state[cell]) for cell in at_guard - marked})
