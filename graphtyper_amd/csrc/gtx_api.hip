@@ -2229,8 +2229,10 @@ static int align_front(AlignCall & a)
     bool const hint_dense = hb && hb[0] == 'd' ? true : hb && hb[0] == 'l' ? false : c->express4_wide;
     bool const hint_long = r.seq_stride > HintGeom<AlignCfg::KC>::ROW_BYTES; // (rows for reads of more than 160 bases: the eight-k-mer build)
     uint32_t const hint_threads = 64u * ((hint_long || hint_dense) ? GTX_HINT_WAVES : GTX_HINT_WAVES_LEAN);
+    IndexView hint_index = c->dev_index;
+    hint_index.hint_less = hint_less_from_env(); // (A/B switch GTX_HINT_MORE=0: the pass declines what it declined before it learnt more shapes)
     hipLaunchKernelGGL(hint_long ? gtx_align_hinted_long_kernel : hint_dense ? gtx_align_hinted_dense_kernel : gtx_align_hinted_kernel,
-                       dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, r.stream, c->dev_graph, c->dev_index, r.seq, r.seq_stride,
+                       dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, r.stream, c->dev_graph, hint_index, r.seq, r.seq_stride,
                        r.meta, n, r.records, r.rec_words, force_both, s->d_queue1.get(), s->d_queue.get(), reinterpret_cast<unsigned long long *>(counters + 2),
                        static_cast<uint32_t>(force != 0 || (eh && eh[0] == 'd')) | (sv_skips_express ? 4u : 0u)
 #ifdef GTX_PROF

@@ -162,7 +162,9 @@ struct IndexView
   const uint2_t * pos_flags;
   const uint2_t * tail_info;
   const uint32_t * filt[2];
-  uint32_t hint_first, n_hint, filt_log2 /* log2 of the number of words */, pad_hint;
+  // hint_less (A/B switch GTX_HINT_MORE=0, hint_less_from_env): nonzero = the pass declines the shapes it learnt to prove last
+  //   (k-mers with several ambiguous bases, twin chains over another allele: hinted.hpp) as it did before
+  uint32_t hint_first, n_hint, filt_log2 /* log2 of the number of words */, hint_less;
   // ---- allele windows (dense build of the pass).  A read that carries another allele than the reference's at a site does not
   // lie on the linear reference; for the alternative alleles of the sites where that matters (HintWindow) the three tables
   // above continue, behind position win_base, with one window of HINT_WIN_STRIDE positions per (site, allele): the
@@ -250,6 +252,13 @@ inline uint32_t hint_filter_log2_words(uint64_t n_keys)
   if (char const * e = std::getenv("GTX_FILTER_BITS_LOG2"))
     extra = static_cast<uint32_t>(std::max(5, std::min(9, std::atoi(e))) - 5);
   return std::min<uint32_t>(fl + extra, 28u);
+}
+
+// IndexView::hint_less from the environment (GTX_HINT_MORE=0: A/B switch, read where the view is handed to the pass)
+inline uint32_t hint_less_from_env()
+{
+  char const * e = std::getenv("GTX_HINT_MORE");
+  return e && e[0] == '0' ? 1u : 0u;
 }
 
 // the half at bit j (what a read in plane form yields with two shifts) -> (word, mask of up to four bits) of the blocked

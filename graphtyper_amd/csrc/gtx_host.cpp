@@ -609,6 +609,7 @@ IndexView HostIndex::view(uint32_t max_index_labels, uint32_t half_bucket_cap) c
   ix.hint_first = hint_first;
   ix.n_hint = n_hint;
   ix.filt_log2 = filt_log2;
+  ix.hint_less = hint_less_from_env();
   ix.win = win.data();
   ix.site_win = site_win.data();
   ix.win_base = win_base;

@@ -374,6 +374,15 @@ GTX_DEV uint32_t hk_make(uint32_t kind, uint32_t site, uint32_t allele, bool mm,
 // caller probes the filters for all k-mers at once -- one memory round trip instead of one per k-mer -- and turns the
 // verdict into a decline when a needed half may occur.
 constexpr uint32_t HK_NEED_LEFT = 64u, HK_NEED_RIGHT = 128u;
+// `amb2`, bits 8 and up (HS_*): what hint_kmer_judge knows about a k-mer it declined for two or three ambiguous bases that none
+// of its rules settles -- the caller decides that k-mer once per read (hinted_on_path), outside the five copies of the judge:
+// the k-mer, whether its first / last 16 bases are the judged key's alone (HINT_L1 / R1, HINT_FAR_*, or a SNP's group),
+// HINT_NEAR_FREE, the half a SNP under the k-mer lies in (0 first, 1 last, 2 none), whether a half holds a substitution, the
+// ambiguous bases of each half, whether a set misses the reference base, the allele the read carries; HS_MANY: a second such
+// k-mer (the read is sent on).  (Shifts and minima, not comparisons: the judge runs five times in every wavefront.)
+constexpr uint32_t HS_SHIFT = 8u, HS_VALID = 1u, HS_KMER_SHIFT = 1u, HS_GL = 1u << 4, HS_GR = 1u << 5, HS_NEAR = 1u << 6, HS_SNP_HALF_SHIFT = 7u,
+                   HS_SUBST_LEFT = 1u << 9, HS_SUBST_RIGHT = 1u << 10, HS_AMB_LEFT_SHIFT = 11u, HS_AMB_RIGHT_SHIFT = 13u,
+                   HS_SET_MISSES = 1u << 15, HS_ALLELE_SHIFT = 16u, HS_MANY = 1u << 18;
 
 template <uint32_t I, bool DENSE, class Row, class Counts>
 GTX_DEV uint32_t hint_kmer_judge(uint2_t const f, Row row, Counts const & h, uint32_t & amb2) // (Counts: HintCounts, or hinted_long.hpp's for eight k-mers)
@@ -461,7 +470,7 @@ GTX_DEV uint32_t hint_kmer_judge(uint2_t const f, Row row, Counts const & h, uin
     uint32_t const amb_far = site_left ? amb_right : amb_left, mis_far = site_left ? mis_right : mis_left;
     if (amb_far != 0 || amb > 1)
     {
-      GTX_HINT_NOTE(7);
+      GTX_HINT_NOTE(71); // an ambiguity code on the SNP and further ambiguous bases
       return declined;
     }
     if (mis == 0)
@@ -526,8 +535,19 @@ GTX_DEV uint32_t hint_kmer_judge(uint2_t const f, Row row, Counts const & h, uin
   }
   if (amb > 1)
   {
-    GTX_HINT_NOTE(7);
-    return declined;
+    GTX_HINT_NOTE(72); // two or three ambiguous bases, neither half provably the judged key's alone
+    if constexpr (std::is_same<Counts, HintCounts>::value) // (the builds for five k-mers)
+      if (amb <= 3u) // (up to 64 keys: under the 97 behind which to_uint64_vec gives a list up, type_conversions.cpp:217)
+      {
+        uint32_t const off = (f.x & HINT_ALT_OK) != 0 ? (f.y >> HINT_SNPOFF_SHIFT) & 31u : 32u; // (32: no SNP under the k-mer)
+        auto one = [](uint32_t n) { return n < 1u ? n : 1u; };
+        uint32_t const w = HS_VALID | (I << HS_KMER_SHIFT) | (GL(mis + amb) ? HS_GL : 0u) | (GR(mis + amb) ? HS_GR : 0u) |
+                           ((f.y >> 31) * HS_NEAR) | ((off >> 4) << HS_SNP_HALF_SHIFT) | (one(mis_left) * HS_SUBST_LEFT) | (one(mis_right) * HS_SUBST_RIGHT) |
+                           (amb_left << HS_AMB_LEFT_SHIFT) | (amb_right << HS_AMB_RIGHT_SHIFT) | (one(amb_out) * HS_SET_MISSES) | (allele << HS_ALLELE_SHIFT);
+        static_assert(HINT_NEAR_FREE == 1u << 31, "bit 31 of the second flag word");
+        amb2 |= ((amb2 >> HS_SHIFT) != 0 ? HS_MANY : w) << HS_SHIFT;
+      }
+    return declined | own_set; // (own_set: kept for hinted_on_path; nobody looks at the sets of a declined verdict)
   }
   // the k-mer is not K: a half without a difference is K's own -- nobody but K (or the SNP's allele keys) may have it
   // (flag), or nobody near enough to K (HINT_FAR_*) --, a half with one must occur in no indexed key (filter probe by the caller)
@@ -833,7 +853,47 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
   uint32_t k4 = n_k > 4 ? hint_kmer<4, DENSE>(f4, row, h, amb2) : none;
   if ((k0 & 3u) == HINT_K_DECLINE || (k1 & 3u) == HINT_K_DECLINE || (k2 & 3u) == HINT_K_DECLINE || (k3 & 3u) == HINT_K_DECLINE ||
       (k4 & 3u) == HINT_K_DECLINE)
-    return false;
+  {
+    // (a read on its way out: a wavefront without a lane that has a k-mer with several ambiguous bases, six in seven, never gets
+    //  past the first line)
+    // A k-mer with two or three ambiguous bases that hint_kmer_judge declined (HS_*), when it is the read's only declined k-mer.
+    // It brings a multi-key list, exact lookups only (kmer_help_functions.cpp:97-119).  Take the half H without a substitution.
+    // When it holds no ambiguous base either, every key of the list carries it unchanged; when it holds exactly one, its
+    // variants are the half of the key the read is judged against or a 16-mer one substitution away from that, and
+    // HINT_NEAR_FREE says the second kind occurs in no indexed key.  The flag of H says that key alone -- or, on the far side of a
+    // SNP, the SNP's allele keys, which differ on the site, where the read has one base -- has the first kind.  So of the list
+    // only that key can be indexed: it is none of the list's when the other half holds a substitution (no label), and it is in
+    // the list when every set holds its base.  HINT_NEAR_FREE speaks of the REFERENCE k-mer's halves: a half with a SNP in it
+    // is not asked (the read may carry another allele there; the flag is clear at such a place anyway -- the other allele's
+    // half is indexed).  An ambiguity code or a foreign base ON the SNP was decided in hint_kmer_judge.
+    uint32_t const sv = amb2 >> HS_SHIFT;
+    if (sv == 0 || (sv & HS_MANY) != 0 || ix.hint_less != 0) // (hint_less: A/B switch GTX_HINT_MORE=0)
+      return false;
+    uint32_t const n_declined = ((k0 & 3u) == HINT_K_DECLINE ? 1u : 0u) + ((k1 & 3u) == HINT_K_DECLINE ? 1u : 0u) + ((k2 & 3u) == HINT_K_DECLINE ? 1u : 0u) +
+                                ((k3 & 3u) == HINT_K_DECLINE ? 1u : 0u) + ((k4 & 3u) == HINT_K_DECLINE ? 1u : 0u);
+    uint32_t const amb_l = (sv >> HS_AMB_LEFT_SHIFT) & 3u, amb_r = (sv >> HS_AMB_RIGHT_SHIFT) & 3u;
+    bool const near = (sv & HS_NEAR) != 0;
+    uint32_t const snp_half = (sv >> HS_SNP_HALF_SHIFT) & 3u;
+    bool const left_known = (sv & HS_SUBST_LEFT) == 0 && (sv & HS_GL) != 0 && (amb_l == 0 || (amb_l == 1 && near && snp_half != 0));
+    bool const right_known = (sv & HS_SUBST_RIGHT) == 0 && (sv & HS_GR) != 0 && (amb_r == 0 || (amb_r == 1 && near && snp_half != 1));
+    if (n_declined != 1 || !(left_known || right_known))
+    {
+      GTX_HINT_NOTE(72);
+      return false;
+    }
+    uint32_t const i = (sv >> HS_KMER_SHIFT) & 7u;
+    uint32_t const km = i == 0 ? k0 : i == 1 ? k1 : i == 2 ? k2 : i == 3 ? k3 : k4; // (declined: its site, and the place's own sets)
+    bool const no_subst = (sv & (HS_SUBST_LEFT | HS_SUBST_RIGHT)) == 0;
+    uint32_t const v = no_subst ? hk_make((sv & HS_SET_MISSES) == 0 ? HINT_K_LABEL : HINT_K_HOLE, km >> HK_SITE_SHIFT, (sv >> HS_ALLELE_SHIFT) & 3u, false, true) |
+                                    (km & ((255u << HK_SET_SHIFT) | HK_TWO))
+                                : hk_make(HINT_K_HOLE, km >> HK_SITE_SHIFT, 0u, false, true);
+    k0 = i == 0 ? v : k0;
+    k1 = i == 1 ? v : k1;
+    k2 = i == 2 ? v : k2;
+    k3 = i == 3 ? v : k3;
+    k4 = i == 4 ? v : k4;
+  }
+  amb2 &= (1u << HS_SHIFT) - 1u;
   GTX_X_STOP(2, k0 ^ (k1 << 1) ^ (k2 << 2) ^ (k3 << 3) ^ (k4 << 4) ^ amb2 ^ h.upto ^ h.more ^ y_end ^ t_end.x);
   if ((k0 | k1 | k2 | k3 | k4) & (HK_NEED_LEFT | HK_NEED_RIGHT))
   {
@@ -887,7 +947,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
     //      k-mer per read is looked at; a second one sends the read on.
     if ((amb2 & (amb2 - 1u)) != 0)
     {
-      GTX_HINT_NOTE(7);
+      GTX_HINT_NOTE(73); // two k-mers with one ambiguous base in each half
       return false;
     }
     uint32_t const A = (K - 1) * static_cast<uint32_t>(__builtin_ctz(amb2));
@@ -965,7 +1025,8 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       uint32_t const run_a = ((1u << len) - 1u) << a_lo, run_b = ((1u << len) - 1u) << b_lo;
       if (best_len == 0 || n_best != 2 || (f0.y & 255u) < L || (par & (run_a | run_b)) != 0)
       {
-        GTX_HINT_NOTE(10);
+        // (no labelled k-mer at all / more than two longest runs / a site under the read / a parallel chain in one of the runs)
+        GTX_HINT_NOTE(best_len == 0 ? 101 : n_best != 2 ? 102 : (f0.y & 255u) < L ? 103 : 104);
         return HINT_TO_GENERAL;
       }
       uint32_t const all = hc_all(h);
@@ -995,7 +1056,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       uint32_t const size_a = re_a - rs_a + 1u, size_b = re_b - rs_b + 1u;
       if (size_a == size_b)
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(105); // two equal runs whose chains end up equally long
         return HINT_TO_GENERAL;
       }
       bool const a_wins = size_a > size_b;
@@ -1322,7 +1383,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       {
         // (neighbours that are not a SNP's alleles; a SNP on the k-mer's last base -- the next k-mer's first: whether the
         //  other allele's chain lives on depends on what kind of list that k-mer brings)
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(106);
         return HINT_TO_GENERAL;
       }
       two_chains = off != 0;
@@ -1334,27 +1395,44 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       // tail walk's first (the chain counted it twice, the twin counts it once and is returned ALONE, one mismatch less)
       // (counted by the walks' rule -- an ambiguity code that is not N is a character of its own there, whatever its k-mer's
       //  lists found -- against the linear reference, which is what the walk sees as long as the run carries reference
-      //  alleles only: a run with another allele or a set of alleles is left to the general pass)
+      //  alleles only.  Where a k-mer of the run names ANOTHER allele of its SNP -- one allele, not a set -- the walk crosses that
+      //  site with one candidate per allele and keeps the one whose base the read has: the compare counted a mismatch on the site
+      //  -- an unambiguous base that is not the reference's --, the walk counts none.  `alt_sites`: that site, when it lies inside
+      //  bases 31 lo .. pre - 1 (on base `pre` it is the tail walk's).  Worked out for ONE such k-mer in a run none of whose
+      //  k-mers took its label from a Hamming-1 list, on the linear reference; a set of alleles, a substitution besides, or a
+      //  SNP on the base two k-mers of the run share is left to the general pass)
       uint32_t const mm_run = mmk & run, km_hi = hi == 0 ? k0 : hi == 1 ? k1 : hi == 2 ? k2 : hi == 3 ? k3 : k4;
       auto plain = [&](uint32_t k, uint32_t km) { return ((run >> k) & 1u) == 0 || (km & ((3u << HK_ALLELE_SHIFT) | (255u << HK_SET_SHIFT))) == 0; };
-      if (!(plain(0, k0) && plain(1, k1) && plain(2, k2) && plain(3, k3) && plain(4, k4)))
+      uint32_t alt_sites = 0;
+      uint32_t const other = (plain(0, k0) ? 0u : 1u) | (plain(1, k1) ? 0u : 2u) | (plain(2, k2) ? 0u : 4u) | (plain(3, k3) ? 0u : 8u) | (plain(4, k4) ? 0u : 16u);
+      if (other != 0)
       {
-        GTX_HINT_NOTE(10);
-        return HINT_TO_GENERAL;
+        uint32_t const k = static_cast<uint32_t>(__builtin_ctz(other));
+        uint32_t const km = k == 0 ? k0 : k == 1 ? k1 : k == 2 ? k2 : k == 3 ? k3 : k4;
+        uint32_t const yk = ix.pos_flags[idx + (K - 1) * k].y; // (k-mer k's place again: rare, and no select over five words)
+        bool ok = ix.hint_less == 0 && mm_run == 0 && pw == nullptr; // (hint_less: A/B switch GTX_HINT_MORE=0)
+        // (a verdict names an allele without a set only over a lone SNP, HINT_ALT_OK: the second flag word has its offset)
+        ok = ok && (other & (other - 1u)) == 0 && ((km >> HK_SET_SHIFT) & 255u) == 0;
+        alt_sites = (K - 1) * k + ((yk >> HINT_SNPOFF_SHIFT) & 31u) < pre ? 1u : 0u; // (the read's base on the SNP: at or behind base 31 lo)
+        if (!ok)
+        {
+          GTX_HINT_NOTE(107); // twin chains over a run with a set of alleles, or with another allele and a substitution
+          return HINT_TO_GENERAL;
+        }
       }
-      bool const region_clean = hc_upto(h, hi + 1) == hc_upto(h, lo);
+      bool const region_clean = hc_upto(h, hi + 1) == hc_upto(h, lo) + alt_sites;
       if (mm_run == (1u << hi) && hi + 1 > 4)
       {
         // (the fifth k-mer of a read of 156 bases and more: whether its substitution sits on its last base -- base 155, the
         //  tail walk's first -- is not among the compare's counts)
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(108);
         return HINT_TO_GENERAL;
       }
       bool const last_only = mm_run == (1u << hi) && hc_edge(h, hi + 1) == 1 && ((km_hi >> HK_SET_SHIFT) & 255u) == 0;
       bool const twin = region_clean && (mm_run == 0 || last_only);
       if (pre == L - 1 || re != L - 1 || (twin && nvar > 1))
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(109); // twin chains: no tail, a failed tail walk, or twins over several sites
         return HINT_TO_GENERAL;
       }
       if (twin && mm_run == 0)

@@ -201,6 +201,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
   uint32_t amb2 = 0; // k-mers with one ambiguous base in each half: three more filter probes (below)
   uint32_t kv[NK];
   hint_kmers<0, NK>(kv, fx, fy, row, h, n_k, none, amb2);
+  amb2 &= (1u << HS_SHIFT) - 1u; // (what hint_kmer_judge notes about a k-mer with several ambiguous bases is not looked at in this build: declined)
   auto any_declined = [&]()
   {
     bool d = false;
@@ -241,7 +242,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
     //      k-mer per read is looked at; a second one sends the read on.
     if ((amb2 & (amb2 - 1u)) != 0)
     {
-      GTX_HINT_NOTE(7);
+      GTX_HINT_NOTE(73); // two k-mers with one ambiguous base in each half
       return false;
     }
     uint32_t const A = (K - 1) * static_cast<uint32_t>(__builtin_ctz(amb2));
@@ -342,7 +343,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
       uint32_t const run_a = ((1u << len) - 1u) << a_lo, run_b = ((1u << len) - 1u) << b_lo;
       if (best_len == 0 || n_best != 2 || (fy[0] & 255u) < L || (par & (run_a | run_b)) != 0)
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(best_len == 0 ? 101 : n_best != 2 ? 102 : (fy[0] & 255u) < L ? 103 : 104); // (the codes of hinted.hpp)
         return HINT_TO_GENERAL;
       }
       uint32_t const all = hc_all(h);
@@ -372,7 +373,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
       uint32_t const size_a = re_a - rs_a + 1u, size_b = re_b - rs_b + 1u;
       if (size_a == size_b)
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(105);
         return HINT_TO_GENERAL;
       }
       bool const a_wins = size_a > size_b;
@@ -621,7 +622,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
       {
         // (neighbours that are not a SNP's alleles; a SNP on the k-mer's last base -- the next k-mer's first: whether the
         //  other allele's chain lives on depends on what kind of list that k-mer brings)
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(106);
         return HINT_TO_GENERAL;
       }
       two_chains = off != 0;
@@ -641,7 +642,7 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
         all_plain = all_plain && (((run >> i) & 1u) == 0 || (kv[i] & ((3u << HK_ALLELE_SHIFT) | (255u << HK_SET_SHIFT))) == 0);
       if (!all_plain)
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(107);
         return HINT_TO_GENERAL;
       }
       bool const region_clean = hc_upto(h, hi + 1) == hc_upto(h, lo);
@@ -649,14 +650,14 @@ GTX_DEV uint32_t hinted_long_path(GraphView const & g, IndexView const & ix, Row
       {
         // (the build's last k-mer -- the fifth of a read of 156 bases and more: whether its substitution sits on its last base --
         //  base 155, the tail walk's first -- is not among the compare's counts)
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(108);
         return HINT_TO_GENERAL;
       }
       bool const last_only = mm_run == (1u << hi) && hc_edge(h, hi + 1) == 1 && ((km_hi >> HK_SET_SHIFT) & 255u) == 0;
       bool const twin = region_clean && (mm_run == 0 || last_only);
       if (pre == L - 1 || re != L - 1 || (twin && nvar > 1))
       {
-        GTX_HINT_NOTE(10);
+        GTX_HINT_NOTE(109);
         return HINT_TO_GENERAL;
       }
       if (twin && mm_run == 0)

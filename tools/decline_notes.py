@@ -16,9 +16,17 @@ import scenarios  # noqa: E402
 from graphtyper_amd import lib as gtx  # noqa: E402
 
 NOTES = {1: "exact k-mer, place not provably simple", 3: "one substitution, other half shared", 4: "filter says the half may occur",
-         5: "ambiguous base(s), other half shared", 6: ">= 2 substitutions, a clean half is shared", 7: "> 1 ambiguous base (not one half)",
-         8: "tail leaves the node (not one SNP site)", 9: "no usable hint / length", 10: "run selection (equal runs, parallel chain)",
-         11: "head walk leaves the node", 12: "ambiguous base + substitution(s) not provable", 13: "site clash / record too long", 15: "no note"}
+         5: "ambiguous base(s), other half shared", 6: ">= 2 substitutions, a clean half is shared",
+         8: "tail leaves the node (not one SNP site)", 9: "no usable hint / length",
+         11: "head walk leaves the node", 12: "ambiguous base + substitution(s) not provable", 13: "site clash / record too long", 15: "no note",
+         # several ambiguous bases in a k-mer (note 7 before every site had its own code)
+         71: "ambiguity code on the SNP + more ambiguous bases", 72: "2-3 ambiguous bases, no half provably K's alone",
+         73: "two k-mers with an ambiguous base in each half",
+         # run selection (note 10 before)
+         101: "no labelled k-mer", 102: "more than two longest runs", 103: "two equal runs, a site under the read",
+         104: "two equal runs, a parallel chain in one", 105: "two equal runs, chains equally long",
+         106: "twin chains: neighbours not a SNP's alleles / SNP on the last base", 107: "twin chains: allele set, or other allele + substitution",
+         108: "twin chains: substitution in the fifth k-mer", 109: "twin chains: no tail / failed tail walk / several sites"}
 
 kind = sys.argv[1] if len(sys.argv) > 1 else "snp1k"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 40000

@@ -6,7 +6,8 @@ import sys
 
 txt = open(sys.argv[1] if len(sys.argv) > 1 else "/tmp/gtx_api.s").read()
 for name in sys.argv[2:] or ["gtx_align_hinted_kernel", "gtx_align_express4q_kernel", "gtx_align_kernelE", "gtx_score_kernel"]:
-    m = re.search(r"^(_ZN3gtx\d+%s\S*):[^\n]*\n(.*?)\n\s*s_endpgm" % name, txt, re.S | re.M)
+    # (to the function's end label, not to its first s_endpgm: the compiler may put a return in front of blocks that are jumped to)
+    m = re.search(r"^(_ZN3gtx\d+%s\S*):[^\n]*\n(.*?)\n\.Lfunc_end\d+:" % name, txt, re.S | re.M)
     if not m:
         print(name, "not found")
         continue
