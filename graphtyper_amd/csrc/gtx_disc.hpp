@@ -1,5 +1,5 @@
 // gtx_disc.hpp -- the discovery object of include/gtx.h, for the translation units that hold its entry points (gtx_discover.hip:
-// the first pass; gtx_realign.hip: the realignment to the indels).
+// the first pass; gtx_realign.hip: the realignment to the indels; gtx_disc_second.hip: the second pass up to the aligner).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -14,4 +14,5 @@ struct gtx_disc
   gtx::DevPtr<uint32_t> d_refp; // (gtx_disc_destroy waits for the device before the two blocks go back to the cache)
   uint32_t ref_groups = 0;
   gtx::DevPtr<uint8_t> d_refc; // the letters themselves (the span of an indel compares them as the host does)
+  gtx::DevPtr<uint32_t> d_ref5; // the letters as five planes per group (gtx_disc_second_dev.hpp: the second pass compares letter against letter)
 };

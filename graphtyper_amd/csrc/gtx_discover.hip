@@ -31,6 +31,7 @@
 #include "gtx_devprim.hpp"
 #include "gtx_disc.hpp"
 #include "gtx_disc_events_dev.hpp"
+#include "gtx_disc_second_dev.hpp"
 #include "gtx_disc_support.hpp"
 #include "wave_hip.hpp"
 
@@ -80,9 +81,12 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
   d->ref_groups = disc_ref_groups(reference_len);
   std::vector<uint32_t> planes(static_cast<size_t>(d->ref_groups) * 4, 0);
   disc_ref_planes(reference, reference_len, planes.data());
+  std::vector<uint32_t> planes5(static_cast<size_t>(d->ref_groups) * disc_second_dev::REF_PLANES, 0);
+  disc_second_ref_planes(reference, reference_len, planes5.data());
   if (hipSetDevice(device) != hipSuccess || !alloc(d->d_refp, planes.size() * 4) ||
       hipMemcpy(d->d_refp.get(), planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess || !alloc(d->d_refc, reference_len) ||
-      hipMemcpy(d->d_refc.get(), reference, reference_len, hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(d->d_refc.get(), reference, reference_len, hipMemcpyHostToDevice) != hipSuccess || !alloc(d->d_ref5, planes5.size() * 4) ||
+      hipMemcpy(d->d_ref5.get(), planes5.data(), planes5.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
   {
     g_last_error = "gtx_disc_create: upload of the reference failed";
     return GTX_ERR_HIP;
@@ -101,6 +105,7 @@ extern "C" void gtx_disc_destroy(gtx_disc * d)
     (void)hipDeviceSynchronize();
     d->d_refp.reset();
     d->d_refc.reset();
+    d->d_ref5.reset();
   }
   delete d;
 }

@@ -34,7 +34,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged",
            "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts",
            "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device",
-           "gtx_disc_realign_batch", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide"]
+           "gtx_disc_realign_batch", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide",
+           "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates"]
 
 
 class GraphView(C.Structure):
@@ -122,6 +123,16 @@ REALIGN_EVENT = np.dtype([("pos", np.uint32), ("len", np.uint16), ("type", np.ui
 REALIGN_DECISION = np.dtype([("pos", np.int64), ("pos_end", np.int64), ("outcome", np.uint32), ("num_clipped_begin", np.uint32),
                              ("num_clipped_end", np.uint32), ("num_ins_begin", np.uint32)], align=True)
 REALIGN_OK, REALIGN_BAD_PAIR, REALIGN_TOO_LONG = 0, 1, 2
+# the second pass up to the aligner (gtx.h: gtx_disc_indel_table .. gtx_disc_second_candidates)
+DISC_INDEL = np.dtype([("pos", np.uint32), ("len", np.uint32), ("seq_off", np.uint32), ("span", np.uint16), ("type", np.uint8), ("good", np.uint8),
+                       ("file_index", np.int32)], align=True)
+DISC_SECOND_READ = np.dtype([("pos", np.int32), ("pos_end", np.int32), ("score", np.int32), ("num_clipped_begin", np.int16), ("num_clipped_end", np.int16),
+                             ("num_ins_begin", np.int16), ("flags", np.uint16), ("mapq", np.uint8), ("reserved", np.uint8), ("l_qseq", np.uint16),
+                             ("bucket", np.uint32), ("first_event", np.uint32), ("n_events", np.uint32)], align=True)
+DISC_SECOND_EVENT = np.dtype([("indel", np.uint32), ("read_pos", np.int32)], align=True)
+DISC_SECOND_PAIR = np.dtype([("read", np.uint32), ("entry", np.uint32)], align=True)
+assert DISC_INDEL.itemsize == 20 and DISC_SECOND_READ.itemsize == 36 and DISC_SECOND_EVENT.itemsize == 8 and DISC_SECOND_PAIR.itemsize == 8
+DISC_NO_BUCKET = 0xFFFFFFFF
 REALIGN_NO_PADDING, REALIGN_BETTER, REALIGN_SAME_OVERLAPPING, REALIGN_SAME, REALIGN_WORSE = 0, 1, 2, 3, 4
 
 
@@ -226,6 +237,13 @@ def lib():
         L.gtx_disc_realign_target.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
         L.gtx_disc_realign_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
+        L.gtx_disc_indel_table.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gtx_disc_indel_table_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gtx_disc_second_intake.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_uint64] + [C.c_void_p] * 8
+        L.gtx_disc_second_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.gtx_disc_second_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []
@@ -501,6 +519,35 @@ def disc_first_pass_device(handle, d_planes, plane_stride, d_reads, d_cigar, d_r
             continue
         check(rc)
         return words[:n_words.value]
+
+
+def disc_indel_table(words):
+    """gtx_disc_indel_table: the words of gtx_disc_merge -> (DISC_INDEL array in table order, the letters as a uint8 array)"""
+    L = lib()
+    words = np.ascontiguousarray(words, np.uint32)
+    n, n_seq = C.c_uint32(), C.c_uint64()
+    rc = L.gtx_disc_indel_table(_p(words), len(words), None, 0, C.byref(n), None, 0, C.byref(n_seq))
+    if rc not in (0, 5):
+        check(rc)
+    entries, seq = np.zeros(max(n.value, 1), DISC_INDEL), np.zeros(max(n_seq.value, 1), np.uint8)
+    check(L.gtx_disc_indel_table(_p(words), len(words), _p(entries), n.value, C.byref(n), _p(seq), n_seq.value, C.byref(n_seq)))
+    return entries[:n.value], seq[:n_seq.value]
+
+
+def disc_second_buckets(reference_len, bucket_size):
+    """the number of buckets of a region (gtx.h)"""
+    return (reference_len - 1) // bucket_size + 1
+
+
+def disc_second_plan(entries, found, file_index):
+    """gtx_disc_second_plan: the table, the found-bits of gtx_disc_second_intake (uint32 words) and the file's index -> its list as
+    table indices"""
+    L = lib()
+    entries, found = np.ascontiguousarray(entries, DISC_INDEL), np.ascontiguousarray(found, np.uint32)
+    out, n = np.zeros(max(len(entries), 1), np.uint32), C.c_uint32()
+    check(L.gtx_disc_second_plan(_p(entries) if len(entries) else None, len(entries), _p(found) if len(entries) else None, file_index, _p(out), len(out),
+                                 C.byref(n)))
+    return out[:n.value]
 
 
 def disc_realign_target(handle, max_read_size, events):

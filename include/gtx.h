@@ -1050,8 +1050,10 @@ int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const 
  * caller.cpp:990-1186) -- on the host over downloaded arrays (gtx_disc_first_pass) or on the device (gtx_disc_first_pass_device) --
  * and, below, the haplotypes of the surviving events and the merge of the files' results, and the pieces of the realignment of
  * reads to the indels (gtx_disc_realign_*, at the end of this header: the aligner, the haplotype windows, the per-pair decisions).
- * Not built: the sequential driver of the realignment, which feeds a read's new state into the next indel
- * (replace_indel_events, the buckets), the second pass behind it and the variant records.
+ * The second pass up to the aligner -- the indel table, the intake of a file's reads, the buckets, the file's list and the reads of
+ * an indel's round -- is gtx_disc_indel_table / gtx_disc_second_* (at the end of this header).
+ * Not built: the sequential driver of the realignment, which feeds a read's new state into the next indel's round
+ * (replace_indel_events), the final good-support decision (caller.cpp:2179-2229) and the variant records (:2985-3092).
  *   gtx_disc_create        the region's reference (upper-case letters; reference[0] = contig position region_begin, 0-based) on `device`
  *   gtx_disc_events_batch  device: the events of n_reads reads in stream order.  d_planes: the reads as plane rows (gtx_pack_planes),
  *                          d_qual: their base qualities (qual_stride bytes per read), d_reads / d_cigar: the bam1_t fields and the raw
@@ -1237,6 +1239,115 @@ int gtx_disc_realign_target(const gtx_disc *, uint32_t max_read_size, const gtx_
                             char * seq, int32_t * ref_pos, uint32_t cap, uint32_t * n, int64_t * begin_padded, uint64_t * applied);
 int gtx_disc_realign_decide(const gtx_disc_realign_result * result, uint32_t read_len, const int32_t * ref_pos, uint32_t n, int64_t begin_padded,
                             int64_t region_begin, int64_t old_score, int64_t indel_pos, gtx_disc_realign_decision * out);
+
+/* ---- discovery's second pass up to the aligner: every step of parallel_second_pass (src/typer/caller.cpp:2633-2751) that comes
+ * before paw::pairwise_alignment is called -- the indel table of the merged result, the intake of a file's reads
+ * (read_hts_and_return_realignment_indels, :2232-2509), the buckets (:2490-2500, include/graphtyper/typer/bucket.hpp:33-43), the
+ * file's list of indels (:2641-2735 with :2914-2946) and which reads an indel's round looks at (:1890-1958).  All outputs are
+ * integers restated from the reference's text; nothing here depends on paw or on this library's tie-break.
+ * NOT BUILT: the sequential driver (replace_indel_events: a read's new state entering the next indel's round), the final
+ * good-support decision (:2179-2229) and the variant records (:2985-3092).  The layout below is what that driver will update:
+ * the reads' state (gtx_disc_second_read), their entries {table index, read_pos} (gtx_disc_second_event), the bucket arrays.
+ *
+ * What the reference's text does, where its comments suggest otherwise: the file's buckets are made new (:2649-2650), so the
+ * EventSupport that add_indel_event_to_bucket inserts has no realignment support and EVERY I and D operation that reaches the
+ * score pays 7 + (count - 1) * 1 (:2402, :2437; :2404 is never taken); the CIGAR indels live in the bucket's map, never in the
+ * global table, so of a read's CIGAR indels only one thing survives the intake: whether the file holds a given event at all
+ * (is_indel_in_bucket, src/typer/bucket.cpp:66-79).  No CIGAR event is written anywhere.
+ * STATED LIMITS THAT DEPART FROM THE REFERENCE, which is undefined there: bases of an M that lie behind the region's end or
+ * behind the read's last base are not compared and add nothing to the score (the offsets advance by the count all the same); a
+ * read that starts at or behind the region's end (the reference ends the process, :2283-2287) is passed over.  The 16-bit
+ * deletion length of gtx_disc_event does NOT apply here: a deletion of any length pays its penalty and is looked up by its length.
+ * The number of buckets is (reference_len - 1) / bucket_size + 1; the reference's NUM_BUCKETS and resizes differ only in empty
+ * buckets, which change nothing.
+ *   gtx_disc_indel_table    host: the words of gtx_disc_merge (or of gtx_disc_first_pass_haplotypes) -> the indel table in table
+ *                           (Event, src/typer/event.cpp:173-181) order, one gtx_disc_indel per entry, the letters behind each other in
+ *                           `seq`.  *n / *n_seq: the sizes (more than cap / seq_cap: GTX_ERR_CAPACITY, nothing written); words that
+ *                           do not parse: GTX_ERR_ARG.
+ *   gtx_disc_indel_table_upload  the table to device arrays of the caller's (n entries, n_seq bytes) on `stream`; waits for it.
+ *   gtx_disc_second_intake  device, on `stream`: the intake of n_reads reads in stream order -- d_planes, d_reads, d_cigar as
+ *                           gtx_disc_events_batch takes them (no qualities).  Leaves d_second[i] per read (pos = -1: passed over --
+ *                           no cigar, in front of the region or behind it; first_event = n_events = 0: the array of
+ *                           gtx_disc_second_event is the caller's and empty after the intake), d_bucket_max[b] = max(-1,
+ *                           end_with_clip of the bucket's reads), d_bucket_global_max[b] = -1 for a bucket without reads, else max(0,
+ *                           end_with_clip of every read up to and including the bucket's last read IN STREAM ORDER) -- a running
+ *                           maximum over the stream, not over bucket numbers (:2499) --, *d_max_read_size = max(100, l_qseq of the
+ *                           reads not passed over), d_bucket_reads: n_reads stream indices grouped by bucket, stable, bucket b at
+ *                           [d_bucket_off[b], d_bucket_off[b + 1]) (n_buckets + 1 offsets; the reads passed over lie behind the
+ *                           last), d_found: (n_table + 31) / 32 words, bit t set when a CIGAR indel of the file equals table entry t
+ *                           in position, type, length and letters.  Every output is initialised by the call.  The bucket maxima
+ *                           come from atomic maxima and a scan in stream order: no launch order shows in them.  The M compare is
+ *                           letter against letter (the read's seq_nt16_str letter, the region's byte; neither N: -4, else +1).
+ *   gtx_disc_second_plan    host: the file's list as table indices (*n_list of them; more than cap: GTX_ERR_CAPACITY) -- the
+ *                           entries without good support whose file_index is `file_index`, in table order; none: an empty list;
+ *                           else with them every good entry within 60 positions of one of them (pos + 60 >= p before it, pos - 60 <=
+ *                           p behind it, :2692-2717) that the file holds (its found-bit).  Good entries first, by position within
+ *                           each class.  THIS LIBRARY'S OWN RULE where the reference leaves the outcome to the unspecified order of
+ *                           std::sort (std::unique over iterators sorted by position alone, ties of the last sort): every indel
+ *                           once, ties in Event (table) order.
+ *   gtx_disc_second_candidates  device, on `stream`: for the list entries [k0, k1) the (read, entry) pairs the rounds of
+ *                           realign_to_indels look at, in the reference's order of visit: by list position, then bucket, then
+ *                           stream order.  begin_padded = max(0, pos - max_read_size - 100 - region_begin), end_padded = pos +
+ *                           max_read_size + 100 - region_begin; from bucket begin_padded / bucket_size down while b > 0 and
+ *                           global_max[b] > pos - 50; up to min(n_buckets - 1, end_padded / bucket_size); buckets with max_pos_end
+ *                           <= pos - 50 are passed over; a read is skipped when pos < 0 or l_qseq == 0, when the first of its
+ *                           entries that names the indel has a read_pos other than READ_ANTI_SUPPORT (-1), or when it fails the
+ *                           four-part test of :1948-1958 (gtx_disc_realign_wants, indel_span = pos + span of the table).  The
+ *                           bucket arrays are the intake's, the reads' fields the current ones.  pair.read is the read's stream
+ *                           index (what gtx_disc_realign_batch takes), pair.entry the list position k.  d_counts[0] += pairs
+ *                           produced, d_counts[1] += pairs that did not fit pair_cap (the d_counts convention of
+ *                           gtx_disc_events_batch; pair j of the call goes to d_pairs[d_counts[0] at entry + j]); nothing at or behind
+ *                           pair_cap is written (pair_cap 0: d_pairs may be NULL).  Counted first, emitted behind a scan: the
+ *                           order does not depend on scheduling.
+ * gtx_disc_second_intake and gtx_disc_second_candidates take temporaries from the library's device cache and wait for `stream`
+ * before they return them, as gtx_disc_first_pass_device does; the arrays must be complete on the stream (or before it).  A
+ * gtx_disc made with device -1: GTX_ERR_NO_DEVICE; null or misaligned arrays, bucket_size 0: GTX_ERR_ARG; n_reads == 0, an empty
+ * table and an empty slice are legal (n_reads == 0 and k0 == k1 write nothing). */
+typedef struct gtx_disc_indel
+{
+  uint32_t pos;     /* Event::pos */
+  uint32_t len;     /* Event::sequence.size() */
+  uint32_t seq_off; /* its first letter in the table's letters */
+  uint16_t span;    /* EventSupport::span */
+  uint8_t type;     /* 'I', 'D' */
+  uint8_t good;     /* has_indel_good_support */
+  int32_t file_index; /* max_log_qual_file_i */
+} gtx_disc_indel;
+typedef struct gtx_disc_second_read
+{
+  int32_t pos, pos_end; /* Alignment::pos, pos_end (read.hpp:43-44); pos = -1: passed over */
+  int32_t score;
+  int16_t num_clipped_begin, num_clipped_end, num_ins_begin; /* (two's-complement conversion of the counts, read.hpp:46-48) */
+  uint16_t flags;   /* core.flag | IS_CLIPPED (8192) */
+  uint8_t mapq, reserved;
+  uint16_t l_qseq;
+  uint32_t bucket;  /* 0xFFFFFFFF: none */
+  uint32_t first_event, n_events; /* its gtx_disc_second_event entries */
+} gtx_disc_second_read;
+typedef struct gtx_disc_second_event
+{
+  uint32_t indel;   /* table index */
+  int32_t read_pos; /* ReadIndelEvent::read_pos; -1 READ_ANTI_SUPPORT, -2 READ_MULTI_SUPPORT */
+} gtx_disc_second_event;
+typedef struct gtx_disc_second_pair
+{
+  uint32_t read, entry; /* (the layout of gtx_disc_realign_pair: entry k -> window k) */
+} gtx_disc_second_pair;
+int gtx_disc_indel_table(const uint32_t * words, uint64_t n_words, gtx_disc_indel * entries, uint32_t cap, uint32_t * n, char * seq, uint64_t seq_cap,
+                         uint64_t * n_seq);
+int gtx_disc_indel_table_upload(const gtx_disc *, const gtx_disc_indel * entries, uint32_t n, const char * seq, uint64_t n_seq, gtx_disc_indel * d_entries,
+                                char * d_seq, void * stream);
+int gtx_disc_second_intake(gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads, const uint32_t * d_cigar,
+                           uint32_t n_reads, uint32_t bucket_size, const gtx_disc_indel * d_table, const char * d_table_seq, uint32_t n_table,
+                           uint64_t n_table_seq, gtx_disc_second_read * d_second, int32_t * d_bucket_max, int32_t * d_bucket_global_max,
+                           uint32_t * d_max_read_size, uint32_t * d_bucket_reads, uint32_t * d_bucket_off, uint32_t * d_found, void * stream);
+int gtx_disc_second_plan(const gtx_disc_indel * entries, uint32_t n, const uint32_t * found, int32_t file_index, uint32_t * list, uint32_t cap,
+                         uint32_t * n_list);
+int gtx_disc_second_candidates(gtx_disc *, const uint32_t * d_list, uint32_t k0, uint32_t k1, const gtx_disc_indel * d_table, uint32_t n_table,
+                               const gtx_disc_second_read * d_second, uint32_t n_reads, const gtx_disc_second_event * d_events, uint32_t n_events,
+                               uint32_t bucket_size, const int32_t * d_bucket_max, const int32_t * d_bucket_global_max, const uint32_t * d_max_read_size,
+                               const uint32_t * d_bucket_reads, const uint32_t * d_bucket_off, gtx_disc_second_pair * d_pairs, uint32_t pair_cap,
+                               uint32_t * d_counts, void * stream);
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--regions", default="50000,1000000")
 ap.add_argument("--out", default="")
-args = ap.parse_args()
 L_READ, COVERAGE, BUCKET = 150, 30, 50
 
 
@@ -147,12 +146,14 @@ def region(ref_len, seed):
     return row
 
 
-out = {"tool": "tools/disc_rate.py", "device_name": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "repeats": args.repeats,
-       "read_length": L_READ, "coverage": COVERAGE, "bucket_size": BUCKET,
-       "regions": [region(int(r), 7 + i) for i, r in enumerate(args.regions.split(","))]}
-text = json.dumps(out)
-print(text)
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(json.dumps(out, indent=1) + "\n")
+if __name__ == "__main__":  # (tools/disc_second_rate.py takes alignments() from here)
+    args = ap.parse_args()
+    out = {"tool": "tools/disc_rate.py", "device_name": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "repeats": args.repeats,
+           "read_length": L_READ, "coverage": COVERAGE, "bucket_size": BUCKET,
+           "regions": [region(int(r), 7 + i) for i, r in enumerate(args.regions.split(","))]}
+    text = json.dumps(out)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
