@@ -6,7 +6,7 @@
 // running maximum in stream order (rocPRIM inclusive scan) and a stable sort of the stream indices by bucket, then one lane per
 // bucket for its offset and its global maximum; gtx_disc_second_candidates -- one wavefront per list entry over its bucket range,
 // counted first, emitted behind an exclusive scan of the counts, so that the pairs lie in the reference's order of visit
-// whatever the scheduling.  The driver that feeds a read's new state into the next round is not built.
+// whatever the scheduling.  The driver that feeds a read's new state into the next round is gtx_disc_rounds.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -2,7 +2,7 @@
 // gtx_realign_kernel (one wavefront per (read, window) pair, gtx_realign_dev.hpp) behind gtx_disc_realign_batch, and the host
 // functions around it -- which reads (gtx_disc_realign_wants), the window with the indels applied (gtx_disc_realign_target,
 // apply_indel_event src/typer/event.cpp:293-396), what becomes of a read (gtx_disc_realign_decide).  The loop over the indels,
-// which carries a read's new state into the next indel's round, is the caller's.
+// which carries a read's new state into the next indel's round, is gtx_disc_second_rounds (gtx_disc_rounds.hip).
 #include "../../include/gtx.h"
 #include "gtx_devmem.hpp"
 #include "gtx_disc.hpp"

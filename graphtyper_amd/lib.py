@@ -35,7 +35,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts",
            "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device",
            "gtx_disc_realign_batch", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide",
-           "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates"]
+           "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates",
+           "gtx_disc_second_rounds", "gtx_disc_second_decide"]
 
 
 class GraphView(C.Structure):
@@ -133,6 +134,18 @@ DISC_SECOND_EVENT = np.dtype([("indel", np.uint32), ("read_pos", np.int32)], ali
 DISC_SECOND_PAIR = np.dtype([("read", np.uint32), ("entry", np.uint32)], align=True)
 assert DISC_INDEL.itemsize == 20 and DISC_SECOND_READ.itemsize == 36 and DISC_SECOND_EVENT.itemsize == 8 and DISC_SECOND_PAIR.itemsize == 8
 DISC_NO_BUCKET = 0xFFFFFFFF
+# the second pass from the aligner on (gtx.h: gtx_disc_second_rounds, gtx_disc_second_decide)
+DISC_SECOND_SUPPORT = np.dtype([("hq_count", np.uint32), ("anti_count", np.uint32), ("multi_count", np.uint32), ("sequence_reversed", np.uint32),
+                                ("proper_pairs", np.uint32), ("max_mapq", np.uint32)], align=True)
+assert DISC_SECOND_SUPPORT.itemsize == 24
+
+
+class DiscRoundsStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("pairs_aligned", C.c_uint64), ("pairs_refused", C.c_uint64), ("windows_built", C.c_uint64), ("rounds_done", C.c_uint32),
+                ("rounds_skipped", C.c_uint32), ("compactions", C.c_uint32), ("events_wanted", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 REALIGN_NO_PADDING, REALIGN_BETTER, REALIGN_SAME_OVERLAPPING, REALIGN_SAME, REALIGN_WORSE = 0, 1, 2, 3, 4
 
 
@@ -244,6 +257,10 @@ def lib():
         L.gtx_disc_second_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.gtx_disc_second_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.gtx_disc_second_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                             C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DiscRoundsStats), C.c_void_p]
+        L.gtx_disc_second_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []
@@ -548,6 +565,88 @@ def disc_second_plan(entries, found, file_index):
     check(L.gtx_disc_second_plan(_p(entries) if len(entries) else None, len(entries), _p(found) if len(entries) else None, file_index, _p(out), len(out),
                                  C.byref(n)))
     return out[:n.value]
+
+
+def disc_second_rounds(handle, d_planes, plane_stride, d_list, k0, k1, d_table, d_table_seq, n_table, n_table_seq, d_second, n_reads, d_events, event_cap,
+                       n_events, bucket_size, d_bucket_max, d_bucket_global_max, d_max_read_size, d_bucket_reads, d_bucket_off, d_support, stream=None):
+    """gtx_disc_second_rounds over device pointers (integers) -> (status, the entries in use, the statistics as a dict).  status is 0, or
+    5 (GTX_ERR_CAPACITY: the event array is too small for round k0 + rounds_done, which wants events_wanted entries; the state is that
+    round's beginning); any other status raises GtxError."""
+    L = lib()
+    n, stats = C.c_uint32(n_events), DiscRoundsStats()
+    rc = L.gtx_disc_second_rounds(handle, d_planes, plane_stride, d_list, k0, k1, d_table, d_table_seq, n_table, n_table_seq, d_second, n_reads, d_events, event_cap,
+                                  C.byref(n), bucket_size, d_bucket_max, d_bucket_global_max, d_max_read_size, d_bucket_reads, d_bucket_off, d_support,
+                                  C.byref(stats), stream)
+    if rc not in (0, 5):
+        check(rc)
+    return rc, int(n.value), stats.as_dict()
+
+
+def disc_second_decide(entries, lst, support):
+    """gtx_disc_second_decide: the table, a file's list and its downloaded counters -> per table entry, whether the file's rounds gave
+    it good support (bool array; an entry that was good already stays False)"""
+    L = lib()
+    entries, lst, support = np.ascontiguousarray(entries, DISC_INDEL), np.ascontiguousarray(lst, np.uint32), np.ascontiguousarray(support, DISC_SECOND_SUPPORT)
+    assert len(support) == len(entries)
+    bits = np.zeros(max((len(entries) + 31) // 32, 1), np.uint32)
+    check(L.gtx_disc_second_decide(_p(entries) if len(entries) else None, len(entries), _p(lst) if len(lst) else None, len(lst),
+                                   _p(support) if len(entries) else None, _p(bits)))
+    return np.array([(bits[t >> 5] >> (t & 31)) & 1 for t in range(len(entries))], bool)
+
+
+def disc_second_file(handle, reference_len, planes, plane_stride, reads, cigar, words, file_index, bucket_size=50, event_cap=None, stream=None):
+    """A file's whole second pass up to the good-bits: the table of the merged `words`, the intake of the file's reads (numpy arrays as
+    gtx_disc_events_batch takes them: plane rows, DISC_READ, cigar words), its plan, its rounds and the final decision.  handle: a gtx_disc of the region, reference_len: the region's length.  The event
+    array starts at `event_cap` entries (default: two per read, at least 1024) and is doubled -- the call continued at the round it
+    stopped in front of -- whenever the rounds report that it is too small.
+    -> dict(entries, letters, lst, good [bool per table entry], second [DISC_SECOND_READ], lists [per read, [(table index, read_pos)]],
+            support [DISC_SECOND_SUPPORT], stats)"""
+    import torch
+    L = lib()
+    entries, letters = disc_indel_table(words)
+    n, nt = len(reads), len(entries)
+    dev = lambda x: torch.from_numpy(np.concatenate([np.ascontiguousarray(x).view(np.uint8).reshape(-1), np.zeros(16, np.uint8)])).to("cuda:0")  # noqa: E731
+    zeros = lambda nbytes: torch.zeros(nbytes + 16, dtype=torch.uint8, device="cuda:0")  # noqa: E731
+    d_planes, d_reads, d_cigar = dev(planes), dev(np.ascontiguousarray(reads, DISC_READ)), dev(np.ascontiguousarray(cigar, np.uint32))
+    d_table, d_letters = zeros(nt * DISC_INDEL.itemsize), zeros(len(letters))
+    check(L.gtx_disc_indel_table_upload(handle, _p(entries) if nt else None, nt, _p(letters) if len(letters) else None, len(letters), d_table.data_ptr(),
+                                        d_letters.data_ptr(), stream))
+    nb = disc_second_buckets(reference_len, bucket_size)
+    d_second, d_bmax, d_gmax, d_mrs = zeros(n * DISC_SECOND_READ.itemsize), zeros(4 * nb), zeros(4 * nb), zeros(4)
+    d_breads, d_boff, d_found = zeros(4 * n), zeros(4 * (nb + 1)), zeros(4 * ((nt + 31) // 32))
+    torch.cuda.synchronize()
+    check(L.gtx_disc_second_intake(handle, d_planes.data_ptr(), plane_stride, d_reads.data_ptr(), d_cigar.data_ptr(), n, bucket_size, d_table.data_ptr(),
+                                   d_letters.data_ptr(), nt, len(letters), d_second.data_ptr(), d_bmax.data_ptr(), d_gmax.data_ptr(), d_mrs.data_ptr(),
+                                   d_breads.data_ptr(), d_boff.data_ptr(), d_found.data_ptr(), stream))
+    torch.cuda.synchronize()
+    found = d_found.cpu().numpy()[:4 * ((nt + 31) // 32)].view(np.uint32)
+    lst = disc_second_plan(entries, found, file_index)
+    d_list = dev(lst)
+    cap = int(event_cap) if event_cap is not None else max(2 * n, 1024)
+    d_events, d_support = zeros(cap * DISC_SECOND_EVENT.itemsize), zeros(nt * DISC_SECOND_SUPPORT.itemsize)
+    k, used, total = 0, 0, None
+    while True:
+        torch.cuda.synchronize()
+        rc, used, stats = disc_second_rounds(handle, d_planes.data_ptr(), plane_stride, d_list.data_ptr(), k, len(lst), d_table.data_ptr(), d_letters.data_ptr(), nt,
+                                             len(letters), d_second.data_ptr(), n, d_events.data_ptr(), cap, used, bucket_size, d_bmax.data_ptr(), d_gmax.data_ptr(),
+                                             d_mrs.data_ptr(), d_breads.data_ptr(), d_boff.data_ptr(), d_support.data_ptr(), stream)
+        torch.cuda.synchronize()
+        k += stats["rounds_done"]
+        wanted = stats.pop("events_wanted")
+        total = stats if total is None else {key: total[key] + stats[key] for key in stats}
+        if rc == 0:
+            break
+        if wanted <= cap:  # (GTX_ERR_CAPACITY for another reason: a round whose windows are too large)
+            check(rc)
+        cap = max(2 * cap, wanted)
+        bigger = zeros(cap * DISC_SECOND_EVENT.itemsize)
+        bigger[:used * DISC_SECOND_EVENT.itemsize] = d_events[:used * DISC_SECOND_EVENT.itemsize]
+        d_events = bigger
+    second = d_second.cpu().numpy()[:n * DISC_SECOND_READ.itemsize].view(DISC_SECOND_READ).copy()
+    events = d_events.cpu().numpy()[:used * DISC_SECOND_EVENT.itemsize].view(DISC_SECOND_EVENT)
+    support = d_support.cpu().numpy()[:nt * DISC_SECOND_SUPPORT.itemsize].view(DISC_SECOND_SUPPORT).copy()
+    lists = [[(int(e["indel"]), int(e["read_pos"])) for e in events[r["first_event"]:r["first_event"] + r["n_events"]]] for r in second]
+    return dict(entries=entries, letters=letters, lst=lst, good=disc_second_decide(entries, lst, support), second=second, lists=lists, support=support, stats=total)
 
 
 def disc_realign_target(handle, max_read_size, events):

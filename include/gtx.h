@@ -1118,7 +1118,8 @@ int gtx_disc_first_pass(const gtx_disc *, const gtx_disc_read * reads, const uin
  * n_events, per event its "ever" and "always" sets (count + events each).
  * gtx_disc_merge: two such results as one -- merge_haplotypes2 (:64-165) and the union of the files' indels
  * (streamlined_discovery, :2853-2903); `into` may be empty; files are merged in their order.  What the reference does next --
- * realign_to_indels -- is built as its pieces (gtx_disc_realign_*, below); the loop over the indels that strings them is the caller's. */
+ * realign_to_indels -- is built as its pieces (gtx_disc_realign_*, below) and as the loop over the indels that strings them, on the
+ * device (gtx_disc_second_rounds, at the end of this header). */
 int gtx_disc_first_pass_haplotypes(const gtx_disc *, const gtx_disc_read * reads, const uint32_t * cigar, const gtx_disc_read_out * read_out,
                                    uint32_t n_reads, const gtx_disc_event * events, uint64_t n_events, const uint8_t * seq, uint32_t seq_stride,
                                    uint32_t bucket_size, int32_t file_index, uint32_t * out, uint64_t cap, uint64_t * n_words);
@@ -1153,7 +1154,7 @@ int gtx_disc_first_pass_haplotypes_device(const gtx_disc *, const uint8_t * d_pl
  * gtx_disc_realign_wants (which reads, :1941-1958), gtx_disc_realign_target (the window, :1890-1907 and :1968-2002 through
  * apply_indel_event, src/typer/event.cpp:293-396), gtx_disc_realign_batch (the alignments, on the device) and
  * gtx_disc_realign_decide (what becomes of one read, :2025-2153).  The loop over the indels, in which a read's new state enters
- * the next indel's round, is the caller's.
+ * the next indel's round, is gtx_disc_second_rounds (at the end of this header); these pieces stay for a caller with a loop of its own.
  *
  * The alignment.  Query q[1..m] (a read, 4-bit BAM codes) against target t[1..n] (a window, letters mapped through htslib's
  * seq_nt16_table); s(a, b) = +1 when a == b, a == 15 or b == 15 (an N on either side scores as a match, caller.cpp:2359), else -4;
@@ -1245,9 +1246,10 @@ int gtx_disc_realign_decide(const gtx_disc_realign_result * result, uint32_t rea
  * (read_hts_and_return_realignment_indels, :2232-2509), the buckets (:2490-2500, include/graphtyper/typer/bucket.hpp:33-43), the
  * file's list of indels (:2641-2735 with :2914-2946) and which reads an indel's round looks at (:1890-1958).  All outputs are
  * integers restated from the reference's text; nothing here depends on paw or on this library's tie-break.
- * NOT BUILT: the sequential driver (replace_indel_events: a read's new state entering the next indel's round), the final
- * good-support decision (:2179-2229) and the variant records (:2985-3092).  The layout below is what that driver will update:
- * the reads' state (gtx_disc_second_read), their entries {table index, read_pos} (gtx_disc_second_event), the bucket arrays.
+ * The sequential driver (replace_indel_events: a read's new state entering the next indel's round) and the final good-support
+ * decision (:2179-2229) are gtx_disc_second_rounds and gtx_disc_second_decide, below; the layout here is what that driver updates:
+ * the reads' state (gtx_disc_second_read) and their entries {table index, read_pos} (gtx_disc_second_event).
+ * NOT BUILT: the variant records (:2985-3092).
  *
  * What the reference's text does, where its comments suggest otherwise: the file's buckets are made new (:2649-2650), so the
  * EventSupport that add_indel_event_to_bucket inserts has no realignment support and EVERY I and D operation that reaches the
@@ -1348,6 +1350,77 @@ int gtx_disc_second_candidates(gtx_disc *, const uint32_t * d_list, uint32_t k0,
                                uint32_t bucket_size, const int32_t * d_bucket_max, const int32_t * d_bucket_global_max, const uint32_t * d_max_read_size,
                                const uint32_t * d_bucket_reads, const uint32_t * d_bucket_off, gtx_disc_second_pair * d_pairs, uint32_t pair_cap,
                                uint32_t * d_counts, void * stream);
+
+/* ---- discovery's second pass from the aligner on: the rounds of realign_to_indels (src/typer/caller.cpp:1876-2171), the support
+ * counters of Alignment::add_indel_event / replace_indel_events (src/typer/read.cpp:29-116) and the good-support decision at the
+ * end (:2179-2229).  With gtx_disc_indel_table, gtx_disc_second_intake and gtx_disc_second_plan this is a file's whole second pass
+ * up to the good-bits.  NOT BUILT: the variant records (:2985-3092), which go through Variant::add_base_in_front and the global
+ * graph and read exactly these good-bits.
+ *   gtx_disc_second_rounds  device, on `stream`: the rounds of the list entries [k0, k1), in list order.  A round is: its pairs
+ *                           (gtx_disc_second_candidates over the reads' CURRENT state and entries); per pair the window -- the
+ *                           round's plain window (entry k applied alone) for a read without entries, else a window of the read's
+ *                           own: entry k, then EVERY entry of the read in list order whatever its read_pos (:1968-2002; every
+ *                           table entry has realignment support, :2924), by apply_indel_event's rules as
+ *                           gtx_disc_realign_target states them, letter for letter and flag for flag, with no limit on the
+ *                           number of entries --; the alignments (gtx_disc_realign_batch's kernel); per pair the decision of
+ *                           gtx_disc_realign_decide, carried out: NO_PADDING and SAME nothing; WORSE appends {entry, -1} to the
+ *                           read's list and adds one to anti_count; SAME_OVERLAPPING appends {entry, -2} and adds one to
+ *                           multi_count; BETTER is replace_indel_events -- the counters of every old entry lowered, the new list
+ *                           {k, 0} followed by every old entry in order, {t, 0} when the window applied it and {t, -1} when not,
+ *                           their counters raised, and pos, pos_end, score, the two clip counts and num_ins_begin taken from the
+ *                           decision (through the reference's int32_t / int16_t fields).  An entry with read_pos >= 0 counts in
+ *                           hq_count, in sequence_reversed on flag 16, in proper_pairs on flag 2, and raises max_mapq when mapq <
+ *                           255.  When entry k itself does not apply (an indel at the region's first base; a window outside the
+ *                           region) the round does nothing (:1905) and is counted in rounds_skipped.  The bucket arrays stay the
+ *                           intake's: the reference never updates max_pos_end after a realignment either.
+ *                           d_support: n_table counters, in/out.  THE COUNTERS ARE PER CALL SEQUENCE OF ONE FILE AND START FROM
+ *                           ZEROS (EventSupport::clear(), :2920-2924), with an empty event array: then sequence_reversed and
+ *                           proper_pairs always equal the number of current holders with the flag, the floors of read.cpp:76,83
+ *                           never act, and atomic add, subtract and max are exact in any order.  They are 32 bits wide; the
+ *                           reference's are uint16_t, and gtx_disc_second_decide reads them through that width.
+ *                           d_events / event_cap / *n_events: the reads' lists (d_second[i].first_event, n_events) and how many
+ *                           entries of the array are in use, in/out.  A round places its new lists behind them, at the exclusive
+ *                           sum of their sizes in pair order: the array is a function of the inputs, run after run.  A list a
+ *                           read has left stays until a compaction (stream order), which happens in front of a round whose new
+ *                           lists might not fit (old sizes + 1 each).  If the round's new lists do not fit even then: the call
+ *                           returns GTX_ERR_CAPACITY, stats->events_wanted is the size that round needs, stats->rounds_done the
+ *                           rounds in front of it; the reads, their lists and the counters are exactly that round's beginning, so a
+ *                           call over [k0 + rounds_done, k1) with a larger array continues and ends where one call would have.
+ *                           STATED LIMIT THAT DEPARTS FROM THE REFERENCE: a pair the aligner refuses -- a read of more than
+ *                           GTX_MAX_READ bases, a window of more than GTX_REALIGN_MAX_TARGET letters -- is not aligned in that
+ *                           round: the read's state stays as it was and the pair is counted in pairs_refused.  A round whose
+ *                           windows would take 2^31 letters or more ends the call with GTX_ERR_CAPACITY in the same way.
+ *                           stats (host, may not be NULL): written by every call that gets past its arguments.
+ *   gtx_disc_second_decide  host: :2179-2229 over the file's list.  good_bits: (n + 31) / 32 words, cleared, then bit t set for
+ *                           every list entry t that was not good and now is: is_good_count (correction, count; lq_count is 0 in
+ *                           this pass) and EventSupport::is_good_indel() with eps = 7 (event.cpp:95-106, :273-291), in doubles,
+ *                           operation for operation.  An entry that is good already is left alone (its bit stays clear).
+ * THE ORDER RULE ACROSS FILES IS THIS LIBRARY'S OWN: every file's plan and rounds read `good` as the merge left it, and the files'
+ * good-bits are ORed into the table afterwards.  In the reference another thread's decision can land before a file's plan reads
+ * the flag (:2696, :2221): the outcome there depends on timing.
+ * gtx_disc_second_rounds takes its temporaries from the library's device cache and waits for `stream` several times a round (the
+ * grid sizes come from counts).  A gtx_disc made with device -1: GTX_ERR_NO_DEVICE; null or misaligned arrays, bucket_size 0, k1 <
+ * k0, *n_events > event_cap, a read whose list does not lie inside the entries in use: GTX_ERR_ARG; k0 == k1 and n_reads == 0 are
+ * legal and write nothing but stats. */
+typedef struct gtx_disc_second_support
+{
+  uint32_t hq_count, anti_count, multi_count, sequence_reversed, proper_pairs, max_mapq;
+} gtx_disc_second_support;
+typedef struct gtx_disc_second_rounds_stats
+{
+  uint64_t pairs, pairs_aligned, pairs_refused; /* of the rounds that were not skipped: pairs = aligned + refused */
+  uint64_t windows_built;                       /* plain windows included */
+  uint32_t rounds_done, rounds_skipped;         /* rounds_skipped: of rounds_done, those entry k did not apply in (:1905) */
+  uint32_t compactions, events_wanted;          /* events_wanted: GTX_ERR_CAPACITY only */
+} gtx_disc_second_rounds_stats;
+int gtx_disc_second_rounds(gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const uint32_t * d_list, uint32_t k0, uint32_t k1,
+                           const gtx_disc_indel * d_table, const char * d_table_seq, uint32_t n_table, uint64_t n_table_seq, gtx_disc_second_read * d_second,
+                           uint32_t n_reads, gtx_disc_second_event * d_events, uint32_t event_cap, uint32_t * n_events, uint32_t bucket_size,
+                           const int32_t * d_bucket_max, const int32_t * d_bucket_global_max, const uint32_t * d_max_read_size,
+                           const uint32_t * d_bucket_reads, const uint32_t * d_bucket_off, gtx_disc_second_support * d_support,
+                           gtx_disc_second_rounds_stats * stats, void * stream);
+int gtx_disc_second_decide(const gtx_disc_indel * entries, uint32_t n, const uint32_t * list, uint32_t n_list, const gtx_disc_second_support * support,
+                           uint32_t * good_bits);
 
 #ifdef __cplusplus
 }
