@@ -14,5 +14,6 @@ struct gtx_disc
   gtx::DevPtr<uint32_t> d_refp; // (gtx_disc_destroy waits for the device before the two blocks go back to the cache)
   uint32_t ref_groups = 0;
   gtx::DevPtr<uint8_t> d_refc; // the letters themselves (the span of an indel compares them as the host does)
+  uint32_t max_read_len = 0; // gtx_disc_set_max_read_len: 0 = GTX_MAX_READ; above it, gtx_disc_realign_batch runs the long aligner behind the short one
   gtx::DevPtr<uint32_t> d_ref5; // the letters as five planes per group (gtx_disc_second_dev.hpp: the second pass compares letter against letter)
 };

@@ -7,6 +7,7 @@
 #include "gtx_devmem.hpp"
 #include "gtx_disc.hpp"
 #include "gtx_realign_dev.hpp"
+#include "gtx_realign_long_dev.hpp"
 #include "wave_hip.hpp"
 
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@ static_assert(sizeof(gtx_disc_realign_result) == sizeof(gtx::RealignResult) && s
 static_assert(sizeof(gtx_disc_realign_pair) == sizeof(gtx::RealignPair) && sizeof(gtx_disc_realign_pair) == 8, "pair layout");
 static_assert(GTX_REALIGN_OK == gtx::REALIGN_OK && GTX_REALIGN_BAD_PAIR == gtx::REALIGN_BAD_PAIR && GTX_REALIGN_TOO_LONG == gtx::REALIGN_TOO_LONG, "statuses");
 static_assert(GTX_REALIGN_MAX_TARGET == gtx::REALIGN_MAX_TARGET && GTX_MAX_READ == gtx::REALIGN_MAX_READ, "limits");
+static_assert(GTX_REALIGN_MAX_TARGET_LONG == gtx::REALIGN_MAX_TARGET_LONG && GTX_MAX_READ_LONG == gtx::REALIGN_MAX_READ_LONG, "long limits");
 
 namespace gtx
 {
@@ -43,7 +45,35 @@ __global__ __launch_bounds__(64 * WAVES) void gtx_realign_kernel(uint8_t const *
   p.target = gtx::WaveHip::uni(pairs[i].target);
   gtx::realign_pair_dev<gtx::WaveHip>(planes, plane_stride, lens, n_reads, target_seq, target_off, n_targets, p, out + i);
 }
+
+// behind gtx_realign_kernel on the same stream, for a gtx_disc in long mode: the pairs that one refused and the limits in force take
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(3))) void gtx_realign_long_kernel(uint8_t const * __restrict__ planes, uint32_t plane_stride, uint16_t const * __restrict__ lens,
+                                                                     uint32_t n_reads, uint8_t const * __restrict__ target_seq,
+                                                                     uint32_t const * __restrict__ target_off, uint32_t n_targets, uint32_t max_read,
+                                                                     gtx::RealignPair const * __restrict__ pairs, uint32_t n_pairs,
+                                                                     gtx::RealignResult * __restrict__ out)
+{
+  uint32_t const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint32_t const i = blockIdx.x * WAVES + wave;
+  if (i >= n_pairs)
+    return;
+  gtx::RealignPair p;
+  p.read = gtx::WaveHip::uni(pairs[i].read);
+  p.target = gtx::WaveHip::uni(pairs[i].target);
+  gtx::realign_long_pair_dev<gtx::WaveHip>(planes, plane_stride, lens, n_reads, target_seq, target_off, n_targets, max_read, p, out + i);
+}
 } // namespace
+
+extern "C" int gtx_disc_set_max_read_len(gtx_disc * d, uint32_t max_read_len)
+{
+  if (!d || !(max_read_len == 0 || (max_read_len >= GTX_MAX_READ && max_read_len <= GTX_MAX_READ_LONG)))
+  {
+    gtx::g_last_error = "gtx_disc_set_max_read_len: max_read_len must be 0, 256 (GTX_MAX_READ) or 257 .. 1000 (GTX_MAX_READ_LONG)";
+    return GTX_ERR_ARG;
+  }
+  d->max_read_len = max_read_len == GTX_MAX_READ ? 0 : max_read_len;
+  return GTX_OK;
+}
 
 extern "C" int gtx_disc_realign_batch(gtx_disc * d, const uint8_t * d_planes, uint32_t plane_stride, const uint16_t * d_lens, uint32_t n_reads,
                                       const char * d_target_seq, const uint32_t * d_target_off, uint32_t n_targets, const gtx_disc_realign_pair * d_pairs,
@@ -62,7 +92,14 @@ extern "C" int gtx_disc_realign_batch(gtx_disc * d, const uint8_t * d_planes, ui
   hipLaunchKernelGGL(gtx_realign_kernel, dim3((n_pairs + WAVES - 1u) / WAVES), dim3(64 * WAVES), 0, static_cast<hipStream_t>(stream), d_planes, plane_stride, d_lens,
                      n_reads, reinterpret_cast<uint8_t const *>(d_target_seq), d_target_off, n_targets, reinterpret_cast<gtx::RealignPair const *>(d_pairs), n_pairs,
                      reinterpret_cast<gtx::RealignResult *>(d_out));
-  return gtx::hip_ok(hipGetLastError(), "launch of gtx_realign_kernel", "gtx_disc_realign_batch: ") ? GTX_OK : GTX_ERR_HIP;
+  if (!gtx::hip_ok(hipGetLastError(), "launch of gtx_realign_kernel", "gtx_disc_realign_batch: "))
+    return GTX_ERR_HIP;
+  if (d->max_read_len <= GTX_MAX_READ)
+    return GTX_OK;
+  hipLaunchKernelGGL(gtx_realign_long_kernel, dim3((n_pairs + WAVES - 1u) / WAVES), dim3(64 * WAVES), 0, static_cast<hipStream_t>(stream), d_planes, plane_stride,
+                     d_lens, n_reads, reinterpret_cast<uint8_t const *>(d_target_seq), d_target_off, n_targets, d->max_read_len,
+                     reinterpret_cast<gtx::RealignPair const *>(d_pairs), n_pairs, reinterpret_cast<gtx::RealignResult *>(d_out));
+  return gtx::hip_ok(hipGetLastError(), "launch of gtx_realign_long_kernel", "gtx_disc_realign_batch: ") ? GTX_OK : GTX_ERR_HIP;
 }
 
 // ---- host: which reads, the window, the decision ----------------------------------------------------------------------------

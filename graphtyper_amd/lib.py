@@ -34,7 +34,7 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_pack_2bit", "gtx_stream_push_packed", "gtx_packed_to_planes", "gtx_align_batch_packed", "gtx_align_batch_packed_staged",
            "gtx_inflate_create", "gtx_inflate_destroy", "gtx_inflate_batch", "gtx_inflate_bgzf", "gtx_reads_set_inflate_device", "gtx_reads_inflate_counts",
            "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device",
-           "gtx_disc_realign_batch", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide",
+           "gtx_disc_realign_batch", "gtx_disc_set_max_read_len", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide",
            "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates",
            "gtx_disc_second_rounds", "gtx_disc_second_decide"]
 
@@ -124,6 +124,8 @@ REALIGN_EVENT = np.dtype([("pos", np.uint32), ("len", np.uint16), ("type", np.ui
 REALIGN_DECISION = np.dtype([("pos", np.int64), ("pos_end", np.int64), ("outcome", np.uint32), ("num_clipped_begin", np.uint32),
                              ("num_clipped_end", np.uint32), ("num_ins_begin", np.uint32)], align=True)
 REALIGN_OK, REALIGN_BAD_PAIR, REALIGN_TOO_LONG = 0, 1, 2
+MAX_READ, MAX_READ_LONG = 256, 1000  # GTX_MAX_READ, GTX_MAX_READ_LONG
+REALIGN_MAX_TARGET, REALIGN_MAX_TARGET_LONG = 2048, 4095  # the aligner's windows: by default, after disc_set_max_read_len(handle, > 256)
 # the second pass up to the aligner (gtx.h: gtx_disc_indel_table .. gtx_disc_second_candidates)
 DISC_INDEL = np.dtype([("pos", np.uint32), ("len", np.uint32), ("seq_off", np.uint32), ("span", np.uint16), ("type", np.uint8), ("good", np.uint8),
                        ("file_index", np.int32)], align=True)
@@ -246,6 +248,7 @@ def lib():
                                                             C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.gtx_disc_realign_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                              C.c_uint32, C.c_void_p, C.c_void_p]
+        L.gtx_disc_set_max_read_len.argtypes = [C.c_void_p, C.c_uint32]
         L.gtx_disc_realign_wants.argtypes = [C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, C.c_int64, C.c_uint32]
         L.gtx_disc_realign_target.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
@@ -594,15 +597,25 @@ def disc_second_decide(entries, lst, support):
     return np.array([(bits[t >> 5] >> (t & 31)) & 1 for t in range(len(entries))], bool)
 
 
-def disc_second_file(handle, reference_len, planes, plane_stride, reads, cigar, words, file_index, bucket_size=50, event_cap=None, stream=None):
+def disc_set_max_read_len(handle, n):
+    """gtx_disc_set_max_read_len: 0 or 256 for the aligner's default limits (256 bases, 2 048 letters), 257 .. MAX_READ_LONG for reads of
+    up to n bases and windows of up to REALIGN_MAX_TARGET_LONG letters; anything else raises GtxError"""
+    check(lib().gtx_disc_set_max_read_len(handle, int(n)))
+
+
+def disc_second_file(handle, reference_len, planes, plane_stride, reads, cigar, words, file_index, bucket_size=50, event_cap=None, stream=None,
+                     max_read_len=None):
     """A file's whole second pass up to the good-bits: the table of the merged `words`, the intake of the file's reads (numpy arrays as
     gtx_disc_events_batch takes them: plane rows, DISC_READ, cigar words), its plan, its rounds and the final decision.  handle: a gtx_disc of the region, reference_len: the region's length.  The event
     array starts at `event_cap` entries (default: two per read, at least 1024) and is doubled -- the call continued at the round it
-    stopped in front of -- whenever the rounds report that it is too small.
+    stopped in front of -- whenever the rounds report that it is too small.  max_read_len: when given, set on `handle` first
+    (disc_set_max_read_len; it stays set).
     -> dict(entries, letters, lst, good [bool per table entry], second [DISC_SECOND_READ], lists [per read, [(table index, read_pos)]],
             support [DISC_SECOND_SUPPORT], stats)"""
     import torch
     L = lib()
+    if max_read_len is not None:
+        disc_set_max_read_len(handle, max_read_len)
     entries, letters = disc_indel_table(words)
     n, nt = len(reads), len(entries)
     dev = lambda x: torch.from_numpy(np.concatenate([np.ascontiguousarray(x).view(np.uint8).reshape(-1), np.zeros(16, np.uint8)])).to("cuda:0")  # noqa: E731

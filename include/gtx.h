@@ -1181,6 +1181,15 @@ int gtx_disc_first_pass_haplotypes_device(const gtx_disc *, const uint8_t * d_pl
  *                           more than GTX_MAX_READ bases (or more than its plane row holds), a window of more than
  *                           GTX_REALIGN_MAX_TARGET letters -- nothing of such a pair is loaded, its other fields are 0.  A gtx_disc
  *                           made with device -1: GTX_ERR_NO_DEVICE; n_pairs == 0: GTX_OK.
+ *   gtx_disc_set_max_read_len  host (device -1 will do), at any time between launches; mirrors gtx_params::max_read_len.  0 or
+ *                           GTX_MAX_READ: the limits above, the default.  GTX_MAX_READ + 1 .. GTX_MAX_READ_LONG: from the next
+ *                           gtx_disc_realign_batch (and gtx_disc_second_rounds) on, reads of up to that length and windows of up to
+ *                           GTX_REALIGN_MAX_TARGET_LONG letters (2 x 1 000 + 200 for a round's plain window, and room for the read's
+ *                           own insertions; 12 bits of target_begin) are aligned: a second kernel behind the first takes the
+ *                           pairs the first refused, by the same recurrence and the same tie-break, field for field.  A pair
+ *                           within the default limits gives the same bytes in either mode; beyond the limits in force the status
+ *                           stays GTX_REALIGN_TOO_LONG with the other fields 0.  Any other value: GTX_ERR_ARG.  The host pieces
+ *                           (wants, target, decide) do not depend on it.
  *   gtx_disc_realign_wants  host: 1 when realign_to_indels aligns a read at [pos, pos_end] (contig positions) with these clip
  *                           counts to an indel at indel_pos whose EventSupport::span is `span`, else 0 (:1941-1958; pos < 0: 0).
  *   gtx_disc_realign_target host (device -1 will do): the window around events[0], the indel being realigned to --
@@ -1200,6 +1209,7 @@ int gtx_disc_first_pass_haplotypes_device(const gtx_disc *, const uint8_t * d_pl
  *                           ref_pos[target_begin] + begin_padded <= indel_pos <= ref_pos[target_end] + begin_padded, as the text
  *                           has it, :2086-2087) or SAME. */
 #define GTX_REALIGN_MAX_TARGET 2048u
+#define GTX_REALIGN_MAX_TARGET_LONG 4095u /* after gtx_disc_set_max_read_len(> GTX_MAX_READ) */
 #define GTX_REALIGN_OK 0u
 #define GTX_REALIGN_BAD_PAIR 1u
 #define GTX_REALIGN_TOO_LONG 2u
@@ -1235,6 +1245,7 @@ typedef struct gtx_disc_realign_decision
 int gtx_disc_realign_batch(gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const uint16_t * d_lens, uint32_t n_reads, const char * d_target_seq,
                            const uint32_t * d_target_off /* n_targets + 1 */, uint32_t n_targets, const gtx_disc_realign_pair * d_pairs, uint32_t n_pairs,
                            gtx_disc_realign_result * d_out, void * stream);
+int gtx_disc_set_max_read_len(gtx_disc *, uint32_t max_read_len);
 int gtx_disc_realign_wants(int64_t pos, int64_t pos_end, uint32_t num_clipped_begin, uint32_t num_clipped_end, int64_t indel_pos, uint32_t span);
 int gtx_disc_realign_target(const gtx_disc *, uint32_t max_read_size, const gtx_disc_realign_event * events, uint32_t n_events, const char * event_seq,
                             char * seq, int32_t * ref_pos, uint32_t cap, uint32_t * n, int64_t * begin_padded, uint64_t * applied);
@@ -1388,7 +1399,10 @@ int gtx_disc_second_candidates(gtx_disc *, const uint32_t * d_list, uint32_t k0,
  *                           call over [k0 + rounds_done, k1) with a larger array continues and ends where one call would have.
  *                           STATED LIMIT THAT DEPARTS FROM THE REFERENCE: a pair the aligner refuses -- a read of more than
  *                           GTX_MAX_READ bases, a window of more than GTX_REALIGN_MAX_TARGET letters -- is not aligned in that
- *                           round: the read's state stays as it was and the pair is counted in pairs_refused.  A round whose
+ *                           round: the read's state stays as it was and the pair is counted in pairs_refused.  One read of 925
+ *                           bases in the file makes every round's window that large.  After gtx_disc_set_max_read_len(d, L), L >
+ *                           GTX_MAX_READ, the limits are L bases and GTX_REALIGN_MAX_TARGET_LONG letters, and pairs_refused
+ *                           counts only the pairs beyond those (reads over 1 000 bases stay out of reach).  A round whose
  *                           windows would take 2^31 letters or more ends the call with GTX_ERR_CAPACITY in the same way.
  *                           stats (host, may not be NULL): written by every call that gets past its arguments.
  *   gtx_disc_second_decide  host: :2179-2229 over the file's list.  good_bits: (n + 31) / 32 words, cleared, then bit t set for
