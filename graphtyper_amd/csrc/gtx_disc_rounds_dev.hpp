@@ -112,7 +112,7 @@ GTX_DEV Plain plain_window(long pos, long max_read_size, long region_begin, long
 {
   long const begin = std::max(0l, pos - max_read_size - 2 * PAD - region_begin), end_padded = pos + max_read_size + 2 * PAD - region_begin;
   long end = end_padded >= REF_SIZE ? REF_SIZE : end_padded;
-  if (begin >= REF_SIZE || end < begin) // (:1891 asserts otherwise)
+  if (end < begin) // (:1891 asserts otherwise; a window that begins at or behind the region's end has end == REF_SIZE <= begin)
     end = begin;
   return Plain{begin, end};
 }
@@ -485,25 +485,33 @@ GTX_HD uint32_t disc_log_qual(uint32_t count, uint32_t anti_count, uint32_t eps)
   return gt00 > gt_alt ? gt00 - gt_alt : 0u;
 }
 
+// is_good_count (:2187-2194) of a list entry and its counters.  With hq_count above 6 -- which is_good_indel asks for -- the first
+// arm always holds, so disc_second_good never shows the two others; they are a function of their own so that they can be held to
+// the text all the same (tests/emu_disc_rounds).
+GTX_HD bool disc_second_good_count(gtx_disc_indel const & indel, gtx_disc_second_support const & s)
+{
+  uint16_t const hq_count = static_cast<uint16_t>(s.hq_count), span = indel.span; // (lq_count is 0 in this pass and left out)
+  double const size = static_cast<double>(indel.len);
+  double const correction = indel.type == 'I' ? static_cast<double>(size / 2.0 + 8.0) / 8.0 : static_cast<double>(size / 3.0 + 10.0) / 10.0; // :2187-2188
+  double const count = correction * hq_count;                                                                                                // :2190
+  return (hq_count >= 5 && count >= 5.5) || (span >= 5 && hq_count >= 4 && count >= 5.0) || (span >= 15 && hq_count >= 3 && count >= 4.5);
+}
+
 // Does a list entry without good support have it after the file's rounds?  lq_count is 0 in this pass.  The counters are read
 // through the reference's uint16_t (max_mapq: uint8_t); the doubles are one operation each, as the text has them.
 GTX_HD bool disc_second_good(gtx_disc_indel const & indel, gtx_disc_second_support const & s)
 {
-  uint16_t const hq_count = static_cast<uint16_t>(s.hq_count), lq_count = 0, anti_count = static_cast<uint16_t>(s.anti_count),
-                 multi_count = static_cast<uint16_t>(s.multi_count), sequence_reversed = static_cast<uint16_t>(s.sequence_reversed),
-                 proper_pairs = static_cast<uint16_t>(s.proper_pairs), span = indel.span;
-  uint8_t const max_mapq = static_cast<uint8_t>(s.max_mapq);
-  double const size = static_cast<double>(indel.len);
-  double const correction = indel.type == 'I' ? static_cast<double>(size / 2.0 + 8.0) / 8.0 : static_cast<double>(size / 3.0 + 10.0) / 10.0; // :2187-2188
-  double const count = correction * (hq_count + lq_count);                                                                                   // :2190
-  bool const is_good_count = (hq_count >= 5 && count >= 5.5) || (span >= 5 && hq_count >= 4 && count >= 5.0) || (span >= 15 && hq_count >= 3 && count >= 4.5);
-  if (!is_good_count)
+  if (!disc_second_good_count(indel, s))
     return false;
+  uint16_t const hq_count = static_cast<uint16_t>(s.hq_count), anti_count = static_cast<uint16_t>(s.anti_count),
+                 multi_count = static_cast<uint16_t>(s.multi_count), sequence_reversed = static_cast<uint16_t>(s.sequence_reversed),
+                 proper_pairs = static_cast<uint16_t>(s.proper_pairs);
+  uint8_t const max_mapq = static_cast<uint8_t>(s.max_mapq);
   // EventSupport::is_good_indel(eps = 7)
-  long const depth = hq_count + lq_count + anti_count + multi_count;
+  long const depth = hq_count + anti_count + multi_count;
   if (hq_count <= 6 || sequence_reversed <= 0 || sequence_reversed >= depth || proper_pairs <= 4 || (hq_count < 10 && max_mapq <= 10))
     return false;
-  long const qual = 3l * disc_log_qual(static_cast<uint32_t>(hq_count + lq_count), anti_count, 7u);
+  long const qual = 3l * disc_log_qual(hq_count, anti_count, 7u);
   if (qual < 50)
     return false;
   double const qd = static_cast<double>(qual) / static_cast<double>(depth);

@@ -80,17 +80,49 @@ def replace_indel_events(entries, support, flags, mapq, new_entries, trace):
     entries[:] = new_entries
 
 
+def how_applied(ref_pos, pos_, type_, event_size, offset):
+    """what apply_indel_event (event.cpp:293-396, tests/realign_ref.py) will meet on these ref_pos values -- looked at, nothing is
+    changed: dict(search: 'outside' (the position is not an index of the window) | 'at once' | 'walked forward' | 'walked back' |
+    'not found', index (where the search ended), pure (None when the search failed), past / differs: the two arms of a deletion's end
+    test, pos + size >= n and ref_pos[pos + size] != position + size (None where the arm is not evaluated))"""
+    want = pos_ - offset
+    n = len(ref_pos)
+    out = dict(search="outside", index=None, pure=None, past=None, differs=None)
+    if want <= 0 or want >= n:
+        return out
+    pos = want
+    out["search"] = "at once"
+    if ref_pos[pos] != want:
+        while pos + 1 < n and ref_pos[pos] < want:
+            pos += 1
+        forward = pos - want
+        while pos > 0 and ref_pos[pos] > want:
+            pos -= 1
+        out["search"] = "not found" if ref_pos[pos] != want else "walked forward" if forward else "walked back"
+    out["index"] = pos
+    if out["search"] == "not found":
+        return out
+    window = ref_pos[max(0, pos - 3):min(n, pos + 3)]
+    out["pure"] = all(b == a + 1 for a, b in zip(window, window[1:]))
+    if out["pure"] and type_ == 'D':
+        out["past"] = pos + event_size >= n
+        if not out["past"]:
+            out["differs"] = ref_pos[pos + event_size] != want + event_size
+    return out
+
+
 def rounds(reference, region_begin, bucket_size, table, lst, k0, k1, taken, states, entries, support, sequences, after_round=None):
     """:1876-2171 for the list entries k0 .. k1 - 1.  taken: the intake's result (its bucket arrays stay as they are); states, entries,
     support: changed in place; sequences: per read its letters.  after_round(k): called behind every round.
-    -> trace: dict(rounds [per round: dict(k, skipped, visits [(read, outcome or 'refused', applied bits, window length)])], aligned,
-    refused, skipped, windows, floors, lowered)"""
+    -> trace: dict(rounds [per round: dict(k, skipped, visits [(read, outcome or 'refused', applied bits, window length)], own [per
+    visit, per entry of the read: how_applied() in front of its apply_indel_event, with t, read_pos and applied])], aligned, refused,
+    skipped, windows, floors, lowered)"""
     ref_size = len(reference)
     trace = dict(rounds=[], aligned=0, refused=0, skipped=0, windows=0, floors=0, lowered=0)
     for k in range(k0, k1):
         t = lst[k]
         indel = table[t]
-        this = dict(k=k, skipped=False, visits=[])
+        this = dict(k=k, skipped=False, visits=[], own=[])
         trace["rounds"].append(this)
         begin_padded = max(0, indel["pos"] - taken["max_read_size"] - 2 * PAD - region_begin)  # :1890
         end_padded = indel["pos"] + taken["max_read_size"] + 2 * PAD - region_begin            # :1892
@@ -113,13 +145,17 @@ def rounds(reference, region_begin, bucket_size, table, lst, k0, k1, taken, stat
             bits = 1
             if entries[i]:
                 trace["windows"] += 1
-            for e, (te, _) in enumerate(entries[i]):  # :1968 (every table entry has realignment support, :2924)
+            seen = []
+            this["own"].append(seen)
+            for e, (te, held_as) in enumerate(entries[i]):  # :1968 (every table entry has realignment support, :2924)
                 ev = table[te]
+                seen.append(dict(how_applied(ref_pos, ev["pos"], ev["type"], len(ev["seq"]), begin_padded + region_begin), t=te, read_pos=held_as))
                 if realign.apply_indel_event(new_ref, ref_pos, ev["pos"], ev["type"], ev["seq"], begin_padded + region_begin):  # :1975
                     applied_events.append((te, 0))                    # :1986
                     bits |= 2 << e
                 else:
                     applied_events.append((te, READ_ANTI_SUPPORT))    # :1999
+                seen[-1]["applied"] = bool(bits & (2 << e))
             old_score = read["score"]           # :2004
             window = "".join(new_ref)
             if len(sequences[i]) > MAX_READ or len(window) > MAX_TARGET:  # the stated limit
@@ -182,18 +218,29 @@ def is_good_indel(info, eps=7):
     return qd >= 3.5
 
 
+def as_the_reference_holds(info):
+    """the counters through the widths of the reference's EventSupport (event.hpp: uint16_t, max_mapq uint8_t): the library counts in
+    32 bits and reads through these (include/gtx.h: gtx_disc_second_decide)"""
+    return dict(info, **{f: info[f] & (0xFF if f == "max_mapq" else 0xFFFF) for f in ("hq_count", "lq_count", "anti_count", "multi_count", "sequence_reversed",
+                                                                                       "proper_pairs", "max_mapq")})
+
+
+def is_good_count(indel, info):
+    """:2187-2194 of one entry, its counters as the reference holds them"""
+    size = len(indel["seq"])
+    correction = float(size / 2.0 + 8.0) / 8.0 if indel["type"] == 'I' else float(size / 3.0 + 10.0) / 10.0  # :2187-2188
+    count = correction * (info["hq_count"] + info["lq_count"])                                               # :2190
+    return (info["hq_count"] >= 5 and count >= 5.5) or (info["span"] >= 5 and info["hq_count"] >= 4 and count >= 5.0) or \
+        (info["span"] >= 15 and info["hq_count"] >= 3 and count >= 4.5)                                      # :2192-2194
+
+
 def good_after(table, lst, support):
     """:2179-2229 -> per table entry: it had no good support and has it now (an entry that is good already is left alone)"""
     out = [False] * len(table)
     for t in lst:
-        indel, info = table[t], support[t]
+        indel, info = table[t], as_the_reference_holds(support[t])
         if indel["good"]:                       # :2184
             continue
-        size = len(indel["seq"])
-        correction = float(size / 2.0 + 8.0) / 8.0 if indel["type"] == 'I' else float(size / 3.0 + 10.0) / 10.0  # :2187-2188
-        count = correction * (info["hq_count"] + info["lq_count"])                                               # :2190
-        is_good_count = (info["hq_count"] >= 5 and count >= 5.5) or (info["span"] >= 5 and info["hq_count"] >= 4 and count >= 5.0) or \
-            (info["span"] >= 15 and info["hq_count"] >= 3 and count >= 4.5)                                      # :2192-2194
-        if is_good_count and is_good_indel(info):  # :2219
+        if is_good_count(indel, info) and is_good_indel(info):  # :2219
             out[t] = True
     return out

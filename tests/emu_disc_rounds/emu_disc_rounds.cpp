@@ -9,7 +9,10 @@
 // out.bin: uint32 status (0, or 5: the event array is too small), n_events, rounds_done, rounds_skipped, pairs_aligned,
 // pairs_refused, windows_built, compactions, events_wanted; n_reads gtx_disc_second_read; event_cap gtx_disc_second_event; n_table
 // gtx_disc_second_support; then per window built, in the order of the rounds and the slots: uint32 k, read (0xFFFFFFFF: the plain
-// window), n, n_entries; n letters; n int32 ref_pos values; n_entries applied flags.
+// window), n, n_entries, the W::mem_sync() calls of its build (a sequential wave cannot see what they order, it can count them); n letters; n int32 ref_pos values; n_entries applied flags.
+// A case.bin whose first word is 0xFFFFFFFF asks for the final decision instead: n_table (the fifth word) gtx_disc_indel and as many
+// gtx_disc_second_support follow the header; out.bin: per entry two bytes, disc_second_good_count and disc_second_good of the entry and its
+// counters.
 // Every array is a heap block of exactly its number of entries, the arena of a round exactly the sum of its slots: a load or a
 // store the kernels' bounds should have prevented stops the program.  The host's part -- the exclusive sums, the order of the
 // steps, the compaction's copy back -- is restated here with the standard library.
@@ -42,7 +45,8 @@ struct WaveSeq
       f(l);
   }
   static bool leader() { return true; }
-  static void mem_sync() {}
+  static inline uint64_t syncs = 0;
+  static void mem_sync() { ++syncs; }
   static uint32_t uni(uint32_t v) { return v; }
   static uint32_t from_lane(PerLane<uint32_t> const & p, uint32_t lane) { return p.v[lane]; }
   static void shift_up(PerLane<uint32_t> const & in, uint32_t first, PerLane<uint32_t> & out)
@@ -122,6 +126,25 @@ int main(int argc, char ** argv)
   int64_t region_begin = 0;
   if (!f || !read_exact(f, h, sizeof h) || !read_exact(f, &region_begin, 8))
     return 2;
+  if (h[0] == 0xFFFFFFFFu) // the final decision on counters of the caller's
+  {
+    uint32_t const n = h[4];
+    std::unique_ptr<gtx_disc_indel[]> entries;
+    std::unique_ptr<gtx_disc_second_support[]> counters;
+    if (!load(f, entries, n) || !load(f, counters, n))
+      return 2;
+    std::fclose(f);
+    auto good = block<uint8_t>(2 * static_cast<size_t>(n));
+    for (uint32_t t = 0; t < n; ++t)
+    {
+      good[2 * t] = disc_second_good_count(entries[t], counters[t]) ? 1 : 0;
+      good[2 * t + 1] = disc_second_good(entries[t], counters[t]) ? 1 : 0;
+    }
+    std::FILE * const o = std::fopen(argv[2], "wb");
+    if (!o || !store(o, good.get(), 2 * static_cast<size_t>(n)))
+      return 2;
+    return std::fclose(o) == 0 ? 0 : 2;
+  }
   uint32_t const plane_stride = h[0], n_reads = h[1], reference_len = h[2], bucket_size = h[3], n_table = h[4], n_table_seq = h[5], n_list = h[6], k0 = h[7], k1 = h[8],
                  event_cap = h[9];
   uint32_t count = h[10];
@@ -234,14 +257,19 @@ int main(int argc, char ** argv)
     auto arena_pos = block<int32_t>(letters);
     in.seq = arena_seq.get();
     in.refpos = arena_pos.get();
+    std::vector<uint32_t> syncs(static_cast<size_t>(n_pairs) + 1);
     for (uint32_t slot = 0; slot <= n_pairs; ++slot)
+    {
+      uint64_t const before = WaveSeq::syncs;
       rounds_window_wave<WaveSeq>(in, slot);
+      syncs[slot] = static_cast<uint32_t>(WaveSeq::syncs - before);
+    }
     for (uint32_t slot = 0; slot <= n_pairs; ++slot)
     {
       gtx_disc_second_read const * const r = slot ? &second[pairs[slot - 1].read] : nullptr;
-      if (slot != 0 && (r->n_events == 0 || ctl[ROUNDS_SKIPPED]))
+      if (slot != 0 && r->n_events == 0) // (a skipped round's windows are dumped too: the aligner is handed them all the same)
         continue;
-      uint32_t const head[4] = {k, slot ? pairs[slot - 1].read : 0xFFFFFFFFu, wlen[slot], r ? r->n_events : 0u};
+      uint32_t const head[5] = {k, slot ? pairs[slot - 1].read : 0xFFFFFFFFu, wlen[slot], r ? r->n_events : 0u, syncs[slot]};
       auto put = [&](void const * p, size_t n) { windows.insert(windows.end(), static_cast<uint8_t const *>(p), static_cast<uint8_t const *>(p) + n); };
       put(head, sizeof head);
       put(in.seq + woff[slot], wlen[slot]);

@@ -182,7 +182,15 @@ def test_final_decision_on_hand_made_counters():
     assert ref.get_log_qual(7, 25, 7) * 3 == 51 and ref.get_log_qual(7, 26, 7) * 3 == 48
     assert not by["3 * log_qual at anti 25"] and not by["3 * log_qual at anti 26"]
     assert by["qual / depth at multi 34"] and by["qual / depth at multi 35"] and not by["qual / depth at multi 36"]
-    assert not by["good already"]
+    assert not by["good already"] and not by["log_qual floor at anti 100"] and ref.get_log_qual(10, 100, 7) == 0
+    # the widths: every such row turns round when its counter is read at 32 bits, and has the value the narrow reading gives
+    wide = {what: ref.is_good_count(e, s) and ref.is_good_indel(s) for e, s, what in ROWS}
+    narrow = [what for what in by if "65536" in what or "256 +" in what]
+    assert len(narrow) == 9 and all(by[what] != wide[what] for what in narrow if what not in ("hq_count 65536 + 10 multi 50", "hq 7 max_mapq 256 + 11", "hq_count 65536 + 4 count 4.5"))
+    e, s4, _ = next(r for r in ROWS if r[2] == "hq_count 65536 + 4 count 4.5")
+    assert ref.is_good_count(e, s4) and not ref.is_good_count(e, ref.as_the_reference_holds(s4))
+    assert not by["hq_count 65536 + 10 multi 51"] and by["hq_count 65536 + 10 multi 50"] and by["anti_count 65536"] and by["multi_count 65536"]
+    assert by["sequence_reversed 65536 + 5"] and not by["proper_pairs 65536 + 4"] and not by["hq 7 max_mapq 256 + 10"] and by["hq 7 max_mapq 256 + 11"]
     # an entry outside the list is left alone too
     none = gtx.disc_second_decide(entries, np.zeros(0, np.uint32), rc.support_array(support))
     assert not none.any()
@@ -198,3 +206,154 @@ def test_the_count_lies_on_its_edges():
     for kind, size, hq, span, arm in (('D', 15, 3, 15, True), ('D', 15, 3, 14, False), ('I', 4, 4, 5, True), ('I', 4, 4, 4, False), ('D', 3, 5, 1, True), ('D', 2, 5, 1, False)):
         c = count(kind, size, hq)
         assert ((hq >= 5 and c >= 5.5) or (span >= 5 and hq >= 4 and c >= 5.0) or (span >= 15 and hq >= 3 and c >= 4.5)) == arm
+    # the rows that show the arms through is_good_count: every bound of every arm has a row on it and one to the side that fails
+    arm = {what: ref.is_good_count(e, s) for e, s, what in ROWS if what.startswith("arm ")}
+    assert [what for what, good in arm.items() if good] == ["arm 2 span 5 hq 4 count 5.0", "arm 3 span 15 hq 3 count 4.5", "arm 1 span 4 hq 5 count 5.5"]
+    assert len(arm) == 15 and count('I', 12, 3) == 5.25 and count('D', 39, 2) >= 4.5 > count('D', 14, 3) and count('D', 2, 5) < 5.5
+
+
+# ---- the sets made for the windows' text ------------------------------------------------------------------------------------------------
+def own_entries(case):
+    """[(k, read, outcome, the table's entry, what the restatement saw in front of its apply_indel_event)] of every entry of a read's own"""
+    want = rc.expected(case)
+    return [(r["k"], i, outcome, case.table[x["t"]], x) for r in want["trace"]["rounds"] for (i, outcome, _, _), own in zip(r["visits"], r["own"]) for x in own]
+
+
+def moving_steps(kind, index, size, n):
+    """the steps of apply_event's moving loop over a window of n letters: 64 entries a step (gtx_disc_rounds_dev.hpp)"""
+    return -(-(n - size - index) // 64) if kind == 'D' else -(-(n - index) // 64)
+
+
+def test_copies_apply_every_size_as_entry_k_and_as_an_own_entry():
+    applied_k, applied_own, after, steps = set(), set(), set(), {'D': 0, 'I': 0}
+    for case in rc.cases("copies"):
+        want = rc.expected(case)
+        for r in want["trace"]["rounds"]:
+            e = case.table[want["lst"][r["k"]]]
+            if not r["skipped"]:
+                applied_k.add((e["type"], len(e["seq"])))
+                plain = min(len(case.reference), e["pos"] + 200) - max(0, e["pos"] - 200)
+                after.add(((plain - len(e["seq"]) if e["type"] == 'D' else plain + len(e["seq"])) % 64, e["type"], len(e["seq"])))
+        for k, i, _, e, x in own_entries(case):
+            if x["applied"]:
+                applied_own.add((e["type"], len(e["seq"])))
+                n = next(v[3] for v in want["trace"]["rounds"][k]["visits"] if v[0] == i)  # the window behind every event
+                before = n + len(e["seq"]) if e["type"] == 'D' else n - len(e["seq"])      # (the large event is the last applied)
+                steps[e["type"]] = max(steps[e["type"]], moving_steps(e["type"], x["index"], len(e["seq"]), before))
+    every = {(kind, size) for kind in "DI" for size in rc.COPY_SIZES}
+    assert applied_k >= every and applied_own >= every
+    assert after >= {(over % 64, kind, size) for over in (-1, 0, 1) for kind in "DI" for size in (63, 64, 65)}
+    assert min(steps.values()) >= 3
+    # an insertion of a read's own at the window's last index; the same entry behind a deletion: its position is no index any more
+    def window(case, k, i):  # the letters of read i's window in round k, every event applied
+        return next(v[3] for v in rc.expected(case)["trace"]["rounds"][k]["visits"] if v[0] == i)
+    at_length, last, outside, one_left = rc.cases("copies")[-4:]
+    assert any(x["search"] == "outside" and e["pos"] - 252 == window(at_length, k, i) for k, i, _, e, x in own_entries(at_length))  # pos == seq_size
+    one_step = rc.cases("copies")[-5]
+    assert len(one_step.reference) - 300 == 64 and rc.expected(one_step)["trace"]["rounds"][0]["visits"][0][1] == ref.realign.WORSE
+    assert any(x["applied"] and e["type"] == 'I' and x["index"] == window(last, k, i) - len(e["seq"]) - 1 for k, i, _, e, x in own_entries(last))
+    assert {x["search"] for *_, x in own_entries(outside)} == {"outside"}
+    assert any(x["applied"] and e["type"] == 'D' and x["index"] + 1 == window(one_left, k, i) for k, i, _, e, x in own_entries(one_left))
+
+
+def test_search_takes_every_exit():
+    seen, sides = set(), set()
+    for case in rc.cases("search"):
+        want = rc.expected(case)
+        for k, i, _, e, x in own_entries(case):
+            seen.add((x["search"], e["type"]))
+            if x["applied"]:
+                sides.add((e["type"], "in front" if e["pos"] < case.table[want["lst"][k]]["pos"] else "behind"))
+    assert seen >= {(how, kind) for how in ("at once", "walked forward", "walked back", "not found") for kind in "DI"}
+    assert sides == {(kind, side) for kind in "DI" for side in ("in front", "behind")}
+    # two entries of the read's own in front of a third: found 3 + 2 (theirs) + 2 (entry k's) indices in front of its position
+    case = rc.cases("search")[3]
+    k, i, _, e, x = own_entries(case)[-1]
+    assert e["type"] == 'I' and x["search"] == "walked back" and (e["pos"] - 132) - x["index"] == 7
+    # the walk forward crosses the letters entry k put in: it begins among them
+    case = rc.cases("search")[2]
+    k_entry = case.table[rc.expected(case)["lst"][2]]
+    assert any(x["search"] == "walked forward" and k_entry["pos"] < e["pos"] < k_entry["pos"] + len(k_entry["seq"]) for *_, e, x in own_entries(case))
+    # not found: by a deletion of entry k, and by a deletion of the read's own
+    assert [x["search"] for *_, x in own_entries(rc.cases("search")[4]) if not x["applied"]][-2:] == ["not found"] * 2
+    assert [(x["search"], x["applied"]) for *_, x in own_entries(rc.cases("search")[5])][-2:] == [("at once", True), ("not found", False)]
+
+
+def test_own_ends_fail_and_hold_by_either_arm():
+    seen = set()
+    for n, case in enumerate(rc.cases("own_ends")):
+        want = rc.expected(case)
+        for k, i, outcome, e, x in own_entries(case):
+            assert e["type"] == 'D' and x["pure"]
+            arm = "past" if x["past"] else "differs" if x["differs"] else "holds"
+            seen.add((n, arm, x["read_pos"], rc.OUTCOME[outcome]))
+            assert x["applied"] == (arm == "holds")
+            if not x["applied"] and outcome == ref.realign.BETTER:  # the refused entry goes into the new list as anti-support
+                assert want["before"][k + 1][1][i] == [(want["lst"][k], 0), (x["t"], -1)]
+                held, now = want["before"][k][2][x["t"]], want["before"][k + 1][2][x["t"]]
+                if x["read_pos"] == 0:
+                    assert now["hq_count"] < held["hq_count"] and now["anti_count"] > held["anti_count"] and now["max_mapq"] == held["max_mapq"]
+    # one letter in front of the window's last: the end test holds; on it and one past it: the first arm; over an insertion and over a
+    # deletion that entry k applied: the second.  Each with the entry held as support (0), as anti-support (-1) and as multi-support
+    assert {(n, arm) for n, arm, _, _ in seen} == {(0, "holds"), (1, "past"), (2, "past"), (3, "differs"), (4, "differs")}
+    for n in (1, 2, 3, 4):
+        assert {(p, o) for m, _, p, o in seen if m == n} >= {(0, "BETTER"), (-1, "BETTER"), (-1, "WORSE")}
+    case = rc.cases("own_ends")[1]
+    t, k = (case.table[e] for e in rc.expected(case)["lst"])
+    assert t["pos"] + len(t["seq"]) == k["pos"] + 200 < len(case.reference)  # the deletion ends with k's window, inside the region
+    assert any(info["max_mapq"] == 254 and info["hq_count"] == 0 for c in rc.cases("own_ends") for info in rc.expected(c)["support"])
+
+
+def test_purity_at_the_windows_ends_and_behind_an_applied_entry():
+    cs = rc.cases("purity")
+    first = {(x["index"], x["applied"]) for c in cs[:6] for *_, x in own_entries(c)}
+    assert first == {(1, True), (2, True), (3, True)} and {c.region_begin for c in cs[:6]} == {0, 3000}
+    last = set()
+    for c in cs[6:11]:
+        want = rc.expected(c)
+        for k, i, _, e, x in own_entries(c):
+            n = next(v[3] for v in want["trace"]["rounds"][k]["visits"] if v[0] == i)
+            before = n + len(e["seq"]) if e["type"] == 'D' else n - len(e["seq"])
+            last.add((before - x["index"], e["type"], x["applied"]))
+    assert last == {(3, 'I', True), (3, 'D', True), (2, 'I', True), (2, 'D', True), (1, 'I', True)}
+    behind = [[(x["pure"], x["applied"]) for *_, x in own_entries(c)] for c in cs[11:19]]
+    assert behind[0::2] == [[(False, False)]] * 3 + [[(True, True)]] and behind[1::2] == [[(False, False)]] * 3 + [[(True, True)]]
+    assert [rc.expected(c)["lst"] for c in cs[11:19]] == [[1, 0]] * 8  # the entry behind is the read's own, the one in front entry k
+    # three and two positions in front of a deletion that entry k applied: pos + 3 is the first index the test does not look at
+    assert [[(x["search"], x["pure"], x["applied"]) for *_, x in own_entries(c)] for c in cs[19:]] == [[("at once", True, True)], [("at once", False, False)]]
+
+
+def test_fields_of_a_read_made_better_and_max_mapq():
+    first, lets_go, sole, far, alone, left = rc.cases("fields")
+    want = rc.expected(alone)
+    assert want["trace"]["rounds"] == [dict(k=0, skipped=True, visits=[], own=[])] and alone.table[0]["pos"] + 4 == len(alone.reference)
+    assert [rc.OUTCOME[v[1]] for v in rc.expected(left)["trace"]["rounds"][0]["visits"]] == ["SAME_OVERLAPPING", "SAME_OVERLAPPING", "SAME"]
+    assert left.region_begin == 7 and [r["pos"] - left.table[0]["pos"] for r in left.reads] == [6, 7, 8]
+    rounds = rc.expected(far)["trace"]["rounds"]
+    assert rc.expected(far)["lst"] == [0, 1] and far.table[0]["pos"] + 200 < far.region_begin and [r["skipped"] for r in rounds] == [True, False]
+    want = rc.expected(first)
+    ins = first.table[0]
+    assert ins["pos"] == len(first.reference) - 1 and [s["num_clipped_end"] for s in want["states"]] == [40, 0]
+    s = want["states"][1]
+    n = want["trace"]["rounds"][0]["visits"][1][3]
+    # the alignment begins on the second inserted letter: the run of equal ref_pos values goes on to the window's last index, where
+    # the loop's bound stops it (51 steps: 50 inserted letters and the region's last base)
+    assert s["num_ins_begin"] == len(ins["seq"]) - 1 == 51 and s["num_clipped_begin"] == 10 and n == 201 + 52
+    assert max(x["num_ins_begin"] for c in (lets_go, sole) for x in rc.expected(c)["states"]) == 0
+    want = rc.expected(lets_go)
+    assert lets_go.reads[2]["mapq"] == 254 and [want["before"][k][2][0]["hq_count"] for k in (1, 2)] == [1, 0]
+    assert [want["before"][k][2][0]["max_mapq"] for k in (1, 2)] == [254, 254] and want["entries"][2] == [(1, 0), (0, -1)]
+    want = rc.expected(sole)
+    assert sole.reads[4]["mapq"] == 255 and want["support"][0]["hq_count"] == 1 and want["support"][0]["max_mapq"] == 0
+
+
+def test_the_long_limits_change_nothing_of_the_new_sets():
+    """no new read has more than 256 bases and no new window more than 2 048 letters: an object with max_read_len 1 000 gives the same"""
+    import disc_rounds_long_cases as lr
+    for name in NEW_SETS:
+        for case in rc.cases(name):
+            by_default, by_long = rc.expected(case), lr.expected_long(case)
+            assert by_default["trace"]["refused"] == 0 and all(by_default[f] == by_long[f] for f in ("states", "entries", "support", "trace", "good"))
+
+
+NEW_SETS = ("copies", "search", "own_ends", "purity", "fields")

@@ -153,6 +153,46 @@ def test_the_event_array_exactly_large_enough_and_one_entry_short():
         run.close()
 
 
+@pytest.mark.parametrize("k", range(len(rc.cases("copies"))))
+def test_copies_in_an_array_exactly_large_enough_and_one_entry_short(k):
+    """the host driver's part -- capacity, where the scan places the lists, when it compacts -- for lists that a window of up to 130
+    copied letters made: max(live + new) entries are enough, one fewer stops in front of the round that does not fit, with
+    events_wanted and the state in front of it, and the call goes on in a larger array"""
+    case = rc.cases("copies")[k]
+    want, room = rc.expected(case), rc.room(case)
+    n_list, need = len(want["lst"]), max(live + new for live, new in room)
+    whole(case, cap=need)
+    run = Run(case)
+    try:
+        run.begin(need - 1)
+        stop = next(k_ for k_, (live, new) in enumerate(room) if live + new > need - 1)
+        status, stats = run.rounds(0, n_list)
+        assert status == 5 and stats["rounds_done"] == stop and stats["events_wanted"] == sum(room[stop]) and run.differs(at=stop) is None
+        run.grow(need)
+        status, stats = run.rounds(stop, n_list)
+        assert status == 0 and stats["rounds_done"] == n_list - stop and run.differs() is None
+    finally:
+        run.close()
+
+
+def test_own_ends_slices_equal_the_whole_run():
+    """the own_ends lists cannot come out of lib.disc_second_file (its list is the plan's, not the set's), so they go through
+    gtx_disc_second_rounds directly: one call, and a call per round, leave the same bytes"""
+    for case in rc.cases("own_ends"):
+        n_list = len(rc.expected(case)["lst"])
+        one = whole(case)
+        run = Run(case)
+        try:
+            run.begin(sum(new for _, new in rc.room(case)))
+            for k in range(n_list):
+                status, _ = run.rounds(k, k + 1)
+                assert status == 0 and run.differs(at=k + 1) is None
+            second, events, support = run.state()
+            assert (second.tobytes(), events[:run.used].tobytes(), support.tobytes(), run.used) == one[:4]
+        finally:
+            run.close()
+
+
 def test_a_stream_of_the_callers():
     import torch
     whole(rc.cases("chain")[1], stream=torch.cuda.Stream().cuda_stream)

@@ -21,8 +21,9 @@ from test_gpu_disc_second import first_pass_words
 pytestmark = pytest.mark.gpu
 
 
-def whole(case, long_mode):
-    """the intake and all rounds, twice over fresh arrays, on an object in the mode -> the statistics and the good-bits"""
+def whole(case, long_mode, keep=None):
+    """the intake and all rounds, twice over fresh arrays, on an object in the mode -> the statistics and the good-bits (keep: a list
+    that takes the bytes the run left)"""
     want = lr.expected_long(case) if long_mode else rc.expected(case)
     trace, n_list = want["trace"], len(want["lst"])
     cap = sum(new for _, new in (lr.room_long(case) if long_mode else rc.room(case)))
@@ -44,6 +45,8 @@ def whole(case, long_mode):
             assert good == want["good"]
             seen.append((second.tobytes(), events[:run.used].tobytes(), support.tobytes(), run.used))
         assert seen[0] == seen[1]
+        if keep is not None:
+            keep.append(seen[0])
     finally:
         run.close()
     return stats, good
@@ -62,6 +65,16 @@ def test_nobody_is_refused_on_a_long_mode_object(name):
 def test_a_default_object_refuses_what_it_did(name):
     stats, _ = whole(CASES[name], False)
     assert stats["pairs_refused"] > 0
+
+
+@pytest.mark.parametrize("name", ("copies", "search", "own_ends", "purity", "fields"))
+def test_the_sets_of_short_reads_leave_the_same_bytes_in_both_modes(name):
+    """no read of these sets has more than 256 bases and no window more than 2 048 letters: a long-mode object refuses nobody either and
+    leaves byte for byte what a default object leaves (test_disc_rounds_cases.py: the two restatements agree)"""
+    for case in rc.cases(name):
+        kept = []
+        (by_long, good_long), (by_default, good_default) = whole(case, True, kept), whole(case, False, kept)
+        assert by_long == by_default and good_long == good_default and kept[0] == kept[1] and by_long["pairs_refused"] == 0
 
 
 def test_the_good_bits_depend_on_the_long_pairs():
