@@ -1,5 +1,6 @@
 // gtx_disc.hpp -- the discovery object of include/gtx.h, for the translation units that hold its entry points (gtx_discover.hip:
-// the first pass; gtx_realign.hip: the realignment to the indels; gtx_disc_second.hip: the second pass up to the aligner).
+// the first pass; gtx_realign.hip: the realignment to the indels; gtx_disc_second.hip: the second pass up to the aligner;
+// gtx_disc_rounds.hip: from the aligner on; gtx_discover_run.hip: the host loops).  Host code without HIP: gtx_disc_region.hpp.
 #pragma once
 #include <cstdint>
 #include <string>

@@ -30,6 +30,7 @@
 #include "gtx_devmem.hpp"
 #include "gtx_devprim.hpp"
 #include "gtx_disc.hpp"
+#include "gtx_disc_region.hpp"
 #include "gtx_disc_events_dev.hpp"
 #include "gtx_disc_second_dev.hpp"
 #include "gtx_disc_support.hpp"
@@ -93,6 +94,13 @@ extern "C" int gtx_disc_create(const char * reference, uint64_t reference_len, i
   }
   *out = d.release();
   return GTX_OK;
+}
+
+void gtx::disc_region(gtx_disc const * d, char const ** reference, uint64_t * reference_len, int64_t * region_begin) // (gtx_disc_region.hpp)
+{
+  *reference = d->reference.data();
+  *reference_len = d->reference.size();
+  *region_begin = d->region_begin;
 }
 
 extern "C" void gtx_disc_destroy(gtx_disc * d)

@@ -10,6 +10,7 @@
 // The calls of an SV graph take another road (sv_graph_records below: reformat_sv_vcf_records and what genotype_sv's merge does).
 // Not built: variant break-down and the merge of pools (vcf_operations.cpp).
 #include "gtx_ctx.hpp"
+#include "gtx_vcf_text.hpp"
 
 #include <algorithm>
 #include <charconv>
@@ -46,17 +47,8 @@ struct Binned
 };
 const Binned BINNED;
 
-void put_u(std::string & s, uint64_t v) // (most of a VCF line is small integers: digits by hand, not through printf)
-{
-  char b[24];
-  int n = 24;
-  do
-  {
-    b[--n] = static_cast<char>('0' + v % 10);
-    v /= 10;
-  } while (v != 0);
-  s.append(b + n, static_cast<size_t>(24 - n));
-}
+using gtx::put_u; // (gtx_vcf_text.hpp: the number writer and variant_type, shared with gtx_disc_variants.cpp)
+using gtx::variant_type;
 
 // ostream << double at that precision, default float format (= printf's %.*g).  Most of what a record holds is a whole number
 // below 10^precision, which that format writes as its digits; the rest goes through std::to_chars, which is specified to give
@@ -252,21 +244,6 @@ struct Info // the reference's std::map<std::string, std::string> of a record: k
     return order;
   }
 };
-
-// Variant::determine_variant_type (variant.cpp:1430-1520) for the alleles of a graph without SV alleles
-const char * variant_type(std::vector<std::pair<const char *, uint32_t>> const & seqs)
-{
-  size_t longer = 0;
-  for (auto const & s : seqs)
-    longer += s.second > 1;
-  if (longer == 0)
-    return "SG";
-  if (seqs.size() - longer == 1)
-    return "IG";
-  if (seqs.size() - longer == 2 && seqs.back().second == 1 && seqs.back().first[0] == '*')
-    return "IG";
-  return "XG";
-}
 } // namespace
 
 

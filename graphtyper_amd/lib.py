@@ -36,7 +36,9 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_disc_first_pass_device", "gtx_disc_first_pass_haplotypes_device",
            "gtx_disc_realign_batch", "gtx_disc_set_max_read_len", "gtx_disc_realign_wants", "gtx_disc_realign_target", "gtx_disc_realign_decide",
            "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates",
-           "gtx_disc_second_rounds", "gtx_disc_second_decide"]
+           "gtx_disc_second_rounds", "gtx_disc_second_decide",
+           "gtx_disc_variants", "gtx_disc_vcf_sites", "gtx_disc_second_file", "gtx_discover_params_default", "gtx_discover_region", "gtx_discover_destroy",
+           "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats"]
 
 
 class GraphView(C.Structure):
@@ -149,6 +151,25 @@ class DiscRoundsStats(C.Structure):
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 REALIGN_NO_PADDING, REALIGN_BETTER, REALIGN_SAME_OVERLAPPING, REALIGN_SAME, REALIGN_WORSE = 0, 1, 2, 3, 4
+# discovery to its end (gtx.h: gtx_disc_variants .. gtx_discover_region)
+DISC_VARIANT = np.dtype([("pos", np.uint32), ("gt_id", np.uint32), ("ref_off", np.uint32), ("ref_len", np.uint32), ("alt_off", np.uint32), ("alt_len", np.uint32),
+                         ("hap_off", np.uint32), ("n_hap", np.uint32), ("anti_off", np.uint32), ("n_anti", np.uint32), ("type", np.uint8), ("reserved", np.uint8, 3)],
+                        align=True)
+assert DISC_VARIANT.itemsize == 44
+
+
+class DiscFile(C.Structure):
+    _fields_ = [("planes", C.c_void_p), ("qual", C.c_void_p), ("reads", C.c_void_p), ("cigar", C.c_void_p), ("plane_stride", C.c_uint32),
+                ("qual_stride", C.c_uint32), ("n_reads", C.c_uint32), ("n_cigar", C.c_uint32)]
+
+
+class DiscoverParams(C.Structure):
+    _fields_ = [("device", C.c_int32), ("bucket_size", C.c_uint32), ("max_read_len", C.c_uint32), ("n_threads", C.c_uint32), ("first_event_cap", C.c_uint32),
+                ("second_event_cap", C.c_uint32)]
+
+
+class DiscoverFileStats(C.Structure):
+    _fields_ = [("events", C.c_uint64), ("events_passes", C.c_uint32), ("n_list", C.c_uint32), ("rounds", DiscRoundsStats)]
 
 
 def build(force=False):
@@ -264,6 +285,30 @@ def lib():
                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DiscRoundsStats), C.c_void_p]
         L.gtx_disc_second_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.gtx_disc_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.gtx_disc_vcf_sites.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_uint64,
+                                         C.POINTER(C.c_uint64)]
+        L.gtx_disc_second_file.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(DiscRoundsStats), C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]
+        L.gtx_discover_params_default.argtypes = [C.POINTER(DiscoverParams)]
+        L.gtx_discover_params_default.restype = None
+        L.gtx_discover_region.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(DiscFile), C.c_uint32, C.POINTER(DiscoverParams),
+                                          C.POINTER(C.c_void_p)]
+        L.gtx_discover_destroy.argtypes = [C.c_void_p]
+        L.gtx_discover_destroy.restype = None
+        L.gtx_discover_text.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.gtx_discover_text.restype = C.c_void_p
+        L.gtx_discover_variants.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_uint64)]
+        L.gtx_discover_variants.restype = C.c_void_p
+        L.gtx_discover_words.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.gtx_discover_words.restype = C.c_void_p
+        L.gtx_discover_good.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.gtx_discover_good.restype = C.c_void_p
+        L.gtx_discover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.gtx_discover_stats.restype = C.POINTER(DiscoverFileStats)
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []
@@ -660,6 +705,115 @@ def disc_second_file(handle, reference_len, planes, plane_stride, reads, cigar, 
     support = d_support.cpu().numpy()[:nt * DISC_SECOND_SUPPORT.itemsize].view(DISC_SECOND_SUPPORT).copy()
     lists = [[(int(e["indel"]), int(e["read_pos"])) for e in events[r["first_event"]:r["first_event"] + r["n_events"]]] for r in second]
     return dict(entries=entries, letters=letters, lst=lst, good=disc_second_decide(entries, lst, support), second=second, lists=lists, support=support, stats=total)
+
+
+def disc_second_file_c(handle, d_planes, plane_stride, d_reads, d_cigar, n_reads, words, file_index, bucket_size=50, event_cap=0, stream=None, state=True):
+    """gtx_disc_second_file: a file's whole second pass in one call of the library, over device arrays of the caller's (pointers as
+    integers) and the merged `words` -> what disc_second_file returns without entries and letters; state=False leaves second, lists and
+    support out (the optional outputs are not asked for)."""
+    L = lib()
+    words = np.ascontiguousarray(words, np.uint32)
+    nt, n_seq = C.c_uint32(), C.c_uint64()
+    rc = L.gtx_disc_indel_table(_p(words), len(words), None, 0, C.byref(nt), None, 0, C.byref(n_seq))
+    if rc not in (0, 5):
+        check(rc)
+    nt = nt.value
+    bits, lst, n_list, stats = np.zeros(max((nt + 31) // 32, 1), np.uint32), np.zeros(max(nt, 1), np.uint32), C.c_uint32(), DiscRoundsStats()
+    second, support = np.zeros(max(n_reads, 1), DISC_SECOND_READ), np.zeros(max(nt, 1), DISC_SECOND_SUPPORT)
+    events_cap, n_events = max(4 * n_reads, 1024), C.c_uint32()
+    while True:
+        events = np.zeros(events_cap, DISC_SECOND_EVENT)
+        rc = L.gtx_disc_second_file(handle, d_planes, plane_stride, d_reads, d_cigar, n_reads, _p(words), len(words), file_index, bucket_size, event_cap, _p(bits),
+                                    _p(lst), len(lst), C.byref(n_list), C.byref(stats), _p(second) if state else None, _p(events) if state else None,
+                                    events_cap if state else 0, C.byref(n_events) if state else None, _p(support) if state else None, stream)
+        if rc == 5 and state and n_events.value > events_cap:  # (the lists are an output of unknown size: the run is repeated for them alone)
+            events_cap = n_events.value
+            continue
+        check(rc)
+        break
+    stats = stats.as_dict()
+    stats.pop("events_wanted")
+    out = dict(lst=lst[:n_list.value].copy(), good=np.array([(bits[t >> 5] >> (t & 31)) & 1 for t in range(nt)], bool), stats=stats)
+    if state:
+        second, events = second[:n_reads], events[:n_events.value]
+        out.update(second=second, support=support[:nt],
+                   lists=[[(int(e["indel"]), int(e["read_pos"])) for e in events[r["first_event"]:r["first_event"] + r["n_events"]]] for r in second])
+    return out
+
+
+def disc_variants(handle, words, good_bits=None):
+    """gtx_disc_variants: the merged words and the files' ORed good-bits (uint32 words, or None) -> (DISC_VARIANT array, letters as bytes,
+    ids as a uint32 array)"""
+    L = lib()
+    words = np.ascontiguousarray(words, np.uint32)
+    bits = None if good_bits is None else np.ascontiguousarray(good_bits, np.uint32)
+    n, n_letters, n_ids = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    rc = L.gtx_disc_variants(handle, _p(words), len(words), _p(bits), None, 0, C.byref(n), None, 0, C.byref(n_letters), None, 0, C.byref(n_ids))
+    if rc not in (0, 5):
+        check(rc)
+    recs, letters, ids = np.zeros(max(n.value, 1), DISC_VARIANT), np.zeros(max(n_letters.value, 1), np.uint8), np.zeros(max(n_ids.value, 1), np.uint32)
+    check(L.gtx_disc_variants(handle, _p(words), len(words), _p(bits), _p(recs), n.value, C.byref(n), _p(letters), n_letters.value, C.byref(n_letters), _p(ids),
+                              n_ids.value, C.byref(n_ids)))
+    return recs[:n.value], letters[:n_letters.value].tobytes(), ids[:n_ids.value]
+
+
+def disc_vcf_sites(recs, letters, ids, contig):
+    """gtx_disc_vcf_sites: records as disc_variants returns them and a contig name -> the text of the sites file behind its header (bytes)"""
+    L = lib()
+    recs, ids = np.ascontiguousarray(recs, DISC_VARIANT), np.ascontiguousarray(ids, np.uint32)
+    letters = np.frombuffer(bytes(letters), np.uint8)
+    n = C.c_uint64()
+    args = (_p(recs) if len(recs) else None, len(recs), _p(letters) if len(letters) else None, len(letters), _p(ids) if len(ids) else None, len(ids), contig.encode())
+    rc = L.gtx_disc_vcf_sites(*args, None, 0, C.byref(n))
+    if rc not in (0, 5):
+        check(rc)
+    buf = C.create_string_buffer(int(n.value) + 1)
+    check(L.gtx_disc_vcf_sites(*args, buf, int(n.value), C.byref(n)))
+    return buf.raw[:int(n.value)]
+
+
+def discover_region(reference, region_begin, contig, files, device=0, bucket_size=50, max_read_len=0, n_threads=1, first_event_cap=0, second_event_cap=0):
+    """gtx_discover_region: a region's discovery from host arrays to the sites file.  reference: the region's letters (str or bytes);
+    files: per file a dict(planes, plane_stride, qual, qual_stride, reads [DISC_READ], cigar [uint32]) of numpy arrays as
+    gtx_disc_events_batch takes them.
+    -> dict(text [bytes], variants [DISC_VARIANT], letters [bytes], ids [uint32], words [uint32], good [bool per table entry],
+            stats [per file: dict(events, events_passes, n_list, rounds)])"""
+    L = lib()
+    refb = reference.encode("latin-1") if isinstance(reference, str) else bytes(reference)
+    keep, structs = [], (DiscFile * max(len(files), 1))()
+    for i, f in enumerate(files):
+        planes, qual = np.ascontiguousarray(f["planes"]).view(np.uint8).reshape(-1), np.ascontiguousarray(f["qual"]).view(np.uint8).reshape(-1)  # (bytes as they lie)
+        reads, cigar = np.ascontiguousarray(f["reads"], DISC_READ), np.ascontiguousarray(f["cigar"], np.uint32)
+        if planes.size != len(reads) * int(f["plane_stride"]) or qual.size != len(reads) * int(f["qual_stride"]):
+            raise ValueError("discover_region: file %d: the rows do not have the strides' sizes" % i)
+        keep.append((planes, qual, reads, cigar))
+        structs[i] = DiscFile(planes.ctypes.data if planes.size else None, qual.ctypes.data if qual.size else None, reads.ctypes.data if len(reads) else None,
+                              cigar.ctypes.data if len(cigar) else None, int(f["plane_stride"]), int(f["qual_stride"]), len(reads), len(cigar))
+    params = DiscoverParams()
+    L.gtx_discover_params_default(C.byref(params))
+    params.device, params.bucket_size, params.max_read_len, params.n_threads = device, bucket_size, max_read_len, n_threads
+    params.first_event_cap, params.second_event_cap = first_event_cap, second_event_cap
+    h = C.c_void_p()
+    check(L.gtx_discover_region(refb, len(refb), region_begin, contig.encode(), structs, len(files), C.byref(params), C.byref(h)))
+    try:
+        def view(ptr, dtype, count):
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+        n64, n32, letters, n_letters, ids, n_ids = C.c_uint64(), C.c_uint32(), C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        ptr = L.gtx_discover_text(h, C.byref(n64))
+        out = dict(text=C.string_at(ptr, n64.value) if n64.value else b"")
+        ptr = L.gtx_discover_variants(h, C.byref(n32), C.byref(letters), C.byref(n_letters), C.byref(ids), C.byref(n_ids))
+        out.update(variants=view(ptr, DISC_VARIANT, n32.value), letters=view(letters.value, np.uint8, n_letters.value).tobytes(),
+                   ids=view(ids.value, np.uint32, n_ids.value))
+        ptr = L.gtx_discover_words(h, C.byref(n64))
+        out["words"] = view(ptr, np.uint32, n64.value)
+        ptr = L.gtx_discover_good(h, C.byref(n32))
+        out["good"] = view(ptr, np.uint8, n32.value).astype(bool)
+        st = L.gtx_discover_stats(h, C.byref(n32))
+        out["stats"] = [dict(events=int(st[i].events), events_passes=int(st[i].events_passes), n_list=int(st[i].n_list), rounds=st[i].rounds.as_dict())
+                        for i in range(n32.value)]
+        return out
+    finally:
+        L.gtx_discover_destroy(h)
 
 
 def disc_realign_target(handle, max_read_size, events):

@@ -1052,8 +1052,9 @@ int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const 
  * reads to the indels (gtx_disc_realign_*, at the end of this header: the aligner, the haplotype windows, the per-pair decisions).
  * The second pass up to the aligner -- the indel table, the intake of a file's reads, the buckets, the file's list and the reads of
  * an indel's round -- is gtx_disc_indel_table / gtx_disc_second_* (at the end of this header).
- * Not built: the sequential driver of the realignment, which feeds a read's new state into the next indel's round
- * (replace_indel_events), the final good-support decision (caller.cpp:2179-2229) and the variant records (:2985-3092).
+ * The rounds of the realignment and the final good-support decision are gtx_disc_second_rounds / gtx_disc_second_decide, the variant
+ * records and the sites file gtx_disc_variants / gtx_disc_vcf_sites, a file's second pass and a whole region in one call
+ * gtx_disc_second_file / gtx_discover_region (all at the end of this header).
  *   gtx_disc_create        the region's reference (upper-case letters; reference[0] = contig position region_begin, 0-based) on `device`
  *   gtx_disc_events_batch  device: the events of n_reads reads in stream order.  d_planes: the reads as plane rows (gtx_pack_planes),
  *                          d_qual: their base qualities (qual_stride bytes per read), d_reads / d_cigar: the bam1_t fields and the raw
@@ -1260,7 +1261,7 @@ int gtx_disc_realign_decide(const gtx_disc_realign_result * result, uint32_t rea
  * The sequential driver (replace_indel_events: a read's new state entering the next indel's round) and the final good-support
  * decision (:2179-2229) are gtx_disc_second_rounds and gtx_disc_second_decide, below; the layout here is what that driver updates:
  * the reads' state (gtx_disc_second_read) and their entries {table index, read_pos} (gtx_disc_second_event).
- * NOT BUILT: the variant records (:2985-3092).
+ * The variant records (:2985-3092) are gtx_disc_variants, at the end of this header.
  *
  * What the reference's text does, where its comments suggest otherwise: the file's buckets are made new (:2649-2650), so the
  * EventSupport that add_indel_event_to_bucket inserts has no realignment support and EVERY I and D operation that reaches the
@@ -1365,8 +1366,7 @@ int gtx_disc_second_candidates(gtx_disc *, const uint32_t * d_list, uint32_t k0,
 /* ---- discovery's second pass from the aligner on: the rounds of realign_to_indels (src/typer/caller.cpp:1876-2171), the support
  * counters of Alignment::add_indel_event / replace_indel_events (src/typer/read.cpp:29-116) and the good-support decision at the
  * end (:2179-2229).  With gtx_disc_indel_table, gtx_disc_second_intake and gtx_disc_second_plan this is a file's whole second pass
- * up to the good-bits.  NOT BUILT: the variant records (:2985-3092), which go through Variant::add_base_in_front and the global
- * graph and read exactly these good-bits.
+ * up to the good-bits, which the variant records (:2985-3092; gtx_disc_variants, below) read.
  *   gtx_disc_second_rounds  device, on `stream`: the rounds of the list entries [k0, k1), in list order.  A round is: its pairs
  *                           (gtx_disc_second_candidates over the reads' CURRENT state and entries); per pair the window -- the
  *                           round's plain window (entry k applied alone) for a read without entries, else a window of the read's
@@ -1435,6 +1435,119 @@ int gtx_disc_second_rounds(gtx_disc *, const uint8_t * d_planes, uint32_t plane_
                            gtx_disc_second_rounds_stats * stats, void * stream);
 int gtx_disc_second_decide(const gtx_disc_indel * entries, uint32_t n, const uint32_t * list, uint32_t n_list, const gtx_disc_second_support * support,
                            uint32_t * good_bits);
+
+/* ---- discovery to its end: the variant records of streamlined_discovery (src/typer/caller.cpp:2985-3092), the sites file of
+ * iteration 1 (src/utilities/genotype.cpp:427-468: streamlined_discovery, then Vcf::write), a file's second pass and a whole
+ * region as one call each.
+ *   gtx_disc_variants       host (device -1 will do): the words of gtx_disc_merge and the files' good-bits -> the records, in the
+ *                           haplotype map's order.  good_bits: (n_table + 31) / 32 words in table order, the OR over the files of
+ *                           what gtx_disc_second_decide wrote; NULL: none.  An entry's final good support is entry.good | its bit.
+ *                           event_index (GT_ID) counts every event of the map from 1, skipped indels included, and so do the ids
+ *                           of the next events (:2985-2987, :3039-3042).  An indel is skipped, as an event and as a next event,
+ *                           when the table holds it without good support or does not hold it (:2998, :3056: the assert's other
+ *                           arm).  The scan over the next events ends at next.pos >= pos + 100 (:3046; 2 * BUCKET_SIZE with the
+ *                           constant of :2764, whatever bucket size the passes ran with).  A next event in "always" goes to
+ *                           GT_HAPLOTYPE, one not in "ever" to GT_ANTI_HAPLOTYPE, one in "ever" alone nowhere (:3060-3079).
+ *                           Alleles: an SNP has the region's letter and the event's base; an indel has empty / sequence with the
+ *                           base in front of Variant::add_base_in_front with add_N (src/typer/variant.cpp:1135-1167: a letter other
+ *                           than A, C, G, T becomes N) and its position goes one down.
+ *                           AN INDEL WHOSE BASE IN FRONT LIES OUTSIDE THE REGION -- the indel at the region's first base --: the
+ *                           reference's text is defined there and is followed.  Graph::get_generated_reference_genome
+ *                           (src/graph/graph.cpp:409-435) clamps [from, to) to the region, which leaves no base;
+ *                           add_base_in_front returns false in front of any change (variant.cpp:1142-1143) and its caller does not
+ *                           look (:3019, :3026).  The record keeps its EMPTY allele and the event's own position; the sites file
+ *                           then has an empty REF or ALT column for it, as the reference's file has.
+ *                           An SNP outside the region (the asserts of :3006-3007), words that do not parse: GTX_ERR_ARG.
+ *                           Capacity, as gtx_disc_indel_table: *n, *n_letters and *n_ids are always written; more than cap /
+ *                           letters_cap / ids_cap: GTX_ERR_CAPACITY and nothing else is written.
+ *   gtx_disc_vcf_sites      host: such records and a contig name -> the text of iteration 1's file behind its header (the header
+ *                           is gtx_vcf_header's): the column line, then the records in the order of Vcf::write_records
+ *                           (src/typer/vcf.cpp:1161-1275: position; SNP, insertion, deletion; REF shorter, REF longer, equal
+ *                           lengths; the alleles; more INFO keys first), ".0", ".1", ... behind the ID of a record that shares
+ *                           position and type code with the one in front of it, and per record what Vcf::write_record writes
+ *                           for a file without samples (:767-1015): POS = pos + 1, ID contig:POS:type, QUAL 0, FILTER ".", INFO in
+ *                           std::map's order (GT_ANTI_HAPLOTYPE, GT_HAPLOTYPE, GT_ID).  A record whose alleles have more than
+ *                           16 000 letters together is left out (:791-807) but still is the neighbour the next one's suffix
+ *                           looks at.  THIS LIBRARY'S OWN RULE where std::sort leaves it open: records equal in every key keep
+ *                           their order (no region's records are).  *len is always written; more than cap: GTX_ERR_CAPACITY and
+ *                           nothing else is written.  A record that reaches behind the letters or the ids: GTX_ERR_ARG.
+ *   gtx_disc_second_file    device: a file's whole second pass over device arrays of the caller's (plane rows, reads, cigar words,
+ *                           as gtx_disc_second_intake takes them) and the merged words (host): the table and its upload, the
+ *                           intake, the found-bits, the plan, the list's upload, the rounds -- the event array (event_cap entries
+ *                           at first; 0: two per read, at least 1 024) grown and the call continued whenever
+ *                           gtx_disc_second_rounds names events_wanted --, the counters, gtx_disc_second_decide.  Outputs (host):
+ *                           good_bits ((n_table + 31) / 32 words), list / *n_list (list_cap >= n_table always fits), *stats (the
+ *                           sum over the continued calls; events_wanted 0).  Optional, NULL when not wanted: second (n_reads
+ *                           entries, the reads' final state), events / *n_events (the entries in use, which the reads' first_event
+ *                           index), support (n_table counters).  *n_list and *n_events are always written; a list or an event array
+ *                           that does not fit: GTX_ERR_CAPACITY, nothing else written.  All device memory is the library
+ *                           cache's; the call waits for `stream`.
+ *   gtx_discover_region     device: a region's discovery from host arrays to the sites file.  Per file, on one of n_threads workers
+ *                           with a gtx_disc and a stream of its own: one upload, gtx_disc_events_batch (repeated with a buffer
+ *                           of the size it names when the buffer overflowed), gtx_disc_first_pass_haplotypes_device with the
+ *                           file's index.  Then on the calling thread gtx_disc_merge in file order.  Then per file, on the
+ *                           workers, gtx_disc_second_file over the arrays still on the device.  Then the OR of the good-bits,
+ *                           gtx_disc_variants and gtx_disc_vcf_sites.  THE RESULT DOES NOT DEPEND ON n_threads: the files are
+ *                           independent in both passes (the order rule across files stated at gtx_disc_second_decide).  The
+ *                           first error of a worker, in file order, ends the call with its status and message.  A file
+ *                           without reads and a region in which nothing survives are legal (the text is then the column line);
+ *                           n_files == 0, n_threads > 8, bucket_size 0: GTX_ERR_ARG; device -1: GTX_ERR_NO_DEVICE.
+ *                           The result is a handle; what its accessors return lives until gtx_discover_destroy. */
+typedef struct gtx_disc_variant
+{
+  uint32_t pos;              /* 0-based contig position of REF's first base (VCF POS - 1) */
+  uint32_t gt_id;            /* event_index */
+  uint32_t ref_off, ref_len; /* into the letters */
+  uint32_t alt_off, alt_len;
+  uint32_t hap_off, n_hap;   /* GT_HAPLOTYPE: into the ids */
+  uint32_t anti_off, n_anti; /* GT_ANTI_HAPLOTYPE */
+  uint8_t type;              /* 'X', 'I', 'D' */
+  uint8_t reserved[3];
+} gtx_disc_variant;
+int gtx_disc_variants(const gtx_disc *, const uint32_t * words, uint64_t n_words, const uint32_t * good_bits, gtx_disc_variant * out, uint32_t cap, uint32_t * n,
+                      char * letters, uint64_t letters_cap, uint64_t * n_letters, uint32_t * ids, uint64_t ids_cap, uint64_t * n_ids);
+int gtx_disc_vcf_sites(const gtx_disc_variant * variants, uint32_t n, const char * letters, uint64_t n_letters, const uint32_t * ids, uint64_t n_ids,
+                       const char * contig, char * out, uint64_t cap, uint64_t * len);
+int gtx_disc_second_file(gtx_disc *, const uint8_t * d_planes, uint32_t plane_stride, const gtx_disc_read * d_reads, const uint32_t * d_cigar, uint32_t n_reads,
+                         const uint32_t * words, uint64_t n_words, int32_t file_index, uint32_t bucket_size, uint32_t event_cap, uint32_t * good_bits,
+                         uint32_t * list, uint32_t list_cap, uint32_t * n_list, gtx_disc_second_rounds_stats * stats, gtx_disc_second_read * second,
+                         gtx_disc_second_event * events, uint32_t events_cap, uint32_t * n_events, gtx_disc_second_support * support, void * stream);
+
+typedef struct gtx_disc_file /* host arrays, as gtx_disc_events_batch takes them on the device */
+{
+  const uint8_t * planes; /* n_reads rows of plane_stride bytes (gtx_pack_planes) */
+  const uint8_t * qual;   /* n_reads rows of qual_stride bytes */
+  const gtx_disc_read * reads;
+  const uint32_t * cigar; /* n_cigar words */
+  uint32_t plane_stride, qual_stride, n_reads, n_cigar;
+} gtx_disc_file;
+typedef struct gtx_discover_params
+{
+  int32_t device;
+  uint32_t bucket_size;      /* 50 */
+  uint32_t max_read_len;     /* as gtx_disc_set_max_read_len takes it; 0 */
+  uint32_t n_threads;        /* 1 .. 8; 1 */
+  uint32_t first_event_cap;  /* the events buffer of a file at first; 0: eight per read, at least 4 096.  (Small values make the */
+  uint32_t second_event_cap; /* growth paths run.)  The event array of gtx_disc_second_file at first; 0: its default */
+} gtx_discover_params;
+typedef struct gtx_discover_file_stats
+{
+  uint64_t events;        /* of gtx_disc_events_batch */
+  uint32_t events_passes; /* 1 + the repeats */
+  uint32_t n_list;
+  gtx_disc_second_rounds_stats rounds;
+} gtx_discover_file_stats;
+typedef struct gtx_discover_result gtx_discover_result;
+void gtx_discover_params_default(gtx_discover_params *);
+int gtx_discover_region(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const gtx_disc_file * files, uint32_t n_files,
+                        const gtx_discover_params * params, gtx_discover_result ** out);
+void gtx_discover_destroy(gtx_discover_result *);
+const char * gtx_discover_text(const gtx_discover_result *, uint64_t * len);
+const gtx_disc_variant * gtx_discover_variants(const gtx_discover_result *, uint32_t * n, const char ** letters, uint64_t * n_letters, const uint32_t ** ids,
+                                               uint64_t * n_ids);
+const uint32_t * gtx_discover_words(const gtx_discover_result *, uint64_t * n_words);
+const uint8_t * gtx_discover_good(const gtx_discover_result *, uint32_t * n_table); /* per table entry: entry.good | its bit */
+const gtx_discover_file_stats * gtx_discover_stats(const gtx_discover_result *, uint32_t * n_files);
 
 #ifdef __cplusplus
 }

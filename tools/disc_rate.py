@@ -29,8 +29,9 @@ ap.add_argument("--out", default="")
 L_READ, COVERAGE, BUCKET = 150, 30, 50
 
 
-def alignments(ref_len, seed):
-    """-> (reference str, reads gtx.DISC_READ, cigar words, codes [n, 160], qual [n, 160]), sorted by position"""
+def alignments(ref_len, seed, read_seed=None):
+    """-> (reference str, reads gtx.DISC_READ, cigar words, codes [n, 160], qual [n, 160]), sorted by position.  read_seed: the reads
+    are drawn from a generator of their own, so that several files of one region and one sample can be made (tools/discover_rate.py)"""
     rng = np.random.default_rng(seed)
     ref = rng.integers(0, 4, ref_len).astype(np.int8)
     haps = [ref.copy(), ref.copy()]
@@ -45,6 +46,8 @@ def alignments(ref_len, seed):
     on_both = rng.random(len(sites)) < 0.5
     inserted = rng.integers(0, 4, (len(sites), 8)).astype(np.int8)
     n = ref_len * COVERAGE // L_READ
+    if read_seed is not None:
+        rng = np.random.default_rng(read_seed)
     start = np.sort(rng.integers(0, ref_len - L_READ - 10, n))
     hap = rng.integers(0, 2, n)
     j = np.arange(L_READ)
