@@ -139,6 +139,62 @@ struct WaveHipCombine : WaveHip
     return true;
 #endif
   }
+  // The scope around the adds of ONE site entry (apply_recent's statistics / likelihood / depth loop).  A cfg2 entry makes about
+  // eight adds, and the lanes of a position-sorted wavefront -- one or two sites x two alleles -- would form the same two to four
+  // groups for each of them, a wave_group loop per add.  The scope forms them ONCE, by everything that decides the entry's
+  // addresses and addends, and leaves in a word per lane how many lanes the lane adds for (0 outside a scope: add_to above).
+  // INVARIANT: between entry_begin and entry_end every lane of a group executes the same sequence of (address, addend) -- all of
+  // it is a function of the key below and of kernel arguments -- so the group's first lane, adding addend x members each time, adds
+  // what the members would have, and the other members (entry_begin returns false) leave the entry out.
+  static __device__ inline uint32_t * entry_words()
+  {
+    __shared__ uint32_t members[GTX_SCORE_THREADS];
+    return members;
+  }
+  template <class Set>
+  static __device__ inline bool entry_begin(uint32_t sample, uint32_t site, uint32_t coverage, Set const & explains, uint32_t eps, uint32_t clipped_bp,
+                                            uint32_t read_len, uint32_t mapq, uint32_t flags, uint32_t mm8, uint32_t score_diff, bool proper_pair)
+  {
+#ifdef GTX_NO_WAVE_GROUP // (A/B build: every lane for itself, add by add)
+    return true;
+#else
+    // the key, field by field (compared as it is: a hash would not be equality).  coverage is 16 bits, the strand and first-in-pair
+    // bits two, eps at most 8 (four bits), mm8 eight bits, read_len 14 (geno_of) and mapq 8: no field reaches into another
+    constexpr uint32_t NK = 3 + Set::WORDS32 / 2;
+    unsigned long long key[NK];
+    uint32_t const strand_first = ((flags & F_SEQ_REVERSED) ? 1u : 0u) | ((flags & F_FIRST_IN_PAIR) ? 2u : 0u);
+    key[0] = (static_cast<unsigned long long>(site) << 32) | sample;
+    key[1] = (static_cast<unsigned long long>(score_diff) << 32) | clipped_bp;
+    key[2] = (static_cast<unsigned long long>((mapq << 16) | (read_len & 0xFFFFu)) << 32) | ((mm8 & 0xFFu) << 24) | (proper_pair ? 1u << 22 : 0u) | ((eps & 15u) << 18) |
+             (strand_first << 16) | (coverage & 0xFFFFu);
+#pragma unroll
+    for (uint32_t k = 3; k < NK; ++k)
+      key[k] = explains.w[k - 3];
+    uint32_t const lane = threadIdx.x & 63u;
+    uint32_t members = 1u; // (a lane left over when the groups get small: on its own)
+    for (;;)
+    {
+      bool same = true;
+#pragma unroll
+      for (uint32_t k = 0; k < NK; ++k)
+        same &= key[k] == uni(static_cast<uint64_t>(key[k])); // (no short cut: every lane here takes part in the broadcast)
+      unsigned long long const group = __ballot(same);
+      uint32_t const n = static_cast<uint32_t>(__builtin_popcountll(group));
+      if (same)
+      {
+        members = lane == static_cast<uint32_t>(__builtin_ctzll(group)) ? n : 0u;
+        break;
+      }
+      if (n < GTX_WAVE_GROUP_MIN) // (as in wave_group: the first small group is the last one)
+        break;
+    }
+    if (members == 0u)
+      return false;
+    entry_words()[threadIdx.x] = members;
+    return true;
+#endif
+  }
+  static __device__ inline void entry_end() { entry_words()[threadIdx.x] = 0u; }
 #if defined(GTX_EXPERIMENT) && defined(GTX_X_SCORE_NO_ADDS) // (experiment builds only, wrong results: what the kernel takes without its adds)
   static __device__ inline void atomic_add_u32(uint32_t *, uint32_t) {}
   static __device__ inline void atomic_add_u64(unsigned long long *, unsigned long long) {}
@@ -149,7 +205,13 @@ struct WaveHipCombine : WaveHip
   static __device__ GTX_SCORE_ADD_INLINE void add_to(unsigned long long address, bool is64, unsigned long long v)
   {
     unsigned long long sum;
-    if (wave_group(address, v, sum) && !combine(address, is64, sum))
+    uint32_t const members = entry_words()[threadIdx.x]; // (0: no entry scope is open, the lanes with this add find each other)
+    bool mine = true;
+    if (members != 0u)
+      sum = v * static_cast<unsigned long long>(members);
+    else
+      mine = wave_group(address, v, sum);
+    if (mine && !combine(address, is64, sum))
     {
       if (is64)
         atomicAdd(reinterpret_cast<unsigned long long *>(address), sum);
@@ -171,6 +233,7 @@ struct WaveHipCombine : WaveHip
     }
     if (threadIdx.x == 0)
       t.base = base;
+    entry_end(); // (no entry scope is open)
     __syncthreads();
   }
   static __device__ inline void flush()
@@ -1295,6 +1358,8 @@ __device__ __forceinline__ void score_visit(GraphView const & g, ScoreParams con
     bool const dense = acc.compact && (acc.compact_flags[2ull * ai] & GTX_TASK_COMPACT);
     uint32_t const * const src = dense ? acc.compact + static_cast<uint64_t>(ai) * GTX_COMPACT_WORDS : records + static_cast<uint64_t>(ai) * 2 * rec_words;
     uint32_t const have = dense ? GTX_COMPACT_WORDS : (rec_words < SCORE_STAGE_WORDS ? rec_words : SCORE_STAGE_WORDS);
+    mine.staged_read = ai; // (geno_of takes the side byte from here and does not ask for it again)
+    mine.staged_dense = dense;
     uint4_t const * const q = reinterpret_cast<uint4_t const *>(src);
     uint4_t x[SCORE_STAGE_WORDS / 4];
 #pragma unroll

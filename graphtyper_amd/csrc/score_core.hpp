@@ -51,7 +51,10 @@ GTX_DEV Geno geno_of(uint32_t const * records, uint32_t rec_words, Acc const & a
 {
   Geno g;
   g.rec = records + (static_cast<uint64_t>(align_index) * 2 + orient) * rec_words;
-  if (orient == 0 && acc.compact && (acc.compact_flags[2ull * align_index] & GTX_TASK_COMPACT))
+  // (the read's byte of the side array would be a global round trip in the visit's chain: a caller that has looked at it says what it holds)
+  bool const dense = orient == 0 && acc.compact &&
+                     (align_index == acc.staged_read ? acc.staged_dense : (acc.compact_flags[2ull * align_index] & GTX_TASK_COMPACT) != 0);
+  if (dense)
     g.rec = acc.compact + static_cast<uint64_t>(align_index) * GTX_COMPACT_WORDS; // (a record of at most that many words: never external)
   if (g.rec == acc.staged_from)
     g.rec = acc.staged_copy; // (the scoring kernel has fetched this record in one go: every word the parser looks at is in the copy)
@@ -315,6 +318,10 @@ struct ScoreAcc // device pointers, see gtx_score_buffers in include/gtx.h
   // a record the caller has copied (whole, in one round trip) to faster memory: geno_of reads the copy (per thread; NULL: none)
   uint32_t const * staged_from = nullptr;
   uint32_t const * staged_copy = nullptr;
+  // the read whose byte of the side array the caller has looked at (per thread; INVALID: none), and whether that byte carries
+  // GTX_TASK_COMPACT: geno_of does not load it again for the read's forward orientation
+  uint32_t staged_read = 0xFFFFFFFFu;
+  bool staged_dense = false;
   unsigned long long combine_base = 0; // the lowest address of the accumulators above (the scoring kernel's LDS table keys counters by their distance from it)
   // dense records of the position-hinted pass (gtx_align_batch_planes_compact): GTX_COMPACT_WORDS words per read; a task whose
   // byte of the side array carries GTX_TASK_COMPACT has its record there, not in its slot
@@ -561,6 +568,25 @@ GTX_DEV uint32_t explain_epsilon(Geno const & ge, bool fully, bool unique, bool 
   return static_cast<uint32_t>((e > 8 ? e : 8) - 4);
 }
 
+// The adds of one site entry stand in a scope of the wave policy: a policy with entry_begin / entry_end (the scoring kernel's) is told
+// everything that decides the entry's counters and addends before the first add, may have one lane add for all the lanes that bring
+// the same -- begin() is false for the others, which leave the entry out -- and is told when the entry's last add is behind.  A policy
+// without the two (plain atomics, the host emulation) adds lane by lane as ever.
+template <class W, class = void>
+struct EntryScope
+{
+  template <class... A>
+  static GTX_DEV bool begin(A const &...) { return true; }
+  static GTX_DEV void end() {}
+};
+template <class W>
+struct EntryScope<W, decltype(W::entry_end())>
+{
+  template <class... A>
+  static GTX_DEV bool begin(A const &... a) { return W::entry_begin(a...); }
+  static GTX_DEV void end() { W::entry_end(); }
+};
+
 template <class W, class Tab>
 GTX_DEV void apply_recent(GraphView const & g, ScoreAcc const & acc, Geno const & ge, bool fully, bool unique, uint32_t sample,
                           Tab recent, uint32_t n, uint32_t order = 0)
@@ -614,6 +640,11 @@ GTX_DEV void apply_recent(GraphView const & g, ScoreAcc const & acc, Geno const 
     uint64_t const toff = g.tri_off[h];
     uint32_t const cov = rh.coverage;
     bool const unique_allele = cov < MULTI_REF_COVERAGE;
+    // (the scope of the entry's adds, told all that decides their counters and addends -- whatever an add below reads has to be in
+    //  this list or be the same for every item of a call; false: another lane adds for this one)
+    if (!EntryScope<W>::begin(sample, h, cov, rh.explains, explain_epsilon(ge, fully, unique, rh.overlapping), clipped_bp, ge.read_len, ge.mapq, ge.flags,
+                              static_cast<uint32_t>(static_cast<uint8_t>(mismatches)), ge.score_diff, ge.proper_pair))
+      continue;
     // clipped_reads_to_stats (haplotype.cpp:229-244)
     if (clipped_bp != 0)
     {
@@ -679,6 +710,7 @@ GTX_DEV void apply_recent(GraphView const & g, ScoreAcc const & acc, Geno const 
       if (cov > 0 && ge.proper_pair)
         W::atomic_add_u32(cell + 3, 1u);
     }
+    EntryScope<W>::end();
   }
 }
 
