@@ -69,14 +69,10 @@ GTX_HD void hint_judge_key(HintKeys const & t, uint32_t k, uint32_t & nb, uint32
     if (lb.site == INVALID || lb.start != t.labels[own0].start || lb.end != t.labels[own0].end)
       known = 0;
   }
+  // (`same` is read for a key whose own labels are one, or 2..HINT_OWN_MAX that hint_own_labels found on one interval of one site:
+  //  the first label stands for them all.  Two keys cannot both have a label without a site on one interval -- it names the
+  //  reference's bases there --, so a neighbour's label never equals a label without a site.)
   DevLabel const la = t.labels[t.key_off[k]];
-  // (k's own labels: one, or up to HINT_OWN_MAX on one interval of one site -- the alleles of a merged site that share the k-mer)
-  bool uniform = t.key_off[k + 1] - t.key_off[k] <= HINT_OWN_MAX;
-  for (uint32_t i = t.key_off[k] + 1; i < t.key_off[k + 1] && uniform; ++i)
-  {
-    DevLabel const lb = t.labels[i];
-    uniform = la.site != INVALID && lb.site == la.site && lb.start == la.start && lb.end == la.end;
-  }
   auto look = [&](uint32_t b)
   {
     if (b == k || !hint_distance1(t.keys[k], t.keys[b]))
@@ -85,7 +81,7 @@ GTX_HD void hint_judge_key(HintKeys const & t, uint32_t k, uint32_t & nb, uint32
     for (uint32_t i = t.key_off[b]; i < t.key_off[b + 1]; ++i)
     {
       DevLabel const lb = t.labels[i];
-      if (!uniform || la.site == INVALID || lb.site != la.site || lb.start != la.start || lb.end != la.end)
+      if (lb.site != la.site || lb.start != la.start || lb.end != la.end)
         same = 0;
       bool among = false;
       for (uint32_t o = own0; o < own1 && !among && known; ++o)
@@ -128,7 +124,12 @@ GTX_HD bool hint_find_key(HintKeys const & t, uint64_t key, uint32_t & k)
 GTX_HD bool hint_neighbours_ok(HintKeys const & t, uint32_t const * nb, uint8_t const * nb_same, uint32_t k, bool & par)
 {
   par = nb[k] != 0;
-  return t.lsize[k] <= HINT_HE_CAP && t.rsize[k] <= HINT_HE_CAP && (nb[k] == 0 || ((nb_same[k] & 1u) && nb[k] <= HINT_NB_MAX));
+  return t.lsize[k] <= HINT_HE_CAP && t.rsize[k] <= HINT_HE_CAP && (nb_same[k] & 1u) && nb[k] <= HINT_NB_MAX; // (no neighbours: `same` is still 1)
+}
+
+GTX_HD bool hint_label_on(DevLabel const & l, uint32_t exp_start, uint32_t exp_end) // the label lies where the k-mer's path lies
+{
+  return l.start == exp_start && l.end == exp_end;
 }
 
 // Key k's labels when there are several: all (order, order + 31) on one site, alleles below HINT_MASK_BITS -> their set
@@ -146,7 +147,7 @@ GTX_HD uint32_t hint_own_labels(HintKeys const & t, uint32_t k, uint32_t exp_sta
   for (uint32_t i = t.key_off[k]; i < t.key_off[k + 1]; ++i)
   {
     DevLabel const l = t.labels[i];
-    if (l.start != exp_start || l.end != exp_end || l.site == INVALID || l.site != site || l.allele >= HINT_MASK_BITS)
+    if (!hint_label_on(l, exp_start, exp_end) || l.site != site || l.allele >= HINT_MASK_BITS) // (labels without a site: the caller's msite < HINT_NO_SITE)
       return 0;
     mask |= 1u << l.allele;
   }
@@ -166,14 +167,14 @@ GTX_HD uint32_t hint_own_labels_two(HintKeys const & t, uint32_t k, uint32_t exp
   for (uint32_t i = t.key_off[k]; i < t.key_off[k + 1]; ++i)
   {
     DevLabel const l = t.labels[i];
-    if (l.start != exp_start || l.end != exp_end || l.site == INVALID || (l.site != site && l.site != site + 1) || l.allele >= 4u)
+    if (!hint_label_on(l, exp_start, exp_end) || l.site == INVALID || (l.site != site && l.site != site + 1) || l.allele >= 4u)
       return 0;
     if (l.site == site)
       lo |= 1u << l.allele;
     else
       hi |= 1u << l.allele;
   }
-  return hi == 0 ? 0u : lo | (hi << 4);
+  return lo | (hi << 4); // (asked behind hint_own_labels' 0: labels of this form on ONE site would have passed there)
 }
 
 // express4's rule for the neighbours of an exact hit over several sites: every neighbour label is the k-mer's own interval
@@ -181,7 +182,7 @@ GTX_HD uint32_t hint_own_labels_two(HintKeys const & t, uint32_t k, uint32_t exp
 GTX_HD bool hint_neighbours_known(HintKeys const & t, uint32_t const * nb, uint8_t const * nb_same, uint32_t k, bool & par)
 {
   par = nb[k] != 0;
-  return t.lsize[k] <= HINT_HE_CAP && t.rsize[k] <= HINT_HE_CAP && (nb[k] == 0 || ((nb_same[k] & 2u) && nb[k] <= HINT_NB_MAX));
+  return t.lsize[k] <= HINT_HE_CAP && t.rsize[k] <= HINT_HE_CAP && (nb_same[k] & 2u) && nb[k] <= HINT_NB_MAX; // (no neighbours: `known` says that the own labels share an interval and lie on sites, as hint_own_labels_two found)
 }
 
 // ... and with one label: it has to be (order, order + 31, site, allele)
@@ -191,7 +192,7 @@ GTX_HD bool hint_exact_verdict(HintKeys const & t, uint32_t const * nb, uint8_t 
   if (t.key_off[k + 1] - t.key_off[k] != 1)
     return false;
   DevLabel const l = t.labels[t.key_off[k]];
-  if (l.start != exp_start || l.end != exp_end || l.site != want_site || (l.site != INVALID && l.allele != want_allele))
+  if (!hint_label_on(l, exp_start, exp_end) || l.site != want_site || (l.site != INVALID && l.allele != want_allele))
     return false;
   return hint_neighbours_ok(t, nb, nb_same, k, par);
 }
@@ -199,11 +200,6 @@ GTX_HD bool hint_exact_verdict(HintKeys const & t, uint32_t const * nb, uint8_t 
 GTX_HD uint32_t hint_two_bits(uint32_t nibble) // A=1 C=2 G=4 T=8 -> 0..3
 {
   return nibble == 1 ? 0u : nibble == 2 ? 1u : nibble == 4 ? 2u : 3u;
-}
-
-GTX_HD uint32_t hint_acgt(uint8_t code) // graph comparison code -> nibble of A/C/G/T, 15 for anything else
-{
-  return (code == 1 || code == 2 || code == 4 || code == 8) ? code : 15u;
 }
 
 // ... -> the nibble the reference planes hold for that base: an IUPAC letter's own 4-bit code (the walks compare characters: a
@@ -222,10 +218,12 @@ GTX_HD bool hint_is_acgt(uint32_t nibble)
 // IndexView::pos_flags[p]: `base` = the linear reference as nibbles (15 = not ACGT), `room` / `back` = bases to the end /
 // from the start of the position's reference node (capped at 255, 0 outside reference nodes), n = positions
 // (exp_start, exp_end): where a label of the k-mer at p has to lie -- (first_order + p, + 31) on the linear reference, the
-// window's path in an allele window (`linear` false: the offsets of sites under the k-mer are not plain differences of
-// orders there, the SNP logic is left out)
+// window's path in an allele window (there the flags are asked for k-mers that hold a base of the window's allele: their labels name
+// that allele, or several; the one label of allele 0 that the SNP logic starts from is a k-mer of the linear reference.  This is a
+// fact about the index, not about this text: tests/hint_tables_ref.py asserts it for every window position of every graph it is
+// given -- no k-mer that reaches into its window's allele has one label of allele 0 on a site.)
 GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t const * nb, uint8_t const * nb_same, uint8_t const * base,
-                              uint8_t const * room, uint8_t const * back, uint32_t n, uint32_t p, uint32_t exp_start, uint32_t exp_end, bool linear)
+                              uint8_t const * room, uint8_t const * back, uint32_t n, uint32_t p, uint32_t exp_start, uint32_t exp_end)
 {
   uint32_t x = 0, y = static_cast<uint32_t>(room[p]) | (static_cast<uint32_t>(back[p]) << HINT_BACK_SHIFT);
   uint32_t site = HINT_NO_SITE;
@@ -282,7 +280,7 @@ GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t c
       y |= code << (side == 0 ? HINT_FAR_LEFT_SHIFT : HINT_FAR_RIGHT_SHIFT);
     }
   }
-  bool const one_alt_label = found && t.key_off[k + 1] - t.key_off[k] == 1 && t.labels[t.key_off[k]].site != INVALID && t.labels[t.key_off[k]].allele != 0;
+  bool const one_alt_label = found && t.key_off[k + 1] - t.key_off[k] == 1 && t.labels[t.key_off[k]].site != INVALID; // (of allele 0: hint_own_labels says 0)
   if (found && (t.key_off[k + 1] - t.key_off[k] > 1 || one_alt_label) && !g.is_sv_graph)
   {
     // the k-mer lies over a merged site and several of its alleles spell it
@@ -309,7 +307,7 @@ GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t c
   {
     DevLabel const l = t.labels[t.key_off[k]];
     uint32_t const order = exp_start;
-    if (l.start == exp_start && l.end == exp_end && (l.site == INVALID || l.allele == 0) && !(l.site != INVALID && g.is_sv_graph))
+    if (hint_label_on(l, exp_start, exp_end) && (l.site == INVALID || l.allele == 0) && !(l.site != INVALID && g.is_sv_graph))
     {
       site = l.site == INVALID ? HINT_NO_SITE : l.site;
       x |= HINT_SINGLE_OK;
@@ -318,15 +316,19 @@ GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t c
       if (t.rsize[k] == 1)
         x |= HINT_R1;
       bool par = false;
-      if (hint_exact_verdict(t, nb, nb_same, k, exp_start, exp_end, l.site, 0, par))
+      if (hint_neighbours_ok(t, nb, nb_same, k, par)) // (the one label is (exp_start, exp_end, site, allele 0): tested above)
         x |= HINT_EXACT_OK | (par ? HINT_PAR : 0u);
       // the other alleles of a SNP under the k-mer
-      if (l.site != INVALID && linear)
+      if (l.site != INVALID)
       {
         uint32_t const fv = g.ref_first_var[l.site], nv = g.ref_nvar[l.site];
-        bool snp = nv >= 2 && nv <= 4 && g.var_order[fv] >= order && g.var_order[fv] <= order + K - 1;
+        // (The label says that the site lies under the k-mer; with every allele one base its place is one of the k-mer's 32.  More than
+        //  four alleles: one base comes twice, and the verdict below refuses a key with two labels.  An allele that is no A/C/G/T has no key: hint_two_bits
+        //  makes a T of it, and K with a T there is indexed, if at all, with the label of the allele that IS a T -- the verdict asks
+        //  for this allele's number.  The reference allele is one of K's bases.)
+        bool snp = nv >= 2;
         for (uint32_t a = 0; a < nv && snp; ++a)
-          snp = g.var_len[fv + a] == 1 && hint_acgt(static_cast<uint8_t>(g.dna[g.var_dna[fv + a]])) != 15;
+          snp = g.var_len[fv + a] == 1;
         if (snp)
         {
           uint32_t const off = g.var_order[fv] - order; // base of the k-mer that lies on the site
@@ -337,11 +339,13 @@ GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t c
           bool group = (snp_left ? t.lsize[k] : t.rsize[k]) == 1 && (snp_left ? t.rsize[k] : t.lsize[k]) == nv;
           for (uint32_t a = 1; a < nv && snp; ++a)
           {
-            uint32_t const two = hint_two_bits(hint_acgt(static_cast<uint8_t>(g.dna[g.var_dna[fv + a]])));
+            uint32_t const two = hint_two_bits(static_cast<uint8_t>(g.dna[g.var_dna[fv + a]]));
             uint64_t const alt = (key & ~(3ull << (2 * (K - 1 - off)))) | (static_cast<uint64_t>(two) << (2 * (K - 1 - off)));
             uint32_t ka = 0;
             bool pa = false;
-            snp = alt != key && ((idx_of >> (2 * two)) & 3u) == 0 && hint_find_key(t, alt, ka) && hint_exact_verdict(t, nb, nb_same, ka, exp_start, exp_end, l.site, a, pa);
+            // (an allele with the reference allele's base: alt is key, whose one label names allele 0 -- the verdict for allele a says no;
+            //  two alleles with one base: their key has two labels, or the label of the other one)
+            snp = hint_find_key(t, alt, ka) && hint_exact_verdict(t, nb, nb_same, ka, exp_start, exp_end, l.site, a, pa);
             idx_of |= a << (2 * two);
             group = group && snp && (snp_left ? t.lsize[ka] : t.rsize[ka]) == 1;
           }
@@ -362,7 +366,7 @@ GTX_HD uint2_t hint_flags_at(GraphView const & g, HintKeys const & t, uint32_t c
 GTX_HD uint2_t hint_position_flags(GraphView const & g, HintKeys const & t, uint32_t const * nb, uint8_t const * nb_same, uint8_t const * base,
                                     uint8_t const * room, uint8_t const * back, uint32_t n, uint32_t p)
 {
-  return hint_flags_at(g, t, nb, nb_same, base, room, back, n, p, g.first_order + p, g.first_order + p + K - 1, true);
+  return hint_flags_at(g, t, nb, nb_same, base, room, back, n, p, g.first_order + p, g.first_order + p + K - 1);
 }
 
 // ---- allele windows (IndexView::win) ----
@@ -389,7 +393,7 @@ GTX_HD bool hint_site_wants_windows(GraphView const & g, uint32_t r)
 GTX_HD bool hint_allele_gets_window(GraphView const & g, uint32_t r, uint32_t a)
 {
   uint32_t const len = g.var_len[g.ref_first_var[r] + a];
-  return a != 0 && len != 0 && len <= HINT_WIN_ALLELE_MAX;
+  return len != 0 && len <= HINT_WIN_ALLELE_MAX; // (asked for a = 1 .. : hint_list_windows)
 }
 
 // one position of a window: base / room / back / tail entry (those of the linear reference's position it copies; inside the
@@ -455,7 +459,7 @@ GTX_HD uint2_t hint_window_flags(GraphView const & g, HintKeys const & t, uint32
     uint32_t const m = order - g.first_order;
     return m < n_main ? main_flags[m] : none;
   }
-  return hint_flags_at(g, t, nb, nb_same, base, room, back, n_total, p, hint_win_order(g, w, local), hint_win_order(g, w, local + K - 1), false);
+  return hint_flags_at(g, t, nb, nb_same, base, room, back, n_total, p, hint_win_order(g, w, local), hint_win_order(g, w, local + K - 1));
 }
 
 } // namespace gtx

@@ -275,7 +275,7 @@ def test_device_built_index_equals_the_oracles(case):
     k3, c3, l3 = h.index_dump()
     assert np.array_equal(k1, k3) and np.array_equal(c1, c3) and np.array_equal(l1, l3)
     # the tables of the position-hinted pass: the device's build == the host's (gtx_ctx_hint_table)
-    for which in range(5):
+    for which in range(7):
         assert np.array_equal(c.hint_table(which), h.hint_table(which)), "hint table %d" % which
 
 

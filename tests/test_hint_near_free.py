@@ -9,28 +9,7 @@ import pytest
 
 import scenarios
 from graphtyper_amd import lib as gtx
-
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def _hash(w0, w1):
-    """hint_filter_hash (gtx_flat.hpp) on arrays of uint64 holding 32-bit values"""
-    h = (w1 * np.uint64(0x9E3779B1)) & M32
-    h ^= h >> np.uint64(15)
-    h = (h + w0) & M32
-    h = (h * np.uint64(0x85EBCA77)) & M32
-    h ^= h >> np.uint64(16)
-    h2 = (h * np.uint64(0x9E3779B1)) & M32
-    return h, h2
-
-
-def _present(filt, log2_words, w0, w1):
-    h, h2 = _hash(w0, w1)
-    word = h >> np.uint64(32 - log2_words)
-    one = np.uint64(1)
-    mask = (one << (h2 >> np.uint64(27))) | (one << ((h2 >> np.uint64(22)) & np.uint64(31))) | (one << ((h2 >> np.uint64(17)) & np.uint64(31))) | \
-           (one << ((h2 >> np.uint64(12)) & np.uint64(31)))
-    return (filt[word].astype(np.uint64) & mask) == mask
+from hint_tables_ref import filter_present as _present  # (the filter's hash restated in numpy: hint_filter_hash, hint_filter_slot)
 
 
 @pytest.mark.parametrize("kind", ["snp100", "cfg3"])
