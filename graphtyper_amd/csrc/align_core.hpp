@@ -7,8 +7,8 @@
 // lives in LDS, scalars are replicated), LDS writes are done by the leader lane only, and the data-parallel pieces --
 // read unpacking, 2-bit key assembly, the 97 index probes per k-mer, stable hit compaction, character comparison of a
 // read against graph sequence, table copies -- are expressed as lambdas over the lane index plus wave primitives
-// (ballot, exclusive scan).  A policy type W supplies those primitives: WaveHip (gtx_api.hip) maps them to the
-// hardware; tests/emu supplies a sequential stand-in so the very same source can be debugged without a GPU.
+// (ballot, exclusive scan).  A policy type W supplies those primitives: WaveHip (wave_hip.hpp) maps them to the
+// hardware, one sequential wave (tests/wave_seq.hpp) runs the very same source without a GPU; the contract: graph_dev.hpp.
 #pragma once
 #include <type_traits>
 

@@ -8,8 +8,37 @@
 // lives in LDS, scalars are replicated), LDS writes are done by the leader lane only, and the data-parallel pieces --
 // read unpacking, 2-bit key assembly, the 97 index probes per k-mer, stable hit compaction, character comparison of a
 // read against graph sequence, table copies -- are expressed as lambdas over the lane index plus wave primitives
-// (ballot, exclusive scan).  A policy type W supplies those primitives: WaveHip (gtx_api.hip) maps them to the
-// hardware; tests/emu supplies a sequential stand-in so the very same source can be debugged without a GPU.
+// (ballot, exclusive scan).  A policy type W supplies those primitives.  It has two sides: WaveHip / WaveHipMem (wave_hip.hpp) map
+// them to the hardware; gtx::WaveSeq (tests/wave_seq.hpp, test harness only) is one sequential wave, so that the very same source
+// runs on the host, under the sanitizers, without a GPU.  Both sides are held to the table below, primitive by primitive, by one
+// probe (wave_probe.hpp: gtx_wave_probe on the device, tests/emu_wave on the host, tests/wave_probe_cases.py the plain statement).
+//
+// The convergence model.  The text outside the lambdas is wave-uniform: the hardware runs it on all 64 lanes with equal values, the
+// sequential side runs it once.  W::lanes(f) runs f(lane) for every lane: the hardware on all lanes at once, the sequential side for
+// lane 0 .. 63 in order, each to completion -- so a lambda must not wait for what another lane does later in the same lambda.
+//
+//   PerLane<T>              one T per lane, p[lane] inside a lambda (the hardware: a register and the index is not looked at; the
+//                           sequential side: T v[64])
+//   lanes(f)                f(lane) for each of the 64 lanes
+//   leader()                true for the one lane that does the wave's single-lane work (lane 0; the sequential side: always)
+//   uni(v)                  v, which all lanes hold equal, as a wave-uniform value (a scalar register); uint32, int32, bool, uint64
+//   from_lane(p, k)         p[k]; k wave-uniform and below 64
+//   ballot(p)               uint64 with bit l = p[l], of a PerLane<bool>
+//   sum(p)                  p[0] + ... + p[63] modulo 2^32
+//   max(p)                  the largest p[l], unsigned
+//   excl_scan(in, out, t)   out[l] = in[0] + ... + in[l - 1] (out[0] = 0), t = the sum of all 64, both modulo 2^32
+//   shift_up(in, first, out) out[l] = in[l - 1], out[0] = first (wave-uniform); in and out may be one object
+//   lds_sync()              what the leader wrote to LDS before it, every lane reads after it (W of a workspace in HBM: the same there)
+//   mem_sync()              the same for global memory (WaveHipMem and the policies of kernels that hand over through HBM)
+//   atomic_add_u32 / _u64, atomic_sub_u32, atomic_max_u32 / _i32, atomic_or_u32 / _u64 (p, v)
+//                           *p becomes *p + v, - v (modulo 2^32 / 2^64), max(*p, v), | v, atomically against every other wave and
+//                           lane on the device; nothing is returned; called inside a lambda, by any subset of the lanes
+//   claim_u32(p, n)         outside a lambda: the leader adds n (wave-uniform) to *p once; every lane gets the value from before
+//   atomic_claim_u32(p)     inside a lambda, by any subset of the lanes: *p grows by one per caller; the lanes of a wave that arrive
+//                           together get consecutive values in lane order (old + rank among them)
+//   clock()                 a cycle counter for the profiling builds (the sequential side: 0)
+//   note(k)                 GTX_EMU_NOTES builds of the host emulation only: counts why a task left a pass (tests/emu: WaveEmu)
+// The scoring kernels' policies add what is theirs alone (score_core.hpp: combine, wave_group, entry_begin / entry_end).
 #pragma once
 #include <cstdint>
 

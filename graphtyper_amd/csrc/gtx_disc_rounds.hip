@@ -32,31 +32,24 @@ constexpr char const * MSG_PREFIX = "gtx_disc_second_rounds: ";
 constexpr uint32_t TB = 256;
 uint32_t blocks(uint64_t n) { return static_cast<uint32_t>((n + TB - 1) / TB); }
 
-// the hardware wave over global memory, with the atomics the counters need
-struct WaveRounds : WaveHipMem
-{
-  static __device__ inline void atomic_sub_u32(uint32_t * p, uint32_t v) { atomicSub(p, v); }
-  static __device__ inline void atomic_max_u32(uint32_t * p, uint32_t v) { atomicMax(p, v); }
-};
-
 __global__ __launch_bounds__(TB) void gtx_disc_rounds_begin_kernel(gtx_disc_second_read const * __restrict__ reads, uint32_t n_reads, uint32_t n_events,
                                                                    uint16_t * __restrict__ lens, uint32_t * __restrict__ ctl)
 {
   rounds_begin(blockIdx.x * blockDim.x + threadIdx.x, reads, n_reads, n_events, lens, ctl);
 }
 
-__global__ __launch_bounds__(TB) void gtx_disc_rounds_prepare_kernel(RoundsIn in) { rounds_prepare<WaveRounds>(in, blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(TB) void gtx_disc_rounds_prepare_kernel(RoundsIn in) { rounds_prepare<WaveHipMem>(in, blockIdx.x * blockDim.x + threadIdx.x); }
 
 __global__ __launch_bounds__(TB) void gtx_disc_rounds_window_kernel(RoundsIn in)
 {
-  rounds_window_wave<WaveRounds>(in, __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  rounds_window_wave<WaveHipMem>(in, __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
 }
 
-__global__ __launch_bounds__(TB) void gtx_disc_rounds_decide_kernel(RoundsIn in) { rounds_decide<WaveRounds>(in, blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(TB) void gtx_disc_rounds_decide_kernel(RoundsIn in) { rounds_decide<WaveHipMem>(in, blockIdx.x * blockDim.x + threadIdx.x); }
 
 __global__ __launch_bounds__(TB) void gtx_disc_rounds_apply_kernel(RoundsIn in, uint32_t base, uint32_t event_cap)
 {
-  rounds_apply<WaveRounds>(in, blockIdx.x * blockDim.x + threadIdx.x, base, event_cap);
+  rounds_apply<WaveHipMem>(in, blockIdx.x * blockDim.x + threadIdx.x, base, event_cap);
 }
 
 __global__ __launch_bounds__(TB) void gtx_disc_rounds_sizes_kernel(gtx_disc_second_read const * __restrict__ reads, uint32_t n_reads, uint32_t * __restrict__ cnt)

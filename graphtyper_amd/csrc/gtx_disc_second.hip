@@ -29,14 +29,6 @@ constexpr char const * MSG_PREFIX = "gtx_disc_second: ";
 constexpr uint32_t TB = 256;
 uint32_t blocks(uint64_t n) { return static_cast<uint32_t>((n + TB - 1) / TB); }
 
-// the hardware wave with the three atomics the intake needs
-struct WaveSecond : WaveHip
-{
-  static __device__ inline void atomic_max_i32(int32_t * p, int32_t v) { atomicMax(p, v); }
-  static __device__ inline void atomic_max_u32(uint32_t * p, uint32_t v) { atomicMax(p, v); }
-  static __device__ inline void atomic_or_u32(uint32_t * p, uint32_t v) { atomicOr(p, v); }
-};
-
 __global__ __launch_bounds__(TB) void gtx_disc_second_init_kernel(int32_t * __restrict__ bucket_max, uint32_t n_buckets, uint32_t * __restrict__ found,
                                                                   uint32_t found_words, uint32_t * __restrict__ max_read_size)
 {
@@ -45,7 +37,7 @@ __global__ __launch_bounds__(TB) void gtx_disc_second_init_kernel(int32_t * __re
 
 __global__ __launch_bounds__(TB) void gtx_disc_second_intake_kernel(SecondBatch in)
 {
-  disc_second_intake_wave<WaveSecond>(in, blockIdx.x * blockDim.x + (threadIdx.x & ~63u));
+  disc_second_intake_wave<WaveHip>(in, blockIdx.x * blockDim.x + (threadIdx.x & ~63u));
 }
 
 __global__ __launch_bounds__(TB) void gtx_disc_second_buckets_kernel(uint32_t n_buckets, uint32_t const * __restrict__ sorted_key,
@@ -64,8 +56,8 @@ __global__ __launch_bounds__(TB) void gtx_disc_second_count_kernel(SecondRound i
   uint32_t const w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (w > m)
     return;
-  uint32_t const n = w < m ? disc_second_round_wave<WaveSecond, false>(in, k0 + w, 0) : 0;
-  if (WaveSecond::leader())
+  uint32_t const n = w < m ? disc_second_round_wave<WaveHip, false>(in, k0 + w, 0) : 0;
+  if (WaveHip::leader())
     n_of[w] = n;
 }
 
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(TB) void gtx_disc_second_emit_kernel(SecondRound in
   uint32_t const w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (w >= m)
     return;
-  (void)disc_second_round_wave<WaveSecond, true>(in, k0 + w, counts[0] + off[w]);
+  (void)disc_second_round_wave<WaveHip, true>(in, k0 + w, counts[0] + off[w]);
 }
 
 __global__ void gtx_disc_second_count_finish_kernel(uint32_t * counts, uint32_t const * __restrict__ off, uint32_t m, uint32_t pair_cap)

@@ -1,6 +1,7 @@
 // wave_hip.hpp -- the hardware side of the wave policy the kernel sources are written against (graph_dev.hpp: "wave-uniform +
-// lane lambdas"): WaveHip for workspaces in LDS, WaveHipMem for workspaces in HBM, and the wave-level claims on device counters.
-// Device code only; included by the translation units that hold kernels (gtx_api.hip, gtx_hbm_passes.hip).
+// lane lambdas", and the table of what each primitive must do): WaveHip for workspaces in LDS, WaveHipMem for workspaces in HBM,
+// and the wave-level claims on device counters.  Device code only; included by every translation unit that instantiates kernel
+// text with a wave policy.  The sequential side is tests/wave_seq.hpp; gtx_wave_probe (wave_probe.hpp) holds both to the table.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,6 +92,10 @@ struct WaveHip
   static __device__ inline unsigned long long clock() { return clock64(); }
   static __device__ inline void atomic_add_u32(uint32_t * p, uint32_t v) { atomicAdd(p, v); }
   static __device__ inline void atomic_add_u64(unsigned long long * p, unsigned long long v) { atomicAdd(p, v); }
+  static __device__ inline void atomic_sub_u32(uint32_t * p, uint32_t v) { atomicSub(p, v); }
+  static __device__ inline void atomic_max_u32(uint32_t * p, uint32_t v) { atomicMax(p, v); }
+  static __device__ inline void atomic_max_i32(int32_t * p, int32_t v) { atomicMax(p, v); }
+  static __device__ inline void atomic_or_u32(uint32_t * p, uint32_t v) { atomicOr(p, v); }
   // the leader takes `n` (wave-uniform) units from a device counter; every lane gets the old value
   static __device__ inline uint32_t claim_u32(uint32_t * p, uint32_t n)
   {

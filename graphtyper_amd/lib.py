@@ -38,7 +38,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_disc_indel_table", "gtx_disc_indel_table_upload", "gtx_disc_second_intake", "gtx_disc_second_plan", "gtx_disc_second_candidates",
            "gtx_disc_second_rounds", "gtx_disc_second_decide",
            "gtx_disc_variants", "gtx_disc_vcf_sites", "gtx_disc_second_file", "gtx_discover_params_default", "gtx_discover_region", "gtx_discover_destroy",
-           "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats"]
+           "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats",
+           "gtx_wave_probe"]
 
 
 class GraphView(C.Structure):
@@ -309,6 +310,7 @@ def lib():
         L.gtx_discover_good.restype = C.c_void_p
         L.gtx_discover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.gtx_discover_stats.restype = C.POINTER(DiscoverFileStats)
+        L.gtx_wave_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_device_cache_release.argtypes = []

@@ -1549,6 +1549,12 @@ const uint32_t * gtx_discover_words(const gtx_discover_result *, uint64_t * n_wo
 const uint8_t * gtx_discover_good(const gtx_discover_result *, uint32_t * n_table); /* per table entry: entry.good | its bit */
 const gtx_discover_file_stats * gtx_discover_stats(const gtx_discover_result *, uint32_t * n_files);
 
+/* Inspection of the wavefront primitives every kernel is written against (csrc/graph_dev.hpp: the wave policy's table): runs
+ * csrc/wave_probe.hpp on `device`, one wavefront per input set.  in: n_sets x 200 words, out: n_sets x 340 words, both HOST
+ * arrays (the layout: the WP_* constants of wave_probe.hpp; tests/wave_probe_cases.py states what must come out).  n_sets = 0:
+ * GTX_OK, nothing is written.  device < 0: GTX_ERR_NO_DEVICE. */
+int gtx_wave_probe(int device, const uint32_t * in, uint32_t n_sets, uint32_t * out);
+
 #ifdef __cplusplus
 }
 #endif

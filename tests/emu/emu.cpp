@@ -16,11 +16,10 @@
 #include "../../graphtyper_amd/csrc/align_core.hpp"
 #include "../../graphtyper_amd/csrc/score_core.hpp"
 #include "../../graphtyper_amd/csrc/score_replay.hpp"
+#include "../wave_seq.hpp"
 
 namespace
 {
-// Sequential stand-in for one wavefront: lane lambdas run for lane 0..63 one after the other, per-lane values are
-// arrays of 64, the wave-uniform parts of the kernel source run once.
 uint64_t g_notes[16];  // why a task left the express pass (W::note), test diagnostics only
 uint64_t g_hnotes[16]; // ... and the position-hinted pass (hint_note)
 uint32_t g_last_hnote;  // the last non-zero note of the current hinted_one call: why THIS read was declined
@@ -37,66 +36,10 @@ void hint_note(uint32_t k)
 } // namespace gtx
 namespace
 {
-struct WaveEmu
+// the sequential wave (tests/wave_seq.hpp) with the one thing that is this library's own: the notes of a GTX_EMU_NOTES build
+struct WaveEmu : gtx::WaveSeq
 {
   static void note(uint32_t k) { ++g_notes[k & 15u]; }
-  template <class T>
-  struct PerLane
-  {
-    T v[64];
-    T & operator[](uint32_t l) { return v[l]; }
-    T const & operator[](uint32_t l) const { return v[l]; }
-  };
-  static uint32_t from_lane(PerLane<uint32_t> const & p, uint32_t lane) { return p.v[lane]; }
-  template <class F>
-  static void lanes(F && f)
-  {
-    for (uint32_t l = 0; l < 64; ++l)
-      f(l);
-  }
-  static bool leader() { return true; }
-  template <class T>
-  static T uni(T v)
-  {
-    return v;
-  }
-  static void lds_sync() {}
-  static uint64_t ballot(PerLane<bool> const & p)
-  {
-    uint64_t m = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-      m |= static_cast<uint64_t>(p.v[l] ? 1u : 0u) << l;
-    return m;
-  }
-  static uint32_t sum(PerLane<uint32_t> const & p)
-  {
-    uint32_t s = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-      s += p.v[l];
-    return s;
-  }
-  static void excl_scan(PerLane<uint32_t> const & in, PerLane<uint32_t> & out, uint32_t & total)
-  {
-    uint32_t s = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-    {
-      out.v[l] = s;
-      s += in.v[l];
-    }
-    total = s;
-  }
-  static uint32_t max(PerLane<uint32_t> const & p)
-  {
-    uint32_t m = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-      m = p.v[l] > m ? p.v[l] : m;
-    return m;
-  }
-  static void atomic_or_u64(uint64_t * p, uint64_t v) { *p |= v; }
-  static unsigned long long clock() { return 0; }
-  static void atomic_add_u32(uint32_t * p, uint32_t v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-  static uint32_t atomic_claim_u32(uint32_t * p) { return __atomic_fetch_add(p, 1u, __ATOMIC_RELAXED); }
-  static void atomic_add_u64(unsigned long long * p, unsigned long long v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 };
 
 struct Emu

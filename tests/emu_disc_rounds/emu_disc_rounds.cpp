@@ -23,59 +23,18 @@
 #include <memory>
 #include <vector>
 
+#include "../wave_seq.hpp"
 #include "gtx_disc_rounds_dev.hpp" // from the Makefile's CSRC
 
 using namespace gtx;
 
 namespace
 {
-struct WaveSeq
+// the sequential wave with the count of W::mem_sync() calls this program writes out per window
+struct WaveSeqCounted : WaveSeq
 {
-  template <class T>
-  struct PerLane
-  {
-    T v[64];
-    T & operator[](uint32_t l) { return v[l]; }
-    T const & operator[](uint32_t l) const { return v[l]; }
-  };
-  template <class F>
-  static void lanes(F && f)
-  {
-    for (uint32_t l = 0; l < 64; ++l)
-      f(l);
-  }
-  static bool leader() { return true; }
   static inline uint64_t syncs = 0;
   static void mem_sync() { ++syncs; }
-  static uint32_t uni(uint32_t v) { return v; }
-  static uint32_t from_lane(PerLane<uint32_t> const & p, uint32_t lane) { return p.v[lane]; }
-  static void shift_up(PerLane<uint32_t> const & in, uint32_t first, PerLane<uint32_t> & out)
-  {
-    for (uint32_t l = 63; l > 0; --l)
-      out.v[l] = in.v[l - 1];
-    out.v[0] = first;
-  }
-  static uint32_t max(PerLane<uint32_t> const & p)
-  {
-    uint32_t x = p.v[0];
-    for (uint32_t l = 1; l < 64; ++l)
-      x = p.v[l] > x ? p.v[l] : x;
-    return x;
-  }
-  static void excl_scan(PerLane<uint32_t> const & in, PerLane<uint32_t> & out, uint32_t & total)
-  {
-    uint32_t sum = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-    {
-      out.v[l] = sum;
-      sum += in.v[l];
-    }
-    total = sum;
-  }
-  static void atomic_add_u32(uint32_t * p, uint32_t v) { *p += v; }
-  static void atomic_sub_u32(uint32_t * p, uint32_t v) { *p -= v; }
-  static void atomic_max_u32(uint32_t * p, uint32_t v) { *p = std::max(*p, v); }
-  static void atomic_add_u64(unsigned long long * p, unsigned long long v) { *p += v; }
 };
 
 template <class T>
@@ -223,10 +182,10 @@ int main(int argc, char ** argv)
     SecondRound const round{list.get(), table.get(), n_table, second.get(), n_reads, events.get(), count, static_cast<long>(region_begin), REF_SIZE,
                             static_cast<long>(bucket_size), n_buckets, bucket_max.get(), bucket_global_max.get(), max_read_size.get(), bucket_reads.get(),
                             bucket_off.get(), pairs.get(), n_reads};
-    uint32_t const produced = disc_second_round_wave<WaveSeq, true>(round, k, 0);
+    uint32_t const produced = disc_second_round_wave<WaveSeqCounted, true>(round, k, 0);
     disc_second_count(counts.get(), produced, n_reads);
     for (uint32_t i = 0; i < slots; ++i)
-      rounds_prepare<WaveSeq>(in, i);
+      rounds_prepare<WaveSeqCounted>(in, i);
     exclusive_sum(ub.get(), woff.get(), slots);
     uint32_t const n_pairs = ctl[ROUNDS_N_PAIRS];
     uint64_t const letters = (static_cast<uint64_t>(ctl[ROUNDS_LETTERS_HI]) << 32) | ctl[ROUNDS_LETTERS_LO];
@@ -260,9 +219,9 @@ int main(int argc, char ** argv)
     std::vector<uint32_t> syncs(static_cast<size_t>(n_pairs) + 1);
     for (uint32_t slot = 0; slot <= n_pairs; ++slot)
     {
-      uint64_t const before = WaveSeq::syncs;
-      rounds_window_wave<WaveSeq>(in, slot);
-      syncs[slot] = static_cast<uint32_t>(WaveSeq::syncs - before);
+      uint64_t const before = WaveSeqCounted::syncs;
+      rounds_window_wave<WaveSeqCounted>(in, slot);
+      syncs[slot] = static_cast<uint32_t>(WaveSeqCounted::syncs - before);
     }
     for (uint32_t slot = 0; slot <= n_pairs; ++slot)
     {
@@ -278,9 +237,9 @@ int main(int argc, char ** argv)
         put(applied.get() + r->first_event, r->n_events);
     }
     for (uint32_t j = 0; j < n_pairs; ++j)
-      realign_pair_dev<WaveSeq>(planes.get(), plane_stride, lens.get(), n_reads, in.seq, target_off.get(), 2 * (n_pairs + 1), rpairs[j], &results[j]);
+      realign_pair_dev<WaveSeqCounted>(planes.get(), plane_stride, lens.get(), n_reads, in.seq, target_off.get(), 2 * (n_pairs + 1), rpairs[j], &results[j]);
     for (uint32_t j = 0; j <= n_reads; ++j)
-      rounds_decide<WaveSeq>(in, j);
+      rounds_decide<WaveSeqCounted>(in, j);
     exclusive_sum(newn.get(), noff.get(), static_cast<size_t>(n_reads) + 1);
     uint32_t const total = noff[n_reads];
     if (static_cast<uint64_t>(count) + total > event_cap)
@@ -290,7 +249,7 @@ int main(int argc, char ** argv)
       break;
     }
     for (uint32_t j = 0; j < n_pairs; ++j)
-      rounds_apply<WaveSeq>(in, j, count, event_cap);
+      rounds_apply<WaveSeqCounted>(in, j, count, event_cap);
     count += total;
     ++rounds_done;
     built += ctl[ROUNDS_WINDOWS];

@@ -23,43 +23,13 @@
 #include <numeric>
 #include <vector>
 
+#include "../wave_seq.hpp"
 #include "gtx_disc_second_dev.hpp" // from the Makefile's CSRC
 
 using namespace gtx;
 
 namespace
 {
-struct WaveSeq
-{
-  template <class T>
-  struct PerLane
-  {
-    T v[64];
-    T & operator[](uint32_t l) { return v[l]; }
-    T const & operator[](uint32_t l) const { return v[l]; }
-  };
-  template <class F>
-  static void lanes(F && f)
-  {
-    for (uint32_t l = 0; l < 64; ++l)
-      f(l);
-  }
-  static bool leader() { return true; }
-  static void excl_scan(PerLane<uint32_t> const & in, PerLane<uint32_t> & out, uint32_t & total)
-  {
-    uint32_t sum = 0;
-    for (uint32_t l = 0; l < 64; ++l)
-    {
-      out.v[l] = sum;
-      sum += in.v[l];
-    }
-    total = sum;
-  }
-  static void atomic_max_i32(int32_t * p, int32_t v) { *p = std::max(*p, v); }
-  static void atomic_max_u32(uint32_t * p, uint32_t v) { *p = std::max(*p, v); }
-  static void atomic_or_u32(uint32_t * p, uint32_t v) { *p |= v; }
-};
-
 // the file as the intake's text asks for it, a heap block per read and array
 struct HeapBatch
 {

@@ -16,29 +16,12 @@
 #include <vector>
 
 #include "../../graphtyper_amd/csrc/gtx_inflate_dev.hpp"
+#include "../wave_seq.hpp"
 
 using namespace gtx;
 
 namespace
 {
-struct WaveSeq
-{
-  template <class F>
-  static void lanes(F && f)
-  {
-    for (uint32_t l = 0; l < 64; ++l)
-      f(l);
-  }
-  static bool leader() { return true; }
-  template <class T>
-  static T uni(T v)
-  {
-    return v;
-  }
-  static void lds_sync() {}
-  static void mem_sync() {}
-};
-
 bool read_exact(std::FILE * f, void * p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 bool write_exact(std::FILE * f, void const * p, size_t n) { return n == 0 || std::fwrite(p, 1, n, f) == n; }
 } // namespace

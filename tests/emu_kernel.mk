@@ -10,5 +10,5 @@ SAN ?= address,undefined
 OPT ?= -O1 -g
 SANFLAGS = $(if $(SAN),-fsanitize=$(SAN) -fno-sanitize-recover=all -fno-omit-frame-pointer,)
 all: $(OUT)
-$(OUT): $(NAME).cpp $(addprefix $(CSRC)/,$(HEADERS)) $(LIB_CSRC)/graph_dev.hpp $(LIB_CSRC)/gtx_flat.hpp ../../include/gtx.h
+$(OUT): $(NAME).cpp ../wave_seq.hpp $(addprefix $(CSRC)/,$(HEADERS)) $(LIB_CSRC)/graph_dev.hpp $(LIB_CSRC)/gtx_flat.hpp ../../include/gtx.h
 	$(CXX) -std=c++17 $(OPT) -Wall -Wno-unused-function -Wno-unknown-pragmas $(SANFLAGS) -I$(CSRC) -I$(LIB_CSRC) -o $@ $(NAME).cpp

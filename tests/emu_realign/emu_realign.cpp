@@ -15,45 +15,13 @@
 #include <memory>
 #include <vector>
 
+#include "../wave_seq.hpp"
 #include "gtx_realign_dev.hpp" // from the Makefile's CSRC
 
 using namespace gtx;
 
 namespace
 {
-struct WaveSeq
-{
-  template <class T>
-  struct PerLane
-  {
-    T v[64];
-    T & operator[](uint32_t l) { return v[l]; }
-    T const & operator[](uint32_t l) const { return v[l]; }
-  };
-  template <class F>
-  static void lanes(F && f)
-  {
-    for (uint32_t l = 0; l < 64; ++l)
-      f(l);
-  }
-  static bool leader() { return true; }
-  static uint32_t uni(uint32_t v) { return v; }
-  static uint32_t from_lane(PerLane<uint32_t> const & p, uint32_t lane) { return p.v[lane]; }
-  static void shift_up(PerLane<uint32_t> const & in, uint32_t first, PerLane<uint32_t> & out) // (in and out may be one)
-  {
-    for (uint32_t l = 63; l > 0; --l)
-      out.v[l] = in.v[l - 1];
-    out.v[0] = first;
-  }
-  static uint32_t max(PerLane<uint32_t> const & p)
-  {
-    uint32_t x = p.v[0];
-    for (uint32_t l = 1; l < 64; ++l)
-      x = p.v[l] > x ? p.v[l] : x;
-    return x;
-  }
-};
-
 bool read_exact(std::FILE * f, void * p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 } // namespace
 

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <memory>
 
+#include "../wave_seq.hpp"
 #include "gtx_flat.hpp"
 #include "score_core.hpp" // from the Makefile's CSRC
 
@@ -21,12 +22,7 @@ namespace emu_case
 {
 using namespace gtx;
 
-struct WaveSeq
-{
-  static void atomic_add_u32(uint32_t * p, uint32_t v) { *p += v; }
-  static uint32_t atomic_claim_u32(uint32_t * p) { return (*p)++; }
-  static void atomic_add_u64(unsigned long long * p, unsigned long long v) { *p += v; }
-};
+using WaveSeq = gtx::WaveSeq;
 
 bool read_exact(std::FILE * f, void * p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
 
