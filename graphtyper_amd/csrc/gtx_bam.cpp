@@ -413,38 +413,15 @@ extern "C" int gtx_reads_open(const char * const * bam_paths, uint32_t n_paths, 
       return fail(r, file->path + " is not a BAM file (CRAM is not read)", GTX_ERR_UNSUPPORTED);
     if (got == gtx::BAM_TRUNCATED)
       return fail(r, file->path + ": truncated header", GTX_ERR_IO);
-    std::string const & text = head.text;
     for (auto const & ref : head.refs)
       file->ref_names.push_back(ref.first);
-    // @RG lines -> read groups and samples (hts_reader.cpp:31-80: first "\tID:", last "\tSM:")
-    size_t at = 0;
-    while (at < text.size())
-    {
-      size_t const nl = std::min(text.find('\n', at), text.size());
-      std::string const line = text.substr(at, nl - at);
-      at = nl + 1;
-      if (line.rfind("@RG", 0) != 0)
-        continue;
-      size_t const pid = line.find("\tID:"), psm = line.rfind("\tSM:");
-      if (pid == std::string::npos || psm == std::string::npos)
-      {
-        return fail(r, file->path + ": an @RG line without ID or SM", GTX_ERR_ARG);
-      }
-      size_t const eid = std::min(line.find('\t', pid + 1), line.size()), esm = std::min(line.find('\t', psm + 1), line.size());
-      std::string const id = line.substr(pid + 4, eid - pid - 4), sm = line.substr(psm + 4, esm - psm - 4);
-      file->rg2index[id] = static_cast<uint32_t>(file->rg2sample.size());
-      auto it = std::find(file->samples.begin(), file->samples.end(), sm);
-      file->rg2sample.push_back(static_cast<uint32_t>(it - file->samples.begin()));
-      if (it == file->samples.end())
-        file->samples.push_back(sm);
-    }
-    if (file->samples.empty()) // the file name up to its first '.' (hts_reader.cpp:83-91)
-    {
-      std::string s = file->path.substr(file->path.rfind('/') + 1);
-      if (s.find('.') != std::string::npos)
-        s = s.substr(0, s.find('.'));
-      file->samples.push_back(s);
-    }
+    // @RG lines -> read groups and samples
+    gtx::BamSamples table;
+    if (!gtx::read_bam_samples(head.text, file->path, table))
+      return fail(r, file->path + ": an @RG line without ID or SM", GTX_ERR_ARG);
+    file->samples.swap(table.samples);
+    file->rg2index.swap(table.rg2index);
+    file->rg2sample.swap(table.rg2sample);
     if (!whole)
     {
       auto it = std::find(file->ref_names.begin(), file->ref_names.end(), contig);

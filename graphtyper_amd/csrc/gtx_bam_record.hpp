@@ -1,11 +1,13 @@
-// gtx_bam_record.hpp -- the BAM format as both of its readers see it (gtx_bam.cpp: gtx_reads_*; gtx_shrink.cpp: the pre-filter):
-// the header, the next record's block, the fixed 32 bytes of a record with the offsets of what follows them, the reference span
-// of a CIGAR.  (SAM spec 4.2)
+// gtx_bam_record.hpp -- the BAM format as all of its readers see it (gtx_bam.cpp: gtx_reads_*; gtx_shrink.cpp: the pre-filter;
+// gtx_disc_bam.cpp: discovery's files): the header, its samples, the next record's block, the fixed 32 bytes of a record with the
+// offsets of what follows them, the reference span of a CIGAR.  (SAM spec 4.2)
 #pragma once
 #include "gtx_bgzf.hpp"
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -45,6 +47,47 @@ inline BamHeaderRead read_bam_header(Bgzf & fp, BamHeader & h)
   return BAM_HEADER_OK;
 }
 
+// the read groups and samples of a header's @RG lines (hts_reader.cpp:31-80: first "\tID:", last "\tSM:"); without an @RG line the
+// one sample is the file name up to its first '.' (hts_reader.cpp:83-91)
+struct BamSamples
+{
+  std::vector<std::string> samples;         // in header order
+  std::map<std::string, uint32_t> rg2index; // read group id -> its index
+  std::vector<uint32_t> rg2sample;          // -> index into samples
+};
+
+// false: an @RG line without ID or SM
+inline bool read_bam_samples(std::string const & text, std::string const & path, BamSamples & s)
+{
+  size_t at = 0;
+  while (at < text.size())
+  {
+    size_t const nl = std::min(text.find('\n', at), text.size());
+    std::string const line = text.substr(at, nl - at);
+    at = nl + 1;
+    if (line.rfind("@RG", 0) != 0)
+      continue;
+    size_t const pid = line.find("\tID:"), psm = line.rfind("\tSM:");
+    if (pid == std::string::npos || psm == std::string::npos)
+      return false;
+    size_t const eid = std::min(line.find('\t', pid + 1), line.size()), esm = std::min(line.find('\t', psm + 1), line.size());
+    std::string const id = line.substr(pid + 4, eid - pid - 4), sm = line.substr(psm + 4, esm - psm - 4);
+    s.rg2index[id] = static_cast<uint32_t>(s.rg2sample.size());
+    auto it = std::find(s.samples.begin(), s.samples.end(), sm);
+    s.rg2sample.push_back(static_cast<uint32_t>(it - s.samples.begin()));
+    if (it == s.samples.end())
+      s.samples.push_back(sm);
+  }
+  if (s.samples.empty())
+  {
+    std::string name = path.substr(path.rfind('/') + 1);
+    if (name.find('.') != std::string::npos)
+      name = name.substr(0, name.find('.'));
+    s.samples.push_back(name);
+  }
+  return true;
+}
+
 // the next record's block (what follows its block_size) into buf
 enum BamBlockRead { BAM_BLOCK_OK, BAM_BLOCK_END, BAM_BLOCK_DAMAGED };
 inline BamBlockRead read_bam_block(Bgzf & fp, std::vector<uint8_t> & buf)
@@ -59,6 +102,26 @@ inline BamBlockRead read_bam_block(Bgzf & fp, std::vector<uint8_t> & buf)
   return fp.read(buf.data(), buf.size()) == static_cast<long>(buf.size()) ? BAM_BLOCK_OK : BAM_BLOCK_DAMAGED;
 }
 
+// the same behind what `stream` holds already, as the bytes lie in the file: the block_size word, then the block, read where it
+// stays (gtx_disc_bam.cpp keeps a file's records so).  *at: where the block begins.  Not BAM_BLOCK_OK: `stream` is as it was.
+inline BamBlockRead append_bam_block(Bgzf & fp, std::vector<uint8_t> & stream, size_t * at)
+{
+  size_t const before = stream.size();
+  int32_t block = 0;
+  long const got = fp.read(&block, 4);
+  if (got == 0)
+    return BAM_BLOCK_END;
+  if (got != 4 || block < 32)
+    return BAM_BLOCK_DAMAGED;
+  stream.resize(before + 4 + static_cast<size_t>(block));
+  std::memcpy(stream.data() + before, &block, 4);
+  *at = before + 4;
+  if (fp.read(stream.data() + *at, static_cast<size_t>(block)) == static_cast<long>(block))
+    return BAM_BLOCK_OK;
+  stream.resize(before);
+  return BAM_BLOCK_DAMAGED;
+}
+
 struct BamCore
 {
   int32_t tid, pos, l_seq, mtid, mpos, tlen;
@@ -68,9 +131,8 @@ struct BamCore
 };
 
 // false: the block is shorter than its own counts say (or l_seq is negative)
-inline bool parse_bam_core(std::vector<uint8_t> const & buf, BamCore & c)
+inline bool parse_bam_core(uint8_t const * p, size_t size, BamCore & c) // a block of `size` bytes (at least 32) at p
 {
-  uint8_t const * p = buf.data();
   std::memcpy(&c.tid, p, 4);
   std::memcpy(&c.pos, p + 4, 4);
   c.l_read_name = p[8];
@@ -87,8 +149,9 @@ inline bool parse_bam_core(std::vector<uint8_t> const & buf, BamCore & c)
   c.o_seq = c.o_cigar + 4ull * c.n_cigar;
   c.o_qual = c.o_seq + (static_cast<size_t>(c.l_seq) + 1) / 2;
   c.o_aux = c.o_qual + static_cast<size_t>(c.l_seq);
-  return c.o_aux <= buf.size();
+  return c.o_aux <= size;
 }
+inline bool parse_bam_core(std::vector<uint8_t> const & buf, BamCore & c) { return parse_bam_core(buf.data(), buf.size(), c); }
 
 // reference positions an alignment covers (bam_endpos: M, D, N, =, X consume the reference); cigar: n words of len << 4 | op,
 // at any alignment.  What a span of zero or an unmapped read counts as is the caller's rule.

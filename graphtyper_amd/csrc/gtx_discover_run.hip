@@ -1,6 +1,8 @@
 // gtx_discover_run.hip -- discovery's host loops inside the library, beside gtx_regions.cpp and gtx_pipeline.cpp: a file's second
 // pass as one call (gtx_disc_second_file: what parallel_second_pass, src/typer/caller.cpp:2633-2751, does for one file) and a
-// region's discovery from host arrays to the sites file (gtx_discover_region: streamlined_discovery, :2753-3093, then the writer).
+// region's discovery to the sites file (streamlined_discovery, :2753-3093, then the writer) from host arrays (gtx_discover_region)
+// or from the BAM files themselves (gtx_discover_files: read on the host, gtx_disc_bam.cpp, unpacked on the device, gtx_disc_bam.hip);
+// the two share one body behind "the file's arrays are on the device".
 //
 // No kernel lives here: every stage is an entry point that exists, and this file is their caller -- the uploads, the growth
 // protocols (the events buffer of the first pass, the event array of the rounds), the downloads, the merge.  A file's arrays are
@@ -19,6 +21,7 @@
 #include "../../include/gtx.h"
 #include "gtx_devmem.hpp"
 #include "gtx_disc.hpp"
+#include "gtx_disc_bam.hpp"
 
 static_assert(sizeof(gtx_disc_variant) == 44 && sizeof(gtx_disc_file) == 48 && sizeof(gtx_discover_params) == 24 && sizeof(gtx_discover_file_stats) == 64,
               "layouts of the binding");
@@ -64,6 +67,20 @@ bool uploaded(DevPtr<T> & p, H const * from, size_t n, hipStream_t s, char const
   if (!zeroed(p, n + room_behind, s, what))
     return false;
   return n == 0 || hip_ok(hipMemcpyAsync(p.get(), from, n * sizeof(T), hipMemcpyHostToDevice, s), what, MSG_PREFIX);
+}
+
+// n entries of T on the device that the next work on the stream writes, every one of them: only what lies behind them is zeroed
+template <class T>
+bool made(DevPtr<T> & p, size_t n, hipStream_t s, char const * what, size_t room_behind = 0)
+{
+  size_t const used = n * sizeof(T), bytes = used + room_behind + PAD;
+  return hip_ok(alloc_e(p, bytes), what, MSG_PREFIX) && hip_ok(hipMemsetAsync(reinterpret_cast<uint8_t *>(p.get()) + used, 0, bytes - used, s), what, MSG_PREFIX);
+}
+
+template <class T, class H>
+bool copied_up(T * to, H const * from, size_t n, hipStream_t s, char const * what)
+{
+  return n == 0 || hip_ok(hipMemcpyAsync(to, from, n * sizeof(T), hipMemcpyHostToDevice, s), what, MSG_PREFIX);
 }
 
 template <class T>
@@ -198,6 +215,7 @@ struct FileState // a file's arrays on the device and what its passes left
   DevPtr<uint8_t> planes, qual;
   DevPtr<gtx_disc_read> reads;
   DevPtr<uint32_t> cigar;
+  uint32_t plane_stride = 0, qual_stride = 0, n_reads = 0, n_cigar = 0;
   std::vector<uint32_t> words; // of its first pass
   SecondResult second;
   gtx_discover_file_stats stats{};
@@ -211,31 +229,84 @@ struct Worker
   Stream stream;
 };
 
-int first_pass(Worker & w, gtx_disc_file const & f, uint32_t file_index, gtx_discover_params const & p, FileState & st)
+// gtx_discover_region's way to "the file's arrays are on the device": the host arrays, uploaded
+int load_arrays(Worker & w, gtx_disc_file const & f, FileState & st)
 {
   hipStream_t const s = w.stream.get();
-  gtx_disc * const d = w.disc.get();
-  if (int const rc = device_ready(d->device, "gtx_discover_region", ": the object"))
+  if (int const rc = device_ready(w.disc->device, "gtx_discover_region", ": the object"))
     return rc;
+  st.plane_stride = f.plane_stride;
+  st.qual_stride = f.qual_stride;
+  st.n_reads = f.n_reads;
+  st.n_cigar = f.n_cigar;
   if (!uploaded(st.planes, f.planes, static_cast<size_t>(f.n_reads) * f.plane_stride, s, "plane rows") ||
       // (the walk reads the quality under any base of a plane row that differs from the region: a row's worth of room behind the last)
       !uploaded(st.qual, f.qual, static_cast<size_t>(f.n_reads) * f.qual_stride, s, "qualities", 2 * static_cast<size_t>(f.plane_stride)) || !uploaded(st.reads, f.reads, f.n_reads, s, "reads") ||
       !uploaded(st.cigar, f.cigar, f.n_cigar, s, "cigar words"))
     return GTX_ERR_HIP;
+  return GTX_OK;
+}
+
+// gtx_discover_files' way there: the file read on the host and its tables checked, its record stream and the two tables uploaded, the
+// host block freed, the unpack kernel.  The stream leaves the device when the kernel has run.
+int load_bam(Worker & w, char const * path, FileState & st)
+{
+  hipStream_t const s = w.stream.get();
+  if (int const rc = device_ready(w.disc->device, "gtx_discover_files", ": the object"))
+    return rc;
+  gtx_disc_bam * raw = nullptr;
+  if (int const rc = gtx_disc_bam_read(path, &raw))
+    return rc;
+  std::unique_ptr<gtx_disc_bam, Free<gtx_disc_bam_destroy>> bam(raw);
+  uint32_t const longest = bam->max_l_seq;
+  size_t const n_bytes = bam->stream.size() - DISC_BAM_SLACK;
+  st.plane_stride = std::max<uint32_t>((longest + 31u) / 32u * 16u, 16u);
+  st.qual_stride = std::max<uint32_t>((longest + 3u) & ~3u, 4u);
+  st.n_reads = static_cast<uint32_t>(bam->reads.size());
+  st.n_cigar = static_cast<uint32_t>(bam->n_cigar);
+  if (int const rc = disc_bam_unpack_check(n_bytes, bam->offsets.data(), bam->reads.data(), st.n_reads, st.plane_stride, st.qual_stride, st.n_cigar))
+  {
+    g_last_error += std::string(" (") + path + ")";
+    return rc;
+  }
+  DevPtr<uint8_t> d_stream;
+  DevPtr<uint32_t> d_offsets;
+  WaitBehind const behind(s);
+  if (!made(d_stream, bam->stream.size(), s, "record stream") || !copied_up(d_stream.get(), bam->stream.data(), bam->stream.size(), s, "record stream") ||
+      !made(d_offsets, st.n_reads, s, "record offsets") || !copied_up(d_offsets.get(), bam->offsets.data(), st.n_reads, s, "record offsets") ||
+      !made(st.reads, st.n_reads, s, "reads") || !copied_up(st.reads.get(), bam->reads.data(), st.n_reads, s, "reads") || !waited(s))
+    return GTX_ERR_HIP;
+  bam.reset(); // (the upload is done: the host block goes)
+  // the kernel writes every byte of every row and every word; the room behind the last quality row is load_arrays'
+  if (!made(st.planes, static_cast<size_t>(st.n_reads) * st.plane_stride, s, "plane rows") ||
+      !made(st.qual, static_cast<size_t>(st.n_reads) * st.qual_stride, s, "qualities", 2 * static_cast<size_t>(st.plane_stride)) ||
+      !made(st.cigar, st.n_cigar, s, "cigar words"))
+    return GTX_ERR_HIP;
+  if (int const rc = disc_bam_unpack_launch(d_stream.get(), d_offsets.get(), st.reads.get(), st.n_reads, st.planes.get(), st.plane_stride, st.qual.get(),
+                                            st.qual_stride, st.cigar.get(), s))
+    return rc;
+  return waited(s) ? GTX_OK : GTX_ERR_HIP;
+}
+
+// a file's first pass over its arrays on the device
+int first_pass(Worker & w, uint32_t file_index, gtx_discover_params const & p, FileState & st)
+{
+  hipStream_t const s = w.stream.get();
+  gtx_disc * const d = w.disc.get();
   DevPtr<gtx_disc_event> d_events;
   DevPtr<uint32_t> d_counts;
   DevPtr<gtx_disc_read_out> d_read_out;
   WaitBehind const behind(s);
-  uint64_t cap = p.first_event_cap ? p.first_event_cap : std::max<uint64_t>(8ull * f.n_reads, 4096);
+  uint64_t cap = p.first_event_cap ? p.first_event_cap : std::max<uint64_t>(8ull * st.n_reads, 4096);
   uint32_t counts[2] = {0, 0};
-  if (!zeroed(d_read_out, f.n_reads, s, "read_out"))
+  if (!zeroed(d_read_out, st.n_reads, s, "read_out"))
     return GTX_ERR_HIP;
   for (;;) // (a pass whose buffer overflowed names the size it needs: one repeat)
   {
     ++st.stats.events_passes;
     if (!zeroed(d_events, cap, s, "events") || !zeroed(d_counts, 2, s, "event counters"))
       return GTX_ERR_HIP;
-    if (int const rc = gtx_disc_events_batch(d, st.planes.get(), f.plane_stride, st.qual.get(), f.qual_stride, st.reads.get(), st.cigar.get(), f.n_reads,
+    if (int const rc = gtx_disc_events_batch(d, st.planes.get(), st.plane_stride, st.qual.get(), st.qual_stride, st.reads.get(), st.cigar.get(), st.n_reads,
                                              d_events.get(), static_cast<uint32_t>(cap), d_counts.get(), d_read_out.get(), s))
       return rc;
     if (!downloaded(counts, d_counts.get(), 2, s, "event counters") || !waited(s))
@@ -244,7 +315,7 @@ int first_pass(Worker & w, gtx_disc_file const & f, uint32_t file_index, gtx_dis
       break;
     if (counts[0] <= cap)
     {
-      g_last_error = "gtx_discover_region: the events pass overflowed a buffer of the size it named";
+      g_last_error = "gtx_discover: the events pass overflowed a buffer of the size it named";
       return GTX_ERR_HIP;
     }
     cap = counts[0];
@@ -254,7 +325,7 @@ int first_pass(Worker & w, gtx_disc_file const & f, uint32_t file_index, gtx_dis
   st.words.assign(1 << 12, 0);
   for (int turn = 0;; ++turn)
   {
-    int const rc = gtx_disc_first_pass_haplotypes_device(d, st.planes.get(), f.plane_stride, st.reads.get(), st.cigar.get(), d_read_out.get(), f.n_reads,
+    int const rc = gtx_disc_first_pass_haplotypes_device(d, st.planes.get(), st.plane_stride, st.reads.get(), st.cigar.get(), d_read_out.get(), st.n_reads,
                                                          d_events.get(), d_counts.get(), p.bucket_size, static_cast<int32_t>(file_index), st.words.data(),
                                                          st.words.size(), &n_words, s);
     if (rc == GTX_ERR_CAPACITY && turn == 0 && n_words > st.words.size())
@@ -273,7 +344,7 @@ int first_pass(Worker & w, gtx_disc_file const & f, uint32_t file_index, gtx_dis
 // the files of one pass over the workers: file i on worker i % n_workers, each worker's files in their order.  What a file's run
 // returns, with the thread's message, stays with the file; nothing is thrown across a thread's edge.
 template <class Run>
-void over_files(std::vector<Worker> & workers, std::vector<FileState> & files, Run run)
+void over_files(char const * who, std::vector<Worker> & workers, std::vector<FileState> & files, Run run)
 {
   auto work = [&](size_t w)
   {
@@ -288,7 +359,7 @@ void over_files(std::vector<Worker> & workers, std::vector<FileState> & files, R
       catch (std::exception const & e)
       {
         files[i].rc = GTX_ERR_CAPACITY;
-        files[i].error = std::string("gtx_discover_region: ") + e.what();
+        files[i].error = std::string(who) + ": " + e.what();
       }
       if (files[i].rc != GTX_OK)
         return;
@@ -325,8 +396,10 @@ int first_error(std::vector<FileState> const & files)
   return GTX_OK;
 }
 
-int discover(char const * reference, uint64_t reference_len, int64_t region_begin, char const * contig, gtx_disc_file const * files, uint32_t n_files,
-             gtx_discover_params const & p, gtx_discover_result & res)
+// load(worker, i, state): file i's arrays onto the device, their sizes into its state
+template <class Load>
+int discover(char const * who, char const * reference, uint64_t reference_len, int64_t region_begin, char const * contig, uint32_t n_files, gtx_discover_params const & p,
+             gtx_discover_result & res, Load load)
 {
   uint32_t const n_workers = std::min(p.n_threads, n_files);
   std::vector<Worker> workers(n_workers);
@@ -344,7 +417,10 @@ int discover(char const * reference, uint64_t reference_len, int64_t region_begi
     w.stream.reset(s);
   }
   std::vector<FileState> state(n_files); // (behind the workers: the files' blocks go back before the streams and the objects do)
-  over_files(workers, state, [&](Worker & w, size_t i, FileState & st) { return first_pass(w, files[i], static_cast<uint32_t>(i), p, st); });
+  over_files(who, workers, state, [&](Worker & w, size_t i, FileState & st) {
+    int const rc = load(w, i, st);
+    return rc != GTX_OK ? rc : first_pass(w, static_cast<uint32_t>(i), p, st);
+  });
   if (int const rc = first_error(state))
     return rc;
   // the merge, in file order
@@ -365,8 +441,8 @@ int discover(char const * reference, uint64_t reference_len, int64_t region_begi
     merged.swap(next);
   }
   // the second pass of every file, from the arrays still resident
-  over_files(workers, state, [&](Worker & w, size_t i, FileState & st) {
-    return second_file(w.disc.get(), st.planes.get(), files[i].plane_stride, st.reads.get(), st.cigar.get(), files[i].n_reads, merged.data(), merged.size(),
+  over_files(who, workers, state, [&](Worker & w, size_t i, FileState & st) {
+    return second_file(w.disc.get(), st.planes.get(), st.plane_stride, st.reads.get(), st.cigar.get(), st.n_reads, merged.data(), merged.size(),
                        static_cast<int32_t>(i), p.bucket_size, p.second_event_cap, false, w.stream.get(), st.second);
   });
   if (int const rc = first_error(state))
@@ -503,7 +579,8 @@ extern "C" int gtx_discover_region(const char * reference, uint64_t reference_le
   try
   {
     auto res = std::make_unique<gtx_discover_result>();
-    int const rc = discover(reference, reference_len, region_begin, contig, files, n_files, *params, *res);
+    int const rc = discover("gtx_discover_region", reference, reference_len, region_begin, contig, n_files, *params, *res,
+                            [&](Worker & w, size_t i, FileState & st) { return load_arrays(w, files[i], st); });
     if (rc == GTX_OK)
       *out = res.release();
     return rc;
@@ -511,6 +588,39 @@ extern "C" int gtx_discover_region(const char * reference, uint64_t reference_le
   catch (std::exception const & e)
   {
     g_last_error = std::string("gtx_discover_region: ") + e.what();
+    return GTX_ERR_CAPACITY;
+  }
+}
+
+extern "C" int gtx_discover_files(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const char * const * bam_paths,
+                                  uint32_t n_files, const gtx_discover_params * params, gtx_discover_result ** out)
+{
+  if (!out)
+    return bad("gtx_discover_files");
+  *out = nullptr;
+  if (!reference || reference_len == 0 || !contig || !bam_paths || n_files == 0 || !params || params->bucket_size == 0 || params->n_threads == 0 ||
+      params->n_threads > 8)
+    return bad("gtx_discover_files");
+  for (uint32_t i = 0; i < n_files; ++i)
+    if (!bam_paths[i])
+      return bad("gtx_discover_files", "a path");
+  if (params->device < 0) // (before any file is opened)
+  {
+    g_last_error = "gtx_discover_files: no device (libgtx has no CPU path)";
+    return GTX_ERR_NO_DEVICE;
+  }
+  try
+  {
+    auto res = std::make_unique<gtx_discover_result>();
+    int const rc = discover("gtx_discover_files", reference, reference_len, region_begin, contig, n_files, *params, *res,
+                            [&](Worker & w, size_t i, FileState & st) { return load_bam(w, bam_paths[i], st); });
+    if (rc == GTX_OK)
+      *out = res.release();
+    return rc;
+  }
+  catch (std::exception const & e)
+  {
+    g_last_error = std::string("gtx_discover_files: ") + e.what();
     return GTX_ERR_CAPACITY;
   }
 }

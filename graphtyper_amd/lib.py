@@ -39,6 +39,7 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_disc_second_rounds", "gtx_disc_second_decide",
            "gtx_disc_variants", "gtx_disc_vcf_sites", "gtx_disc_second_file", "gtx_discover_params_default", "gtx_discover_region", "gtx_discover_destroy",
            "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats",
+           "gtx_disc_bam_read", "gtx_disc_bam_destroy", "gtx_disc_bam_stream", "gtx_disc_bam_reads", "gtx_disc_bam_info", "gtx_disc_bam_unpack", "gtx_discover_files",
            "gtx_wave_probe"]
 
 
@@ -310,6 +311,20 @@ def lib():
         L.gtx_discover_good.restype = C.c_void_p
         L.gtx_discover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.gtx_discover_stats.restype = C.POINTER(DiscoverFileStats)
+        if hasattr(L, "gtx_discover_files"):  # (GTX_LIB= a build of an earlier commit has no BAM front end of discovery)
+            L.gtx_disc_bam_read.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+            L.gtx_disc_bam_destroy.argtypes = [C.c_void_p]
+            L.gtx_disc_bam_destroy.restype = None
+            L.gtx_disc_bam_stream.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+            L.gtx_disc_bam_stream.restype = C.c_void_p
+            L.gtx_disc_bam_reads.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
+            L.gtx_disc_bam_reads.restype = C.c_void_p
+            L.gtx_disc_bam_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+            L.gtx_disc_bam_info.restype = C.c_char_p
+            L.gtx_disc_bam_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_uint32, C.c_void_p]
+            L.gtx_discover_files.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(DiscoverParams),
+                                             C.POINTER(C.c_void_p)]
         L.gtx_wave_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -791,12 +806,23 @@ def discover_region(reference, region_begin, contig, files, device=0, bucket_siz
         keep.append((planes, qual, reads, cigar))
         structs[i] = DiscFile(planes.ctypes.data if planes.size else None, qual.ctypes.data if qual.size else None, reads.ctypes.data if len(reads) else None,
                               cigar.ctypes.data if len(cigar) else None, int(f["plane_stride"]), int(f["qual_stride"]), len(reads), len(cigar))
-    params = DiscoverParams()
-    L.gtx_discover_params_default(C.byref(params))
-    params.device, params.bucket_size, params.max_read_len, params.n_threads = device, bucket_size, max_read_len, n_threads
-    params.first_event_cap, params.second_event_cap = first_event_cap, second_event_cap
+    params = _discover_params(device, bucket_size, max_read_len, n_threads, first_event_cap, second_event_cap)
     h = C.c_void_p()
     check(L.gtx_discover_region(refb, len(refb), region_begin, contig.encode(), structs, len(files), C.byref(params), C.byref(h)))
+    return _discover_result(h)
+
+
+def _discover_params(device, bucket_size, max_read_len, n_threads, first_event_cap, second_event_cap):
+    params = DiscoverParams()
+    lib().gtx_discover_params_default(C.byref(params))
+    params.device, params.bucket_size, params.max_read_len, params.n_threads = device, bucket_size, max_read_len, n_threads
+    params.first_event_cap, params.second_event_cap = first_event_cap, second_event_cap
+    return params
+
+
+def _discover_result(h):
+    """what a gtx_discover_result holds, as discover_region documents it; the handle is destroyed"""
+    L = lib()
     try:
         def view(ptr, dtype, count):
             return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
@@ -816,6 +842,45 @@ def discover_region(reference, region_begin, contig, files, device=0, bucket_siz
         return out
     finally:
         L.gtx_discover_destroy(h)
+
+
+def discover_files(reference, region_begin, contig, paths, device=0, bucket_size=50, max_read_len=0, n_threads=1, first_event_cap=0, second_event_cap=0):
+    """gtx_discover_files: discover_region from BAM paths (one sample each, read whole and in file order) -> what discover_region returns"""
+    L = lib()
+    refb = reference.encode("latin-1") if isinstance(reference, str) else bytes(reference)
+    arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+    params = _discover_params(device, bucket_size, max_read_len, n_threads, first_event_cap, second_event_cap)
+    h = C.c_void_p()
+    check(L.gtx_discover_files(refb, len(refb), region_begin, contig.encode(), arr, len(paths), C.byref(params), C.byref(h)))
+    return _discover_result(h)
+
+
+def disc_bam_read(path):
+    """gtx_disc_bam_read: a BAM file of discovery, read whole -> dict(stream [uint8: the records as they lie in the file], slack [bytes
+    behind the stream a device block has to have], reads [DISC_READ], offsets [uint32: each record's 32 fixed bytes in the stream],
+    max_l_seq, n_cigar, sample [str]) of copies"""
+    L = lib()
+    h = C.c_void_p()
+    check(L.gtx_disc_bam_read(os.fsencode(path), C.byref(h)))
+    try:
+        def view(ptr, dtype, count):
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+        n64, slack, n32, offsets, longest, n_cigar = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_void_p(), C.c_uint32(), C.c_uint64()
+        ptr = L.gtx_disc_bam_stream(h, C.byref(n64), C.byref(slack))
+        out = dict(stream=view(ptr, np.uint8, n64.value), slack=int(slack.value))
+        ptr = L.gtx_disc_bam_reads(h, C.byref(n32), C.byref(offsets))
+        out.update(reads=view(ptr, DISC_READ, n32.value), offsets=view(offsets.value, np.uint32, n32.value))
+        sample = L.gtx_disc_bam_info(h, C.byref(longest), C.byref(n_cigar))
+        out.update(max_l_seq=int(longest.value), n_cigar=int(n_cigar.value), sample=sample.decode())
+        return out
+    finally:
+        L.gtx_disc_bam_destroy(h)
+
+
+def disc_bam_unpack(handle, d_stream, n_bytes, d_offsets, d_reads, n_reads, d_planes, plane_stride, d_qual, qual_stride, d_cigar, n_cigar, stream=None):
+    """gtx_disc_bam_unpack over device arrays of the caller's (pointers as integers): the stream, offsets and reads of disc_bam_read,
+    uploaded -> the plane rows, quality rows and CIGAR words written; raises GtxError on any status but GTX_OK"""
+    check(lib().gtx_disc_bam_unpack(handle, d_stream, n_bytes, d_offsets, d_reads, n_reads, d_planes, plane_stride, d_qual, qual_stride, d_cigar, n_cigar, stream))
 
 
 def disc_realign_target(handle, max_read_size, events):

@@ -1054,7 +1054,8 @@ int gtx_bam_shrink_multi(const char * bam_in, const char * interval_file, const 
  * an indel's round -- is gtx_disc_indel_table / gtx_disc_second_* (at the end of this header).
  * The rounds of the realignment and the final good-support decision are gtx_disc_second_rounds / gtx_disc_second_decide, the variant
  * records and the sites file gtx_disc_variants / gtx_disc_vcf_sites, a file's second pass and a whole region in one call
- * gtx_disc_second_file / gtx_discover_region (all at the end of this header).
+ * gtx_disc_second_file / gtx_discover_region, and the region from its BAM files gtx_disc_bam_read / gtx_disc_bam_unpack /
+ * gtx_discover_files (all at the end of this header).
  *   gtx_disc_create        the region's reference (upper-case letters; reference[0] = contig position region_begin, 0-based) on `device`
  *   gtx_disc_events_batch  device: the events of n_reads reads in stream order.  d_planes: the reads as plane rows (gtx_pack_planes),
  *                          d_qual: their base qualities (qual_stride bytes per read), d_reads / d_cigar: the bam1_t fields and the raw
@@ -1548,6 +1549,55 @@ const gtx_disc_variant * gtx_discover_variants(const gtx_discover_result *, uint
 const uint32_t * gtx_discover_words(const gtx_discover_result *, uint64_t * n_words);
 const uint8_t * gtx_discover_good(const gtx_discover_result *, uint32_t * n_table); /* per table entry: entry.good | its bit */
 const gtx_discover_file_stats * gtx_discover_stats(const gtx_discover_result *, uint32_t * n_files);
+
+/* ---- discovery from BAM files.  The reference's streamlined_discovery takes the per-region files bamshrink leaves:
+ * parallel_first_pass and parallel_second_pass (src/typer/caller.cpp:2511-2571, :2633-2682) open each with region "." and read every
+ * record in file order with get_next_read.  Here a file is read once on the host, its record stream is uploaded once, and one kernel
+ * splits the records into the four arrays gtx_disc_events_batch takes.
+ *   gtx_disc_bam_read      host: the whole file as the reference reads it -- every record, file order, tid not looked at, no index.
+ *                          The handle holds the record stream (the inflated bytes behind the header as they lie in the file: per
+ *                          record its block_size word, the 32 fixed bytes, name, CIGAR, bases, qualities, aux data), and per record
+ *                          a gtx_disc_read entry -- pos, flag, mapq, l_qseq, n_cigar; cigar_off: the running sum of n_cigar -- and the offset of
+ *                          its 32 fixed bytes in the stream.  Every record's counts are checked against its block, so the device
+ *                          never follows a length nobody checked.  The statuses are those of gtx_reads_open / gtx_reads_next for the
+ *                          same damage: not BAM GTX_ERR_UNSUPPORTED; a file that cannot be opened, a truncated header or record, a
+ *                          block below 32 bytes, counts beyond the block GTX_ERR_IO; an @RG line without ID or SM GTX_ERR_ARG.
+ *                          A read of more than 65 535 bases (l_qseq has 16 bits) and a header with more than one sample (the reference
+ *                          exits there, caller.cpp:2537-2544) GTX_ERR_UNSUPPORTED.  A file without records is legal.
+ *                          STATED LIMITS: a record stream of 2^32 bytes or more is GTX_ERR_CAPACITY (the offsets have 32 bits; no test
+ *                          reaches it); htslib's CG:B,I substitution for CIGARs of more than 65 535 operations is not followed (such a
+ *                          read keeps the two placeholder operations of its record).  Every message names the path.
+ *   gtx_disc_bam_stream / _reads / _info   what the handle holds, alive until gtx_disc_bam_destroy.  *slack: bytes behind the stream
+ *                          that belong to the block (the kernel may read that far; zero-filled).  sample: the SM of the @RG lines, or
+ *                          the file name up to its first '.' (hts_reader.cpp:83-91).
+ *   gtx_disc_bam_unpack    device: stream, offsets and reads as gtx_disc_bam_read left them, uploaded -> per record its plane row
+ *                          (the layout of gtx_pack_planes; the whole row of plane_stride bytes is written, zero behind l_qseq), its
+ *                          quality row (l_qseq bytes as they lie in the record, 0xFF as any other; zero up to qual_stride) and its
+ *                          CIGAR words at d_cigar + cigar_off.  One wavefront per record, a lane per base; nothing else is written.
+ *                          plane_stride not a multiple of 16, a read longer than its plane or quality row, a read whose CIGAR words
+ *                          lie behind n_cigar, an offset whose record cannot lie in n_bytes, d_planes or d_cigar not 4-byte aligned,
+ *                          NULL with n_reads != 0: GTX_ERR_ARG -- the call reads d_reads and d_offsets back for this and waits for
+ *                          `stream` once.  n_reads == 0: GTX_OK, nothing launched.  A gtx_disc made with device -1: GTX_ERR_NO_DEVICE.
+ *                          THE STREAM MUST BE ONE THAT gtx_disc_bam_read MADE, with its own two tables: the kernel takes a record's
+ *                          l_read_name from the stream's byte, which only that walk has held to the record's block; the call's own
+ *                          check of an offset allows for a name of one byte, so with a stream of another origin the kernel can read up
+ *                          to 254 bytes behind n_bytes.
+ *   gtx_discover_files     gtx_discover_region from BAM paths: per file, on its worker, gtx_disc_bam_read, one upload of the stream
+ *                          and the two tables, gtx_disc_bam_unpack into arrays of the library's cache (plane_stride: the smallest
+ *                          multiple of 16 that holds the file's longest read, at least 16; qual_stride: that length rounded up to 4,
+ *                          at least 4), then what gtx_discover_region does behind its uploads.  Same parameters, same result
+ *                          handle.  The first failing file, in file order, ends the call with its status and a message that names
+ *                          the path; device -1 is GTX_ERR_NO_DEVICE before any file is opened. */
+typedef struct gtx_disc_bam gtx_disc_bam;
+int gtx_disc_bam_read(const char * path, gtx_disc_bam ** out);
+void gtx_disc_bam_destroy(gtx_disc_bam *);
+const uint8_t * gtx_disc_bam_stream(const gtx_disc_bam *, uint64_t * n_bytes, uint32_t * slack);
+const gtx_disc_read * gtx_disc_bam_reads(const gtx_disc_bam *, uint32_t * n_reads, const uint32_t ** offsets);
+const char * gtx_disc_bam_info(const gtx_disc_bam *, uint32_t * max_l_seq, uint64_t * n_cigar); /* -> the sample name */
+int gtx_disc_bam_unpack(gtx_disc *, const uint8_t * d_stream, uint64_t n_bytes, const uint32_t * d_offsets, const gtx_disc_read * d_reads, uint32_t n_reads,
+                        uint8_t * d_planes, uint32_t plane_stride, uint8_t * d_qual, uint32_t qual_stride, uint32_t * d_cigar, uint32_t n_cigar, void * stream);
+int gtx_discover_files(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const char * const * bam_paths,
+                       uint32_t n_files, const gtx_discover_params * params, gtx_discover_result ** out);
 
 /* Inspection of the wavefront primitives every kernel is written against (csrc/graph_dev.hpp: the wave policy's table): runs
  * csrc/wave_probe.hpp on `device`, one wavefront per input set.  in: n_sets x 200 words, out: n_sets x 340 words, both HOST
