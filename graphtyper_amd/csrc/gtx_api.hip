@@ -17,6 +17,7 @@
 
 #include <map>
 #include "gtx_devmem.hpp"
+#include "gtx_switches.hpp"
 #include "wave_hip.hpp"
 #include "align_core.hpp"
 #include "gtx_hbm_passes.hpp"
@@ -45,11 +46,6 @@ constexpr uint64_t PROF_WORDS = 40 + PROF_LOG_ENTRIES * PROF_LOG_ENTRY;
 // sends one atomic per (counter, workgroup visit) to memory.  Sums are order-free, so the accumulators come out the same.
 #ifndef GTX_SCORE_THREADS
 #define GTX_SCORE_THREADS 64 // threads of a gtx_score_kernel workgroup: one wavefront goes wherever a slot is beside another batch's queues (cfg2, steps in flight: 256 / 128 / 64 threads = 0.798 / 0.788 / 0.783 ms per step; alone the same)
-#endif
-#ifdef GTX_SCORE_ADDS_CALLED // (A/B build: one body for all of an item's adds, a call each)
-#define GTX_SCORE_ADD_INLINE __attribute__((noinline))
-#else
-#define GTX_SCORE_ADD_INLINE inline
 #endif
 #ifndef GTX_WAVE_GROUP_MIN
 #define GTX_WAVE_GROUP_MIN 4
@@ -111,10 +107,6 @@ struct WaveHipCombine : WaveHip
   // Returns true for the lane that has to add *sum (false: another lane does it).
   static __device__ inline bool wave_group(unsigned long long key, unsigned long long v, unsigned long long & sum)
   {
-#ifdef GTX_NO_WAVE_GROUP // (A/B build: every lane for itself)
-    sum = v;
-    return true;
-#else
     // (groups are formed while they are worth it: one sample deep, a wavefront's lanes make two or three large ones; thirty samples
     //  wide, nearly every lane has a counter of its own, and forming 64 groups of one -- a round of readfirstlanes and a ballot
     //  each, for every one of an item's fifteen adds -- was HALF of the kernel on cfg3.  The first group of fewer than
@@ -137,7 +129,6 @@ struct WaveHipCombine : WaveHip
     }
     sum = v;
     return true;
-#endif
   }
   // The scope around the adds of ONE site entry (apply_recent's statistics / likelihood / depth loop).  A cfg2 entry makes about
   // eight adds, and the lanes of a position-sorted wavefront -- one or two sites x two alleles -- would form the same two to four
@@ -155,9 +146,6 @@ struct WaveHipCombine : WaveHip
   static __device__ inline bool entry_begin(uint32_t sample, uint32_t site, uint32_t coverage, Set const & explains, uint32_t eps, uint32_t clipped_bp,
                                             uint32_t read_len, uint32_t mapq, uint32_t flags, uint32_t mm8, uint32_t score_diff, bool proper_pair)
   {
-#ifdef GTX_NO_WAVE_GROUP // (A/B build: every lane for itself, add by add)
-    return true;
-#else
     // the key, field by field (compared as it is: a hash would not be equality).  coverage is 16 bits, the strand and first-in-pair
     // bits two, eps at most 8 (four bits), mm8 eight bits, read_len 14 (geno_of) and mapq 8: no field reaches into another
     constexpr uint32_t NK = 3 + Set::WORDS32 / 2;
@@ -192,17 +180,12 @@ struct WaveHipCombine : WaveHip
       return false;
     entry_words()[threadIdx.x] = members;
     return true;
-#endif
   }
   static __device__ inline void entry_end() { entry_words()[threadIdx.x] = 0u; }
-#if defined(GTX_EXPERIMENT) && defined(GTX_X_SCORE_NO_ADDS) // (experiment builds only, wrong results: what the kernel takes without its adds)
-  static __device__ inline void atomic_add_u32(uint32_t *, uint32_t) {}
-  static __device__ inline void atomic_add_u64(unsigned long long *, unsigned long long) {}
-#else
   // (inlined, the fifteen adds of a site times the four places an item's entries are applied make the kernel 131 KB of code, twice
-  //  the instruction cache two CUs share; as ONE body and a call each -- GTX_SCORE_ADDS_CALLED -- it is 49 KB and SLOWER: cfg3
+  //  the instruction cache two CUs share; as ONE body that is not inlined and a call each it is 49 KB and SLOWER: cfg3
   //  0.687 ms against 0.634, cfg2 0.160 against 0.146.  The instruction cache is not what the kernel waits for.)
-  static __device__ GTX_SCORE_ADD_INLINE void add_to(unsigned long long address, bool is64, unsigned long long v)
+  static __device__ inline void add_to(unsigned long long address, bool is64, unsigned long long v)
   {
     unsigned long long sum;
     uint32_t const members = entry_words()[threadIdx.x]; // (0: no entry scope is open, the lanes with this add find each other)
@@ -221,7 +204,6 @@ struct WaveHipCombine : WaveHip
   }
   static __device__ inline void atomic_add_u32(uint32_t * p, uint32_t v) { add_to(reinterpret_cast<unsigned long long>(p), false, v); }
   static __device__ inline void atomic_add_u64(unsigned long long * p, unsigned long long v) { add_to(reinterpret_cast<unsigned long long>(p), true, v); }
-#endif
   // all threads of the workgroup
   static __device__ inline void clear(unsigned long long base)
   {
@@ -247,9 +229,6 @@ struct WaveHipCombine : WaveHip
       {
         uint32_t const v = t.val[i];
         unsigned long long const address = t.base + (static_cast<unsigned long long>(k & 0x7FFFFFFFu) << 2);
-#if defined(GTX_EXPERIMENT) && defined(GTX_X_SCORE_NO_FLUSH) // (experiment builds only, wrong results: the table is summed into, nothing reaches memory)
-        if (v == 0xFFFFFFFFu && address == 1ull)
-#endif
         if (k & 0x80000000u)
           atomicAdd(reinterpret_cast<unsigned long long *>(address), static_cast<unsigned long long>(v));
         else
@@ -265,13 +244,7 @@ struct WaveHipCombine : WaveHip
 // The bulk traffic of the position-hinted pass -- every read's bases and meta record in, every record out, each touched
 // once -- is marked non-temporal (the `nt` bit of the global load / store): it streams through the caches without pushing
 // out what the passes behind it live on (their code, the index and graph tables), which they would otherwise find cold at
-// every launch.  GTX_NO_NT at build time: plain accesses (A/B).
-#ifdef GTX_NO_NT
-template <class T>
-static __device__ inline T stream_load(T const * p) { return *p; }
-template <class T>
-static __device__ inline void stream_store(T * p, T const & v) { *p = v; }
-#else
+// every launch.
 static __device__ inline uint32_t stream_load(uint32_t const * p) { return __builtin_nontemporal_load(p); }
 static __device__ inline uint4_t stream_load(uint4_t const * p)
 {
@@ -285,7 +258,6 @@ static __device__ inline void stream_store(uint4_t * p, uint4_t const & v)
   v4 const x = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(x, reinterpret_cast<v4 *>(p));
 }
-#endif
 
 #ifndef GTX_TASK_CHUNK
 #define GTX_TASK_CHUNK 64
@@ -481,13 +453,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GTX_WIDE_WAV
 // task is settled (empty record, or queued for pass 2 when align_read asks for it), reads outside the length limits get
 // their empty records, and the forward task is finished from the position hint where the flags of that place prove the
 // global lookups -- else the read is queued for pass 1 (express4 over the queue).  One atomic per wavefront and queue.
-// (profiling build only, GTX_HINT=x: a timing experiment that lets the results land in the first 1 024 record slots, i.e. stay in
-//  the L2 -- it destroys the results, so the release library has no such switch)
-#ifdef GTX_PROF
-#define GTX_HINT_REC_SLOT(read) ((decline_all & 2u) ? ((read) & 1023u) : (read))
-#else
-#define GTX_HINT_REC_SLOT(read) (read)
-#endif
 template <uint32_t WAVES, bool DENSE, uint32_t NK = AlignCfg::KC, bool META_LDS = true>
 __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const & ix, uint8_t const * __restrict__ seq, uint32_t seq_stride,
                                             gtx_read_meta const * __restrict__ meta, uint32_t n_reads, uint32_t * __restrict__ records,
@@ -588,7 +553,7 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
     //  spilled ones and 2 % of the kernel)
     auto rec_at = [&]() -> uint32_t *
     {
-      uint32_t r = GTX_HINT_REC_SLOT(read);
+      uint32_t r = read;
       GTX_PIN(r);
       return records + static_cast<uint64_t>(r) * 2 * rec_words;
     };
@@ -651,7 +616,6 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
     }
     // the dense side array (gtx_align_batch_flags): what this pass settles -- the forward task it finished, the reverse
     // task that is not aligned at all; the queued tasks get theirs from gtx_task_flags_fixup_kernel behind the last pass
-#ifndef GTX_X_NO_FLAG_STORE /* (experiment build: the kernel without its side bytes) */
     if (task_flags)
     {
       // (both bytes of a read in ONE store where this pass settles both -- nearly every read: a wavefront's 64 pairs are one whole
@@ -668,7 +632,6 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
           task_flags[2ull * read + 1] = 0;
       }
     }
-#endif
   }
   if (var_mask)
   {
@@ -690,9 +653,7 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
     for (uint32_t k = 0; k < 2; ++k)
     {
       uint32_t const r = 32u * k + (lane >> 1);
-#ifndef GTX_X_NO_COMPACT_STORE /* (experiment build: the kernel without its dense records) */
       stream_store(dst + 64u * k + lane, s_seq[wave][r * ROW_PITCH + (lane & 1u)]);
-#endif
     }
   }
   {
@@ -713,10 +674,8 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
         {
           uint4_t const v = s_seq[wave][r * ROW_PITCH + part];
           uint32_t const rd = wave_first + r;
-          uint32_t * dst = records + static_cast<uint64_t>(GTX_HINT_REC_SLOT(rd)) * 2 * rec_words;
-#ifndef GTX_X_NO_REC_STORE /* (experiment build: the kernel without its record stores) */
+          uint32_t * dst = records + static_cast<uint64_t>(rd) * 2 * rec_words;
           stream_store(reinterpret_cast<uint4_t *>(dst + 4 * part), v);
-#endif
         }
       }
     }
@@ -1336,11 +1295,6 @@ __global__ __launch_bounds__(TRIAGE_THREADS) void gtx_score_triage_kernel(gtx_sc
 }
 
 // Scoring, stage 2: the items of the work queue, one thread each (orientation / pair selection, path checks, atomics).
-#ifdef GTX_SCORE_WAVES // A/B builds: wavefronts per SIMD the compiler sizes the registers for
-#define GTX_SCORE_ATTR __attribute__((amdgpu_waves_per_eu(GTX_SCORE_WAVES, GTX_SCORE_WAVES)))
-#else
-#define GTX_SCORE_ATTR
-#endif
 // one item of the scoring kernels' visits (lane = item): the record staged through LDS, score_item, the second pass' queue
 constexpr uint32_t SCORE_STAGE_WORDS = 16, SCORE_STAGE_PITCH = SCORE_STAGE_WORDS + 1; // (an odd pitch: a word of every lane's row in a bank of its own)
 __device__ __forceinline__ void score_visit(GraphView const & g, ScoreParams const & par, gtx_score_item const & it, uint32_t i, uint32_t const * __restrict__ records,
@@ -1351,7 +1305,6 @@ __device__ __forceinline__ void score_visit(GraphView const & g, ScoreParams con
   // walks it word by word, every look a dependent load (PMC, cfg3: 68 vector loads per visit, each waited for -- the
   // kernel's time is their latencies in a row).  Records that are longer than the copy, in the arena or wide stay where they are.
   ScoreAcc mine = acc;
-#ifndef GTX_NO_SCORE_STAGING
   if ((rec_words & 3u) == 0u)
   {
     uint32_t const ai = it.first.align_index;
@@ -1383,7 +1336,6 @@ __device__ __forceinline__ void score_visit(GraphView const & g, ScoreParams con
       mine.staged_copy = row;
     }
   }
-#endif
   RecentHap r1[SCORE_MAX_HAPS], r2[SCORE_MAX_HAPS];
   if (!score_item<WaveHipCombine>(g, par, it, records, rec_words, mine, r1, r2, SCORE_MAX_HAPS))
   {
@@ -1397,7 +1349,7 @@ __device__ __forceinline__ void score_visit(GraphView const & g, ScoreParams con
   }
 }
 
-__global__ __launch_bounds__(GTX_SCORE_THREADS) GTX_SCORE_ATTR void gtx_score_kernel(GraphView g, ScoreParams par, gtx_score_item const * __restrict__ items,
+__global__ __launch_bounds__(GTX_SCORE_THREADS) void gtx_score_kernel(GraphView g, ScoreParams par, gtx_score_item const * __restrict__ items,
                                                         uint32_t const * __restrict__ work_queue, uint32_t const * work_count,
                                                         uint32_t const * __restrict__ records, uint32_t rec_words, ScoreAcc acc,
                                                         uint32_t * error_flag, uint32_t * __restrict__ big_queue,
@@ -1766,7 +1718,7 @@ int ctx_upload(gtx_ctx & c, int device)
   if (!hip_ok(hipSetDevice(device), "hipSetDevice"))
     return GTX_ERR_HIP;
   c.device = device;
-  bool const timing = std::getenv("GTX_TIMING") != nullptr; // stage times on stderr
+  bool const timing = sw::timing(); // stage times on stderr
   auto t_last = std::chrono::steady_clock::now();
   auto lap = [&](char const * what)
   {
@@ -1874,15 +1826,11 @@ int ctx_upload(gtx_ctx & c, int device)
   c.wall_clock_khz = facts.wall_clock_khz;
   if (ok && !c.params.no_second_pass)
   {
-    // HBM-table pass: one workspace per workgroup (one workgroup per CU is plenty for the few queued reads), arena
-    // (GTX_BIG_BLOCKS_PER_CU: A/B switch.  One workgroup per CU was "plenty for the few queued reads" of an i.i.d. reference; on a
+    // HBM-table pass: one workspace per workgroup, arena
+    // (GTX_BIG_BLOCKS_PER_CU workgroups per CU: one was "plenty for the few queued reads" of an i.i.d. reference; on a
     //  reference with repeats tens of thousands of tasks come this far, every one a chain of dependent round trips to HBM, and the
     //  pass' throughput is the number of tasks in flight)
-    {
-      char const * bb = std::getenv("GTX_BIG_BLOCKS_PER_CU");
-      uint32_t const per_cu = bb && std::atoi(bb) > 0 ? static_cast<uint32_t>(std::min(std::atoi(bb), 16)) : GTX_BIG_BLOCKS_PER_CU;
-      c.big_blocks = (have_prop ? static_cast<uint32_t>(prop.multiProcessorCount) : 256u) * per_cu;
-    }
+    c.big_blocks = (have_prop ? static_cast<uint32_t>(prop.multiProcessorCount) : 256u) * GTX_BIG_BLOCKS_PER_CU;
     c.big_record_words = c.params.big_record_words ? c.params.big_record_words : (16ull << 20);
     // exact pass: the slab of a call in flight, and the walk candidates one task of this graph can have alive
     {
@@ -1890,22 +1838,19 @@ int ctx_upload(gtx_ctx & c, int device)
       for (uint32_t n : c.graph.ref_nvar)
         widest = std::max(widest, n);
       c.exact_cand_cap = exact::exact_cand_cap(widest);
-      char const * xm = std::getenv("GTX_EXACT_PASS_MB");
-      uint64_t mb = c.params.exact_pass_mb ? c.params.exact_pass_mb : (xm && std::atol(xm) > 0) ? static_cast<uint64_t>(std::atol(xm)) : (c.has_wide_sites ? 4096u : 2048u);
+      uint64_t const mb_env = sw::exact_pass_mb();
+      uint64_t mb = c.params.exact_pass_mb ? c.params.exact_pass_mb : mb_env ? mb_env : (c.has_wide_sites ? 4096u : 2048u);
       c.exact_slab_bytes = mb << 20;
-      c.exact_mb_given = c.params.exact_pass_mb != 0 || (xm && std::atol(xm) > 0);
+      c.exact_mb_given = c.params.exact_pass_mb != 0 || mb_env != 0;
       // at most 1 024 parts, none smaller than 2 MB (32 MB where allele sets are wide); the kernel makes as many as there are tasks:
       // the tasks that come this far come in bulk -- every read over one long repeat -- and what one task takes is milliseconds
       // of dependent round trips
-      char const * xq = std::getenv("GTX_EXACT_PARTS_MAX"); // (A/B switch: the most parts of the first launch)
-      uint64_t const most_parts = xq && std::atol(xq) > 0 ? static_cast<uint64_t>(std::min<long>(std::atol(xq), 4096)) : GTX_EXACT_PARTS_MAX;
-      c.exact_parts = static_cast<uint32_t>(std::min<uint64_t>(most_parts, std::max<uint64_t>(1u, mb / (c.has_wide_sites ? 32u : 2u))));
-      if (char const * xp = std::getenv("GTX_EXACT_PARTS")) // (tests: smaller parts, so that tasks reach the launch with the whole slab)
-        if (std::atol(xp) > 0)
-        {
-          c.exact_parts = static_cast<uint32_t>(std::min<long>(std::atol(xp), 1024));
-          c.exact_fixed_parts = true;
-        }
+      c.exact_parts = static_cast<uint32_t>(std::min<uint64_t>(GTX_EXACT_PARTS_MAX, std::max<uint64_t>(1u, mb / (c.has_wide_sites ? 32u : 2u))));
+      if (uint32_t const parts = sw::exact_parts()) // (tests: smaller parts, so that tasks reach the launch with the whole slab)
+      {
+        c.exact_parts = parts;
+        c.exact_fixed_parts = true;
+      }
     }
     ok = ok && ctx_alloc(c.d_big_records, c.big_record_words * sizeof(uint32_t), "big-record arena");
     if (ok)
@@ -2221,7 +2166,7 @@ static int align_setup(AlignCall & a)
     epoch = c->time_epoch;
     // (GTX_TIME_EVERY=n: one call in n is timed -- a timed call brackets its launches with events, packets the streams carry
     //  between the kernels; the means of gtx_ctx_kernel_times are over the timed calls)
-    static uint32_t const every = [] { char const * e = std::getenv("GTX_TIME_EVERY"); int const v = e ? std::atoi(e) : 1; return static_cast<uint32_t>(v > 0 ? v : 1); }();
+    static uint32_t const every = sw::time_every();
     if (a.timed && every > 1 && (c->timed_seq++ % every) != 0)
       a.timed = false;
   }
@@ -2270,17 +2215,14 @@ static int align_front(AlignCall & a)
   AlignRequest const & r = a.r;
   uint32_t const n = r.n_reads;
   uint32_t * const counters = s->d_counters;
-  // test switch: 1 = every task goes through all passes (the last one decides), 2 = every task is done by pass 2
-  char const * fb = std::getenv("GTX_FORCE_SECOND_PASS");
-  uint32_t const force = fb ? static_cast<uint32_t>(std::atoi(fb)) : 0u;
+  sw::AlignSwitches const env = sw::align_switches();
+  uint32_t const force = env.force; // test switch: 1 = every task goes through all passes (the last one decides), 2 = every task is done by pass 2
   uint32_t const n_cu = static_cast<uint32_t>(c->n_cu > 0 ? c->n_cu : 256);
   uint32_t const force_both = static_cast<uint32_t>(c->params.force_align_both_orientations != 0);
-  char const * e4 = std::getenv("GTX_EXPRESS4"); // A/B switch: 0 = one read per wavefront in pass 1
-  char const * eh = std::getenv("GTX_HINT");     // A/B switch: 0 = no position-hinted pass
-  bool const four = !(e4 && e4[0] == '0');
-  a.hinted = four && !(eh && eh[0] == '0');
+  bool const four = env.four; // (A/B switches: GTX_EXPRESS4=0 = one read per wavefront in pass 1, GTX_HINT=0 = no position-hinted pass)
+  a.hinted = env.hinted;
   // GTX_EXPRESS4=lean / wide force a build (tests); else by the graph's density
-  bool const wide = e4 && e4[0] == 'w' ? true : e4 && e4[0] == 'l' ? false : c->express4_wide;
+  bool const wide = env.wide(c->express4_wide);
   // grids: as many single-wave workgroups as are resident at once; they pull work from shared counters
   uint64_t const chunks = (static_cast<uint64_t>(n) + TASK_CHUNK - 1) / TASK_CHUNK;
   uint32_t const express4_per_cu = static_cast<uint32_t>(wide ? c->express4_wide_blocks_per_cu : c->express4_blocks_per_cu);
@@ -2290,21 +2232,16 @@ static int align_front(AlignCall & a)
     // pass 0: one read per lane from the position hint; what it declines is queued for pass 1.  (GTX_HINT=decline: the
     // pass runs but declines everything -- a test of the queue plumbing)
     bool const sv_skips_express = c->params.is_sv_graph != 0 && force == 0;
-    char const * hb = std::getenv("GTX_HINT_BUILD"); // (test switch: lean | dense build of pass 0; default: dense beside the wide express pass)
-    bool const hint_dense = hb && hb[0] == 'd' ? true : hb && hb[0] == 'l' ? false : c->express4_wide;
+    bool const hint_dense = env.hint_dense(c->express4_wide); // (test switch GTX_HINT_BUILD: lean | dense build of pass 0; default: dense beside the wide express pass)
     bool const hint_long = r.seq_stride > HintGeom<AlignCfg::KC>::ROW_BYTES; // (rows for reads of more than 160 bases: the eight-k-mer build)
     uint32_t const hint_threads = 64u * ((hint_long || hint_dense) ? GTX_HINT_WAVES : GTX_HINT_WAVES_LEAN);
     IndexView hint_index = c->dev_index;
-    hint_index.hint_less = hint_less_from_env(); // (A/B switch GTX_HINT_MORE=0: the pass declines what it declined before it learnt more shapes)
+    hint_index.hint_less = env.hint_less; // (A/B switch GTX_HINT_MORE=0: the pass declines what it declined before it learnt more shapes)
     hipLaunchKernelGGL(hint_long ? gtx_align_hinted_long_kernel : hint_dense ? gtx_align_hinted_dense_kernel : gtx_align_hinted_kernel,
                        dim3((n + hint_threads - 1u) / hint_threads), dim3(hint_threads), 0, r.stream, c->dev_graph, hint_index, r.seq, r.seq_stride,
                        r.meta, n, r.records, r.rec_words, force_both, s->d_queue1.get(), s->d_queue.get(), reinterpret_cast<unsigned long long *>(counters + 2),
-                       static_cast<uint32_t>(force != 0 || (eh && eh[0] == 'd')) | (sv_skips_express ? 4u : 0u)
-#ifdef GTX_PROF
-                         | (eh && eh[0] == 'x' ? 2u : 0u)
-#endif
-                         ,
-                       r.task_flags, r.compact, a.timed && s->h_span.get() ? s->d_span : static_cast<unsigned long long *>(nullptr), a.var_masks);
+                       static_cast<uint32_t>(env.decline_all) | (sv_skips_express ? 4u : 0u), r.task_flags, r.compact,
+                       a.timed && s->h_span.get() ? s->d_span : static_cast<unsigned long long *>(nullptr), a.var_masks);
     if (!hip_ok(hipGetLastError(), "gtx_align_hinted_kernel launch"))
       return GTX_ERR_HIP;
   }
@@ -2379,19 +2316,13 @@ static LongPassArgs long_args(AlignCall const & a)
 // context's slabs
 static int align_hbm(AlignCall & a)
 {
-#ifdef GTX_EXPERIMENT
-  // (experiment builds only -- never the product: what a step would take if the passes that find empty queues cost nothing)
-  static bool const skip_hbm_passes = std::getenv("GTX_SKIP_HBM_PASSES") != nullptr;
-#else
-  constexpr bool skip_hbm_passes = false;
-#endif
   gtx_ctx * const c = a.c;
   CallScratch * const s = a.s;
   AlignRequest const & r = a.r;
-  if (!s->d_big_state || skip_hbm_passes)
+  if (!s->d_big_state)
     return GTX_OK;
   // (GTX_BIG_GRID_ADAPTIVE=0, A/B switch: both passes are launched whole, not sized by what the batch before sent them)
-  static bool const adaptive = !(std::getenv("GTX_BIG_GRID_ADAPTIVE") && std::getenv("GTX_BIG_GRID_ADAPTIVE")[0] == '0');
+  static bool const adaptive = sw::big_grid_adaptive();
   HbmPassArgs h;
   h.g = c->dev_graph;
   h.ix = c->dev_index;

@@ -4,6 +4,7 @@
 #include "gtx_ctx.hpp"
 #include "gtx_inflate.hpp"
 #include "gtx_inflate_host.hpp"
+#include "gtx_switches.hpp"
 
 #include <zlib.h>
 
@@ -29,12 +30,12 @@ std::atomic<uint64_t> g_members_reader{0};   // inflated by their reader before 
 // the two switches of the BAM readers, read once each (when the first member is inflated)
 bool env_own_decoder()
 {
-  static bool const own = !(std::getenv("GTX_INFLATE") && std::strcmp(std::getenv("GTX_INFLATE"), "zlib") == 0);
+  static bool const own = !sw::inflate_zlib();
   return own;
 }
 bool env_check_crc()
 {
-  static bool const check = !(std::getenv("GTX_BGZF_CRC") && std::getenv("GTX_BGZF_CRC")[0] == '0');
+  static bool const check = sw::bgzf_crc();
   return check;
 }
 } // namespace
@@ -142,10 +143,7 @@ public:
     std::lock_guard<std::mutex> lock(slot().gate);
     if (slot().users++ == 0)
     {
-      unsigned n = std::min(std::max(std::thread::hardware_concurrency(), 1u), 16u);
-      if (char const * e = std::getenv("GTX_BGZF_THREADS"))
-        n = static_cast<unsigned>(std::max(0, std::atoi(e)));
-      slot().self = new InflateTeam(n);
+      slot().self = new InflateTeam(sw::bgzf_threads(std::min(std::max(std::thread::hardware_concurrency(), 1u), 16u)));
     }
   }
   static void release() { slot().release(); }
@@ -182,8 +180,7 @@ public:
 private:
   explicit InflateTeam(unsigned n)
   {
-    if (char const * e = std::getenv("GTX_BGZF_LINGER_US"))
-      linger_us_ = std::max(0, std::atoi(e));
+    linger_us_ = sw::bgzf_linger_us(linger_us_);
     for (unsigned i = 0; i < n; ++i)
       workers_.emplace_back([this] { run(); });
   }
@@ -495,9 +492,7 @@ int Bgzf::use_device(int device)
   int const rc = DeviceInflateTeam::acquire(device);
   if (rc != GTX_OK)
     return rc;
-  unsigned deep = 256;
-  if (char const * e = std::getenv("GTX_BGZF_DEVICE_RING"))
-    deep = static_cast<unsigned>(std::min(65536, std::max<int>(RING, std::atoi(e))));
+  unsigned const deep = sw::bgzf_device_ring(RING);
   std::unique_ptr<InflateJob[]> ring(new InflateJob[deep]);
   // the members in flight are finished where they are and move to the front of the deeper ring
   uint64_t n = 0;

@@ -14,6 +14,7 @@
 
 #include "gtx_ctx.hpp"
 #include "gtx_devmem.hpp"
+#include "gtx_switches.hpp"
 #include "graph_dev.hpp"
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -54,7 +55,7 @@ extern "C"
       return GTX_ERR_ARG;
     }
     *out = nullptr;
-    bool const timing = std::getenv("GTX_TIMING") != nullptr; // stage times on stderr
+    bool const timing = gtx::sw::timing(); // stage times on stderr
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](char const * what)
     {
@@ -74,7 +75,6 @@ extern "C"
     }
     for (uint32_t n : c->graph.ref_nvar)
       c->has_wide_sites = c->has_wide_sites || n > 64;
-    char const * hb = std::getenv("GTX_INDEX_BUILD"); // A/B switch: "host" builds the tables on the host and uploads them
     if (device < 0)
     {
       build_index(c->graph, c->index);
@@ -89,9 +89,7 @@ extern "C"
       // (gtx_index_dev.hip).  GTX_INDEX_RUNS=0: the host lists every k-mer (A/B, tests).
       std::vector<Emit> em;
       std::vector<EmitRun> runs;
-      char const * er = std::getenv("GTX_INDEX_RUNS");
-      bool const with_runs = !(er && er[0] == '0');
-      enumerate_kmers(c->graph, em, with_runs ? &runs : nullptr);
+      enumerate_kmers(c->graph, em, gtx::sw::index_runs() ? &runs : nullptr);
       lap("list the k-mers through sites (host)");
       if (em.size() + (runs.empty() ? 0ull : static_cast<uint64_t>(runs.back().dev_before) + runs.back().count) >= SLOT_OFF_MASK) // (label offsets are 31 bits in the index slots: gtx_flat.hpp, SLOT_NB_KNOWN)
       {
@@ -112,7 +110,6 @@ extern "C"
         return rc;
       }
       std::vector<uint8_t>().swap(c->upload_stage); // (the index build ended with a wait for the stream: the copy has been made)
-      (void)hb;
     }
     *out = c.release();
     return GTX_OK;

@@ -1,5 +1,6 @@
 // gtx_devmem.cpp -- see gtx_devmem.hpp
 #include "gtx_devmem.hpp"
+#include "gtx_switches.hpp"
 
 #include <cstdlib>
 #include <map>
@@ -60,9 +61,9 @@ hipError_t dev_malloc(void ** p, size_t bytes)
     std::lock_guard<std::mutex> lock(c.m);
     if (c.limit == 0)
     {
-      char const * env = std::getenv("GTX_DEVICE_CACHE_MB");
-      long long const mb = env ? std::atoll(env) : 32768; // (32 GB of 288: a context in flight holds 1.4 GB of workspaces per call scratch and 2 GB slabs) // (a negative value keeps nothing: it must not become a huge unsigned limit)
-      c.limit = static_cast<size_t>(mb < 0 ? 0 : mb) << 20;
+      // (default 32 GB of 288: a context in flight holds 1.4 GB of workspaces per call scratch and 2 GB slabs; a negative value keeps
+      //  nothing: it must not become a huge unsigned limit)
+      c.limit = sw::device_cache_mb() << 20;
       if (c.limit == 0)
         c.limit = 1; // (0 MB: nothing is kept)
     }
@@ -129,8 +130,7 @@ StreamPool & stream_pool()
 BuildStreamScope::BuildStreamScope()
 {
   before = tls_build_stream;
-  char const * off = std::getenv("GTX_BUILD_STREAM");
-  if ((off && off[0] == '0') || hipGetDevice(&device) != hipSuccess)
+  if (!sw::build_stream() || hipGetDevice(&device) != hipSuccess)
   {
     device = -1;
     return;

@@ -162,7 +162,7 @@ struct IndexView
   const uint2_t * pos_flags;
   const uint2_t * tail_info;
   const uint32_t * filt[2];
-  // hint_less (A/B switch GTX_HINT_MORE=0, hint_less_from_env): nonzero = the pass declines the shapes it learnt to prove last
+  // hint_less (A/B switch GTX_HINT_MORE=0, gtx_switches.hpp): nonzero = the pass declines the shapes it learnt to prove last
   //   (k-mers with several ambiguous bases, twin chains over another allele: hinted.hpp) as it did before
   uint32_t hint_first, n_hint, filt_log2 /* log2 of the number of words */, hint_less;
   // ---- allele windows (dense build of the pass).  A read that carries another allele than the reference's at a site does not
@@ -242,23 +242,12 @@ constexpr uint32_t HINT_HE_CAP = 16, HINT_NB_MAX = 16;
 // nowhere met four set bits in a word that two or three keys share (cfg2: a third of what the position-hinted pass sent on,
 // 7 k reads of 10 M), and one position in four failed HINT_NEAR_FREE for one of its 96 neighbours; with a key per four words it
 // is one probe in five thousand and one position in fifty.  32 MB for both filters of a 1 Mb region's million keys.
-// (GTX_FILTER_BITS_LOG2: A/B switch, 5 = the old size)
 inline uint32_t hint_filter_log2_words(uint64_t n_keys)
 {
   uint32_t fl = 5;
   while ((1ull << fl) < n_keys + 1 && fl < 28)
     ++fl;
-  uint32_t extra = 2;
-  if (char const * e = std::getenv("GTX_FILTER_BITS_LOG2"))
-    extra = static_cast<uint32_t>(std::max(5, std::min(9, std::atoi(e))) - 5);
-  return std::min<uint32_t>(fl + extra, 28u);
-}
-
-// IndexView::hint_less from the environment (GTX_HINT_MORE=0: A/B switch, read where the view is handed to the pass)
-inline uint32_t hint_less_from_env()
-{
-  char const * e = std::getenv("GTX_HINT_MORE");
-  return e && e[0] == '0' ? 1u : 0u;
+  return std::min<uint32_t>(fl + 2u, 28u); // (a word per key, rounded up, times four)
 }
 
 // the half at bit j (what a read in plane form yields with two shifts) -> (word, mask of up to four bits) of the blocked

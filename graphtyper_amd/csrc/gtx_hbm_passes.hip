@@ -113,11 +113,7 @@ namespace gtx
 // workgroup's part of a slab of HBM at run time.  Launched twice: EXACT_PARTS workgroups with a part each, then one workgroup
 // with the whole slab for what did not fit a part (its queue is the first launch's next_tasks).
 // (at most one workgroup of this pass per CU, usually none with work: no register diet -- all the registers a wavefront can name)
-#ifdef GTX_EXACT_PASS_WAVES // (A/B builds: registers for that many wavefronts per SIMD)
-#define GTX_EXACT_PASS_ATTR __attribute__((amdgpu_waves_per_eu(GTX_EXACT_PASS_WAVES, GTX_EXACT_PASS_WAVES)))
-#else
 #define GTX_EXACT_PASS_ATTR __attribute__((amdgpu_waves_per_eu(1, 2)))
-#endif
 #ifndef GTX_EXACT_LDS_KEYS
 #define GTX_EXACT_LDS_KEYS 4096
 #endif
@@ -368,14 +364,8 @@ static char const * exact_launches(HbmPassArgs const & a, Kernel kernel, bool li
   unsigned long long const slab_bytes = a.exact_slab_bytes, min_part = slab_bytes / a.exact_parts;
   // (the second launch: parts of at least 16 MB -- 32 of them in a 512 MB slab, 128 in the 2 GB slab of a large batch: on a reference
   //  with repeats two hundred tasks come this far, and 32 parts took them in six rounds of a millisecond each)
-  static uint32_t const large_parts_env = []
-  {
-    char const * e = std::getenv("GTX_EXACT_LARGE_PARTS"); // (A/B switch)
-    return e && std::atoi(e) > 0 ? static_cast<uint32_t>(std::min(std::atoi(e), 1024)) : 0u;
-  }();
   // (graphs with sites of more than 64 alleles keep 32: a walk's candidate table alone can be tens of megabytes there)
   uint32_t const large_parts = a.exact_fixed_parts ? 1u
-                               : large_parts_env ? large_parts_env
                                : a.wide_sites    ? CallScratch::EXACT_LARGE_PARTS
                                                  : static_cast<uint32_t>(std::min<unsigned long long>(256ull, std::max<unsigned long long>(CallScratch::EXACT_LARGE_PARTS, slab_bytes >> 24)));
   uint32_t const grid1 = a.exact_grid_limit ? std::min<uint32_t>(a.exact_parts, a.exact_grid_limit) : a.exact_parts;

@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "gtx_flat.hpp"
+#include "gtx_switches.hpp"
 #include "index_build.hpp"
 
 namespace gtx
@@ -461,8 +462,8 @@ struct Walker
 // ---- a team of host threads for the index build (GTX_HOST_THREADS overrides; the build is ~1 M keys per Mb of graph)
 static unsigned host_threads()
 {
-  if (char const * e = std::getenv("GTX_HOST_THREADS"))
-    return static_cast<unsigned>(std::max(1, std::atoi(e)));
+  if (unsigned const given = sw::host_threads())
+    return given;
   unsigned const hw = std::thread::hardware_concurrency();
   return std::max(1u, std::min(hw ? hw : 1u, 8u)); // (measured on a 256-thread host: 1 / 4 / 8 / 16 / 32 threads = 0.25 / 0.21 / 0.17 / 0.23 / 0.42 s:
                                                    //  the stages are short and memory-bound, a larger team costs more to start than it saves)
@@ -609,7 +610,7 @@ IndexView HostIndex::view(uint32_t max_index_labels, uint32_t half_bucket_cap) c
   ix.hint_first = hint_first;
   ix.n_hint = n_hint;
   ix.filt_log2 = filt_log2;
-  ix.hint_less = hint_less_from_env();
+  ix.hint_less = sw::hint_more() ? 0u : 1u;
   ix.win = win.data();
   ix.site_win = site_win.data();
   ix.win_base = win_base;
@@ -683,8 +684,7 @@ void hint_list_windows(HostGraph const & g, std::vector<HintWindow> & win, std::
 {
   win.clear();
   site_win.assign(g.ref_order.size(), 0u);
-  char const * e = std::getenv("GTX_HINT_WINDOWS");
-  uint64_t const cap = e ? static_cast<uint64_t>(std::max(0l, std::atol(e))) : 16384u;
+  uint64_t const cap = sw::hint_windows();
   GraphView const gv = g.view();
   uint32_t const R = static_cast<uint32_t>(g.ref_order.size());
   if (R == 0 || R - 1 >= HINT_NO_SITE)
@@ -811,8 +811,7 @@ static void build_hints(HostGraph const & g, HostIndex & out)
   });
   // the exact table's slots of the keys whose neighbours are known (gtx_flat.hpp: SLOT_NB_KNOWN; GTX_NB_KNOWN=0: a test
   // switch that leaves the bit clear everywhere, so that the kernels verify the neighbours themselves)
-  char const * nbk = std::getenv("GTX_NB_KNOWN");
-  if (!out.slots.empty() && !(nbk && nbk[0] == '0'))
+  if (!out.slots.empty() && sw::nb_known())
     parallel_slices(nk, host_threads(), [&](unsigned, std::size_t b, std::size_t e) {
       uint64_t const mask = (1ull << out.log2_cap) - 1;
       for (std::size_t k = b; k < e; ++k)
@@ -834,7 +833,7 @@ static void build_hints(HostGraph const & g, HostIndex & out)
             }
         }
     });
-  // filters over the halves of every indexed key (nibble form, as the kernel hashes them): 32 bits per key and side
+  // filters over the halves of every indexed key (nibble form, as the kernel hashes them): 128 bits per key and side
   uint32_t const fl = hint_filter_log2_words(nk);
   out.filt_log2 = fl;
   out.filt[0].assign(1ull << fl, 0);
@@ -904,7 +903,7 @@ void enumerate_kmers(HostGraph const & g, std::vector<Emit> & em, std::vector<Em
   for (uint32_t r = 0; r < R; ++r)
     total += weight(r);
   unsigned T = R < 64 ? 1u : host_threads();
-  if (T > 1 && !std::getenv("GTX_HOST_THREADS"))
+  if (T > 1 && !sw::host_threads())
   {
     if (runs && total < 400000)
       T = std::min(T, 4u);
@@ -1042,7 +1041,7 @@ void enumerate_kmers(HostGraph const & g, std::vector<Emit> & em, std::vector<Em
 
 void build_tables_host(HostGraph const & g, std::vector<Emit> const & em, HostIndex & out)
 {
-  bool const timing = std::getenv("GTX_TIMING") != nullptr; // stage times on stderr
+  bool const timing = sw::timing(); // stage times on stderr
   auto t_last = std::chrono::steady_clock::now();
   auto lap = [&](char const * what)
   {

@@ -22,6 +22,7 @@
 #include "gtx_ctx.hpp"
 #include "gtx_devmem.hpp"
 #include "gtx_devprim.hpp"
+#include "gtx_switches.hpp"
 #include "index_build.hpp"
 
 namespace gtx
@@ -496,9 +497,7 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
   uint32_t const E = n_listed + static_cast<uint32_t>(n_run_kmers);
   IndexView ix{};
   ix.max_index_labels = static_cast<uint32_t>(c.params.max_index_labels);
-  ix.half_bucket_cap = HALF_BUCKET_CAP;
-  if (char const * e = std::getenv("GTX_HALF_BUCKET_CAP")) // A/B switch for benchmarking: 0 = probe the 96 neighbours directly
-    ix.half_bucket_cap = static_cast<uint32_t>(std::min<long>(std::max<long>(std::atol(e), 0), HALF_BUCKET_CAP));
+  ix.half_bucket_cap = sw::half_bucket_cap(HALF_BUCKET_CAP); // (A/B switch for benchmarking: 0 = probe the 96 neighbours directly)
   // ---- emission list on the device (structure of arrays): the listed k-mers from the host, the runs' made here
   uint64_t *d_keys_in = pool.get<uint64_t>(E, "emitted keys"), *d_sorted = pool.get<uint64_t>(E, "sorted keys");
   gtx_label * d_labels_in = pool.get<gtx_label>(E, "emitted labels");
@@ -658,9 +657,9 @@ int build_index_device(gtx_ctx & c, std::vector<Emit> const & em, std::vector<Em
     HintKeys const t{d_keys, d_key_off, d_dev_labels, n_keys, d_lbegin, d_lsize, d_rorder, d_rbegin, d_rsize};
     if (n_keys)
     {
-      char const * nbk = std::getenv("GTX_NB_KNOWN"); // test switch: 0 = no slot gets SLOT_NB_KNOWN
+      // (test switch GTX_NB_KNOWN=0: no slot gets SLOT_NB_KNOWN)
       hipLaunchKernelGGL(k_judge_keys, dim3(blocks_for(n_keys)), dim3(TB), 0, gtx::tls_build_stream, t, d_nb, d_same, d_f0, d_f1, fl, d_pk,
-                         (nbk && nbk[0] == '0') ? static_cast<IndexSlot *>(nullptr) : d_slots, log2_cap);
+                         sw::nb_known() ? d_slots : static_cast<IndexSlot *>(nullptr), log2_cap);
     }
     // (the flags look at the filters k_judge_keys has just filled, in stream order: HINT_NEAR_FREE)
     HintKeys tf = t;

@@ -19,6 +19,7 @@
 // (gtx_host_loops.hpp) when the thread's run ends.
 #include "gtx_ctx.hpp"
 #include "gtx_host_loops.hpp"
+#include "gtx_switches.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -330,8 +331,7 @@ extern "C" int gtx_pipeline_run(gtx_ctx * c, const char * const * bam_paths, uin
   for (uint32_t f = 0; f < n_paths; ++f)
     team[f % n_threads].paths.push_back(bam_paths[f] ? bam_paths[f] : "");
   // GTX_BGZF_DEVICE=1: the readers' BGZF members are inflated by the context's device (gtx_reads_set_inflate_device)
-  char const * const env_dev = std::getenv("GTX_BGZF_DEVICE");
-  bool const bgzf_on_device = env_dev && env_dev[0] != '\0' && std::strcmp(env_dev, "0") != 0;
+  bool const bgzf_on_device = gtx::sw::bgzf_device();
   int const device = c->device;
   // the files are opened first (one thread each): the samples' numbers need every group's names
   {

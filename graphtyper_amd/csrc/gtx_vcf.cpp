@@ -10,6 +10,7 @@
 // The calls of an SV graph take another road (sv_graph_records below: reformat_sv_vcf_records and what genotype_sv's merge does).
 // Not built: variant break-down and the merge of pools (vcf_operations.cpp).
 #include "gtx_ctx.hpp"
+#include "gtx_switches.hpp"
 #include "gtx_vcf_text.hpp"
 
 #include <algorithm>
@@ -1260,8 +1261,8 @@ extern "C" int gtx_vcf_records(const gtx_ctx * c, const gtx_vcf_request * rq, ch
   if (static_cast<uint64_t>(nh) * (ns + 1) >= 200000) // (small jobs: a team costs more to start than it saves)
   {
     T = std::min(std::max(std::thread::hardware_concurrency(), 1u), 32u);
-    if (char const * e = std::getenv("GTX_HOST_THREADS"))
-      T = static_cast<unsigned>(std::max(1, std::atoi(e)));
+    if (unsigned const given = gtx::sw::host_threads())
+      T = given;
     T = std::min<unsigned>(T, std::max<uint32_t>(nh / 16, 1));
   }
   if (T <= 1)

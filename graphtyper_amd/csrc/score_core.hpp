@@ -759,20 +759,10 @@ GTX_DEV bool score_item(GraphView const & g, ScoreParams const & par, gtx_score_
     // update_unpaired_read_paths (alignment.cpp:365-455).  clipped_count() returns 0/1, so IS_CLIPPED is never set.
     gtx_rec_meta const & m = it.first;
     uint32_t const mflag = m.flag & 0x7FFFu; // (without GTX_FLAG_FORWARD_ONLY)
-#ifdef GTX_PROF_SCORE // (a one-off profiling build: cycles of the parts of a single read's item, lane 0 of a workgroup, in the express pass' slots)
-    unsigned long long const ps0 = W::clock();
-#define GTX_PS(slot, since) if ((threadIdx.x & 63u) == 0) atomicAdd(g.prof + (slot), W::clock() - (since))
-#else
-#define GTX_PS(slot, since)
-#endif
     Geno fwd = geno_of(records, rec_words, acc, m.align_index, 0);
     Geno rev = (m.flag & GTX_FLAG_FORWARD_ONLY) ? empty_orientation(fwd) : geno_of(records, rec_words, acc, m.align_index, 1);
     if (!fwd.has_var && !rev.has_var)
       return true; // whichever orientation wins, it touches no variant site: nothing to add
-    GTX_PS(16, ps0 + (fwd.n_paths & 0u));
-#ifdef GTX_PROF_SCORE
-    unsigned long long const ps1 = W::clock();
-#endif
     int const which = compare_single(fwd, rev);
     if (which == 0)
       return true;
@@ -786,25 +776,12 @@ GTX_DEV bool score_item(GraphView const & g, ScoreParams const & par, gtx_score_
       return true;
     bool fully, unique;
     bool const good = geno_is_good(g, par, ge, fully, unique);
-    GTX_PS(17, ps1 + (good ? 0u : 0u));
     if (good)
     {
-#ifdef GTX_PROF_SCORE
-      unsigned long long const ps2 = W::clock();
-#endif
       uint32_t const n = collect_recent(g, ge, r1, cap);
       if (n == 0xFFFFFFFFu)
         return false;
-      GTX_PS(18, ps2 + (n & 0u));
-#ifdef GTX_PROF_SCORE
-      unsigned long long const ps3 = W::clock();
-#endif
       apply_recent<W>(g, acc, ge, fully, unique, it.sample, r1, n);
-      GTX_PS(19, ps3);
-#ifdef GTX_PROF_SCORE
-      if ((threadIdx.x & 63u) == 0)
-        atomicAdd(g.prof + 31, 1ull);
-#endif
     }
     return true;
   }

@@ -38,17 +38,12 @@ struct WaveHip
   }
   // Orders the leader's LDS writes before the other lanes' reads.  All 64 lanes belong to one wavefront whose LDS
   // instructions are issued and serviced in program order, so no hardware wait is needed: the wavefront-scope fences
-  // only stop the compiler from moving or merging LDS accesses across this point (GTX_HARD_SYNC=1 at build time
-  // falls back to a real workgroup barrier for A/B checks).
+  // only stop the compiler from moving or merging LDS accesses across this point.
   static __device__ inline void lds_sync()
   {
-#ifdef GTX_HARD_SYNC
-    __syncthreads();
-#else
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
   }
   static __device__ inline uint64_t ballot(PerLane<bool> const & p) { return __ballot(p.v); }
   static __device__ inline uint32_t sum(PerLane<uint32_t> const & p)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../graphtyper_amd/csrc/gtx_flat.hpp"
+#include "../../graphtyper_amd/csrc/gtx_switches.hpp"
 #include "../../graphtyper_amd/csrc/align_core.hpp"
 #include "../../graphtyper_amd/csrc/score_core.hpp"
 #include "../../graphtyper_amd/csrc/score_replay.hpp"
@@ -186,16 +187,15 @@ extern "C"
                           seq_stride / PLANE_GROUP_BYTES);
     uint8_t const * seq = reinterpret_cast<uint8_t const *>(plane_rows.data());
     GraphView const g = e.graph.view();
-    IndexView ix = e.index.view(static_cast<uint32_t>(e.params.max_index_labels), HALF_BUCKET_CAP);
-    if (char const * cap = std::getenv("GTX_HALF_BUCKET_CAP"))
-      ix.half_bucket_cap = static_cast<uint32_t>(std::atol(cap));
+    IndexView ix = e.index.view(static_cast<uint32_t>(e.params.max_index_labels), sw::half_bucket_cap(HALF_BUCKET_CAP));
     auto ws = std::make_unique<AlignWorkspace>();
     auto big_ws = std::make_unique<big::AlignWorkspace>();
     std::vector<uint32_t> big_keys(2 * big::AlignCfg::MAXPP, 0xABABABABu), wide_keys(2 * wide::AlignCfg::MAXPP, 0xABABABABu);
     std::vector<uint64_t> big_bits(big::AlignCfg::MAXPP / 64 + 1, 0xABABABABABABABABull), wide_bits(wide::AlignCfg::MAXPP / 64 + 1, 0xABABABABABABABABull);
     bool const second_pass = !e.params.no_second_pass;
-    char const * fe = std::getenv("GTX_FORCE_SECOND_PASS"); // 1: every task through all passes, 2: every task done by pass 2
-    int const force = fe ? std::atoi(fe) : 0;
+    // the library's switches, as gtx_align_batch reads them (gtx_switches.hpp)
+    sw::AlignSwitches const env = sw::align_switches();
+    uint32_t const force = env.force; // 1: every task through all passes, 2: every task done by pass 2
     bool const force_big = force == 1;
     auto seed_ws = std::make_unique<SeedWorkspace>();
     e.general_tasks = 0;
@@ -205,13 +205,11 @@ extern "C"
       e.arena.assign(e.params.big_record_words ? e.params.big_record_words : (1u << 20), 0xABABABABu);
     e.second_pass_tasks = 0;
     bool const force_both = e.params.force_align_both_orientations != 0;
-    char const * e4 = std::getenv("GTX_EXPRESS4"); // 0: one read per wavefront in pass 1
-    bool const four = !(e4 && e4[0] == '0');
+    bool const four = env.four; // (GTX_EXPRESS4=0: one read per wavefront in pass 1)
     // lean / wide build of pass 1: forced by GTX_EXPRESS4=lean|wide, else by the graph's density (as gtx_align_batch does)
-    bool const wide = e4 && e4[0] == 'w' ? true : e4 && e4[0] == 'l' ? false : express4_prefers_wide(e.graph, e.index);
+    bool const wide = env.wide(express4_prefers_wide(e.graph, e.index));
     // ... and of pass 0 (GTX_HINT_BUILD=lean|dense; default: the dense build on the graphs that get the wide express pass)
-    char const * hb = std::getenv("GTX_HINT_BUILD");
-    bool const hint_dense = hb && hb[0] == 'd' ? true : hb && hb[0] == 'l' ? false : express4_prefers_wide(e.graph, e.index);
+    bool const hint_dense = env.hint_dense(express4_prefers_wide(e.graph, e.index));
     auto e4_ws = std::make_unique<Express4Workspace<Express4Lean>>();
     auto e4_wide_ws = std::make_unique<Express4Workspace<Express4Wide>>();
     bool has_wide_sites = false;
@@ -224,14 +222,15 @@ extern "C"
       widest_site = std::max(widest_site, n);
     // the exact pass' slab (gtx_api.hip: exact_slab_mb; here one slab, used by one task at a time)
     constexpr uint32_t EXACT_PART_SITES = 24, EXACT_PART_CANDIDATES = 8256, EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64; // (gtx_ctx.hpp: CallScratch)
-    char const * xm = std::getenv("GTX_EXACT_PASS_MB");
+    uint64_t const mb_env = sw::exact_pass_mb();
     std::vector<uint8_t> & exact_slab = e.exact_slab;
     if (exact_slab.empty())
-      exact_slab.resize(static_cast<size_t>(e.params.exact_pass_mb ? e.params.exact_pass_mb : xm && std::atol(xm) > 0 ? std::atol(xm) : (has_wide_sites ? 1024 : 512)) << 20);
+      exact_slab.resize(static_cast<size_t>(e.params.exact_pass_mb ? e.params.exact_pass_mb : mb_env ? mb_env : (has_wide_sites ? 1024 : 512)) << 20);
     uint64_t exact_parts = std::min<uint64_t>(256u, std::max<uint64_t>(1u, (exact_slab.size() >> 20) / (has_wide_sites ? 32u : 2u))); // (the smallest part: as on the device with a full queue)
-    if (char const * xp = std::getenv("GTX_EXACT_PARTS"))
-      if (std::atol(xp) > 0)
-        exact_parts = static_cast<uint64_t>(std::min<long>(std::atol(xp), 1024));
+    uint32_t const parts_env = sw::exact_parts(); // (the test switch GTX_EXACT_PARTS: that many parts, and no large parts either)
+    bool const fixed_parts = parts_env != 0;
+    if (fixed_parts)
+      exact_parts = parts_env;
     e.exact_pass_tasks[0] = e.exact_pass_tasks[1] = e.exact_pass_tasks[2] = e.exact_pass_tasks[3] = 0;
     // one task through an HBM-table pass (the body of GTX_HBM_PASS_KERNEL in gtx_api.hip); returns the pass' status
     auto hbm_pass = [&](auto &, auto && align, auto && size_of, auto && write_body, uint32_t * rec, uint32_t len) -> uint32_t
@@ -310,7 +309,6 @@ extern "C"
       }
       // the exact pass (gtx_align_exact_kernel): first with a part of the slab, then with all of it
       constexpr uint32_t TABLES = GTX_ST_LABEL_OVERFLOW | GTX_ST_PATH_OVERFLOW | GTX_ST_DFS_OVERFLOW;
-      bool const fixed_parts = std::getenv("GTX_EXACT_PARTS") != nullptr; // (the test switch: no large parts either)
       for (uint32_t level = 0; level < 3 && (last & TABLES); ++level)
       {
         ++e.exact_pass_tasks[level];
@@ -349,8 +347,7 @@ extern "C"
       rec[0] = len > AlignCfg::MAX_READ ? (static_cast<uint32_t>(GTX_ST_RECORD_OVERFLOW) << 16) : 0u;
       rec[1] = len << 16;
     };
-    char const * eh = std::getenv("GTX_HINT"); // 0: no position-hinted pass, d(ecline): the pass declines every task
-    if (four && !(eh && eh[0] == '0'))
+    if (env.hinted) // (GTX_HINT=0: no position-hinted pass, d(ecline): the pass declines every task)
     {
       // pass 0, one read per lane from the position hint (gtx_align_hinted_kernel), then pass 1 over its queue
       // (gtx_align_express4q_kernel), as gtx_align_batch launches them
@@ -374,7 +371,7 @@ extern "C"
           uint32_t const * row = reinterpret_cast<uint32_t const *>(seq + static_cast<uint64_t>(read) * seq_stride);
           uint32_t * slot = records + static_cast<uint64_t>(read) * 2 * rec_words;
           // (rows longer than 80 bytes: the eight-k-mer build, as gtx_align_batch chooses gtx_align_hinted_long_kernel)
-          uint32_t const where = (force != 0 || (eh && eh[0] == 'd')) ? 0u
+          uint32_t const where = env.decline_all ? 0u
                                  : seq_stride > HintGeom<AlignCfg::KC>::ROW_BYTES ? hinted_long_one<8>(g, ix, row, seq_stride, m, slot, rec_words)
                                  : hint_dense                                      ? hinted_one<true>(g, ix, row, seq_stride, m, slot, rec_words)
                                                                                    : hinted_one<false>(g, ix, row, seq_stride, m, slot, rec_words);
