@@ -22,8 +22,10 @@ struct BamHeader
 
 // BAM_NOT_BAM: no magic, or no text length behind it; BAM_TRUNCATED: the file ends inside the text or the reference list (or a
 // name's length is none: not positive, or beyond 1 MiB -- no contig is called that, and the field must not size an allocation)
+// Reader: a Bgzf, or anything with its read(dst, n) -> bytes read (gtx_discover_run.hip reads a header out of members it holds)
 enum BamHeaderRead { BAM_HEADER_OK, BAM_NOT_BAM, BAM_TRUNCATED };
-inline BamHeaderRead read_bam_header(Bgzf & fp, BamHeader & h)
+template <class Reader>
+inline BamHeaderRead read_bam_header(Reader & fp, BamHeader & h)
 {
   auto rd = [&](void * d, size_t n) { return fp.read(d, n) == static_cast<long>(n); };
   char magic[4];

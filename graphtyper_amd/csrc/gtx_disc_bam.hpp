@@ -22,6 +22,16 @@ int disc_bam_unpack_check(uint64_t n_bytes, uint32_t const * offsets, gtx_disc_r
                           uint32_t qual_stride, uint32_t n_cigar);
 int disc_bam_unpack_launch(uint8_t const * d_stream, uint32_t const * d_offsets, gtx_disc_read const * d_reads, uint32_t n_reads, uint8_t * d_planes,
                            uint32_t plane_stride, uint8_t * d_qual, uint32_t qual_stride, uint32_t * d_cigar, void * stream);
+
+// gtx_disc_bam_walk in its two halves (gtx_disc_bam_walk.hip), for a caller that sizes the tables from the count (gtx_discover_files_front):
+// guess and resolve, which leave *d_out and the segment table (n_cuts + 1 entries of BamWalkSeg, gtx_disc_bam_walk_dev.hpp); then emit
+// over the same cuts and segment table into tables of at least d_out->n_reads entries.  Launches on `stream`, nothing is waited for.
+// d_cuts: device, strictly ascending in (0, n_bytes); n_bytes > 0.
+struct BamWalkSeg;
+int disc_bam_walk_count(uint8_t const * d_stream, uint32_t n_bytes, uint32_t const * d_cuts, uint32_t n_cuts, BamWalkSeg * d_segs, gtx_bam_walk_out * d_out,
+                        void * stream);
+int disc_bam_walk_emit(uint8_t const * d_stream, uint32_t n_bytes, uint32_t const * d_cuts, uint32_t n_cuts, BamWalkSeg * d_segs, uint32_t * d_offsets,
+                       gtx_disc_read * d_reads, void * stream);
 } // namespace gtx
 
 struct gtx_disc_bam

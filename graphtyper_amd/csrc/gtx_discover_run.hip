@@ -1,8 +1,9 @@
 // gtx_discover_run.hip -- discovery's host loops inside the library, beside gtx_regions.cpp and gtx_pipeline.cpp: a file's second
 // pass as one call (gtx_disc_second_file: what parallel_second_pass, src/typer/caller.cpp:2633-2751, does for one file) and a
 // region's discovery to the sites file (streamlined_discovery, :2753-3093, then the writer) from host arrays (gtx_discover_region)
-// or from the BAM files themselves (gtx_discover_files: read on the host, gtx_disc_bam.cpp, unpacked on the device, gtx_disc_bam.hip);
-// the two share one body behind "the file's arrays are on the device".
+// or from the BAM files themselves (gtx_discover_files: read on the host, gtx_disc_bam.cpp, unpacked on the device, gtx_disc_bam.hip;
+// gtx_discover_files_front with front 1: inflated, walked and unpacked on the device, gtx_inflate_dev.hip, gtx_disc_bam_walk.hip);
+// the three share one body behind "the file's arrays are on the device".
 //
 // No kernel lives here: every stage is an entry point that exists, and this file is their caller -- the uploads, the growth
 // protocols (the events buffer of the first pass, the event array of the rounds), the downloads, the merge.  A file's arrays are
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <exception>
 #include <memory>
 #include <string>
@@ -19,11 +21,15 @@
 #include <vector>
 
 #include "../../include/gtx.h"
+#include "gtx_bam_record.hpp"
 #include "gtx_devmem.hpp"
 #include "gtx_disc.hpp"
 #include "gtx_disc_bam.hpp"
+#include "gtx_disc_bam_walk_dev.hpp"
+#include "gtx_switches.hpp"
 
-static_assert(sizeof(gtx_disc_variant) == 44 && sizeof(gtx_disc_file) == 48 && sizeof(gtx_discover_params) == 24 && sizeof(gtx_discover_file_stats) == 64,
+static_assert(sizeof(gtx_disc_variant) == 44 && sizeof(gtx_disc_file) == 48 && sizeof(gtx_discover_params) == 24 && sizeof(gtx_discover_file_stats) == 64 &&
+                  sizeof(gtx_discover_front_stats) == 24,
               "layouts of the binding");
 
 struct gtx_discover_result
@@ -35,6 +41,7 @@ struct gtx_discover_result
   std::vector<uint32_t> words;
   std::vector<uint8_t> good;
   std::vector<gtx_discover_file_stats> stats;
+  std::vector<gtx_discover_front_stats> front;
 };
 
 namespace
@@ -219,6 +226,7 @@ struct FileState // a file's arrays on the device and what its passes left
   std::vector<uint32_t> words; // of its first pass
   SecondResult second;
   gtx_discover_file_stats stats{};
+  gtx_discover_front_stats front{};
   int rc = GTX_OK;
   std::string error;
 };
@@ -227,6 +235,7 @@ struct Worker
 {
   Disc disc;
   Stream stream;
+  std::unique_ptr<gtx_inflate, Free<gtx_inflate_destroy>> inflater; // the device front's, made with its first file
 };
 
 // gtx_discover_region's way to "the file's arrays are on the device": the host arrays, uploaded
@@ -286,6 +295,176 @@ int load_bam(Worker & w, char const * path, FileState & st)
                                             st.qual_stride, st.cigar.get(), s))
     return rc;
   return waited(s) ? GTX_OK : GTX_ERR_HIP;
+}
+
+// ---- the device front ---------------------------------------------------------------------------------------------------------------
+// A file's bytes, whole.  false: it cannot be opened or read (gtx_disc_bam_read then says so in its own words).
+bool file_bytes(char const * path, std::vector<uint8_t> & out)
+{
+  std::unique_ptr<std::FILE, Free<std::fclose>> fp(std::fopen(path, "rb"));
+  if (!fp || std::fseek(fp.get(), 0, SEEK_END) != 0)
+    return false;
+  long const size = std::ftell(fp.get());
+  if (size < 0 || std::fseek(fp.get(), 0, SEEK_SET) != 0)
+    return false;
+  out.assign(static_cast<size_t>(size) + 8, 0); // (8 bytes behind the last member: the host decoder loads 8 at a time)
+  return size == 0 || std::fread(out.data(), 1, static_cast<size_t>(size), fp.get()) == static_cast<size_t>(size);
+}
+
+// read_bam_header's reader over members that lie in memory: they are inflated on the host one by one, as far as the header reaches
+struct MemberBytes
+{
+  uint8_t const * file;
+  std::vector<gtx_inflate_member> const & members;
+  size_t next = 0, at = 0;
+  std::vector<uint8_t> data;
+  long read(void * dst, size_t n)
+  {
+    while (data.size() - at < n && next < members.size())
+    {
+      gtx_inflate_member const & m = members[next++];
+      size_t const before = data.size();
+      data.resize(before + m.out_len);
+      if (!inflate_bgzf_member(file + m.in_off, m.in_len, data.data() + before, m.out_len, !sw::inflate_zlib(), sw::bgzf_crc()))
+        return -1;
+    }
+    size_t const got = std::min(n, data.size() - at);
+    if (got)
+      std::memcpy(dst, data.data() + at, got);
+    at += got;
+    return static_cast<long>(got);
+  }
+};
+
+// The device front's way to "the file's arrays are on the device" (gtx.h: gtx_discover_files_front): the inflated bytes never leave
+// the device.  GTX_OK with *sound = false: the file is not sound in some way and nothing of it is in `st` -- the caller sends it
+// through load_bam, whose status and message are then the file's (the readers' device team's rule: what the device does not take
+// the host does, so a damaged file fails exactly as it does there).
+int load_bam_device(Worker & w, char const * path, FileState & st, bool * sound)
+{
+  *sound = false;
+  hipStream_t const s = w.stream.get();
+  if (int const rc = device_ready(w.disc->device, "gtx_discover_files_front", ": the object"))
+    return rc;
+  // the file, its members' headers, the BAM header
+  std::vector<uint8_t> file;
+  if (!file_bytes(path, file))
+    return GTX_OK;
+  uint64_t const file_len = file.size() - 8;
+  std::vector<gtx_inflate_member> members;
+  uint64_t total = 0;
+  for (uint64_t at = 0; at < file_len;)
+  {
+    BgzfMember head;
+    if (parse_bgzf_member(file.data() + at, file_len - at, head) != nullptr || !head.whole)
+      return GTX_OK;
+    if (head.isize) // (a member without data -- the end-of-file marker -- gets no descriptor and no cut)
+      members.push_back(gtx_inflate_member{at + head.hlen, total, static_cast<uint32_t>(head.clen), head.isize, head.crc32, 0});
+    total += head.isize;
+    at += head.bsize + 1ull;
+  }
+  if (total >= (1ull << 32) || members.size() >= (1ull << 32))
+    return GTX_OK;
+  MemberBytes head_bytes{file.data(), members};
+  BamHeader head;
+  BamSamples table;
+  if (read_bam_header(head_bytes, head) != BAM_HEADER_OK || !read_bam_samples(head.text, path, table) || table.samples.size() != 1) // (caller.cpp:2537-2544)
+    return GTX_OK;
+  uint64_t const header_len = head_bytes.at, n_bytes = total - header_len;
+  st.front.members = static_cast<uint32_t>(members.size());
+  if (n_bytes == 0) // a file without records
+  {
+    st.plane_stride = 16;
+    st.qual_stride = 4;
+    st.n_reads = st.n_cigar = 0;
+    WaitBehind const behind(s);
+    if (!made(st.planes, 0, s, "plane rows") || !made(st.qual, 0, s, "qualities", 2 * static_cast<size_t>(st.plane_stride)) || !made(st.reads, 0, s, "reads") ||
+        !made(st.cigar, 0, s, "cigar words"))
+      return GTX_ERR_HIP;
+    st.front.members_device = 0; // (the header's members were the host's)
+    *sound = true;
+    return GTX_OK;
+  }
+  std::vector<uint32_t> cuts; // the member ends behind the header
+  for (gtx_inflate_member const & m : members)
+    if (m.out_off + m.out_len > header_len && m.out_off + m.out_len < total)
+      cuts.push_back(static_cast<uint32_t>(m.out_off + m.out_len - header_len));
+  if (!w.inflater)
+  {
+    gtx_inflate * h = nullptr;
+    if (int const rc = gtx_inflate_create(w.disc->device, &h))
+      return rc;
+    w.inflater.reset(h);
+  }
+  // one upload, the inflate, the walk's count, one small download
+  uint32_t const n_members = static_cast<uint32_t>(members.size()), n_cuts = static_cast<uint32_t>(cuts.size());
+  DevPtr<uint8_t> d_file, d_out;
+  DevPtr<gtx_inflate_member> d_members;
+  DevPtr<uint32_t> d_status, d_cuts, d_offsets;
+  DevPtr<BamWalkSeg> d_segs;
+  DevPtr<gtx_bam_walk_out> d_walk;
+  WaitBehind const behind(s);
+  if (!made(d_file, file.size(), s, "file bytes") || !copied_up(d_file.get(), file.data(), file.size(), s, "file bytes") ||
+      !made(d_members, n_members, s, "members") || !copied_up(d_members.get(), members.data(), n_members, s, "members") ||
+      !made(d_cuts, n_cuts, s, "cuts") || !copied_up(d_cuts.get(), cuts.data(), n_cuts, s, "cuts") || !made(d_out, total, s, "inflated bytes") ||
+      !made(d_status, n_members, s, "member statuses") || !made(d_segs, static_cast<size_t>(n_cuts) + 1, s, "segment table") || !made(d_walk, 1, s, "walk counts"))
+    return GTX_ERR_HIP;
+  if (int const rc = gtx_inflate_batch(w.inflater.get(), d_file.get(), file_len, d_members.get(), n_members, d_out.get(), total, d_status.get(), sw::bgzf_crc() ? 1 : 0, s))
+    return rc;
+  uint8_t const * const d_stream = d_out.get() + header_len;
+  if (int const rc = disc_bam_walk_count(d_stream, static_cast<uint32_t>(n_bytes), d_cuts.get(), n_cuts, d_segs.get(), d_walk.get(), s))
+    return rc;
+  gtx_bam_walk_out walk{};
+  std::vector<uint32_t> status(n_members);
+  if (!downloaded(&walk, d_walk.get(), 1, s, "walk counts") || !downloaded(status.data(), d_status.get(), n_members, s, "member statuses") || !waited(s))
+    return GTX_ERR_HIP;
+  file = std::vector<uint8_t>(); // (the upload is done: the host block goes)
+  if (std::any_of(status.begin(), status.end(), [](uint32_t m) { return m != GTX_INFLATE_OK; }) || walk.status != GTX_BAM_WALK_OK || walk.n_cigar >= (1ull << 32))
+    return GTX_OK;
+  // the tables from the count, the arrays with load_bam's strides, the unpack kernel
+  st.plane_stride = std::max<uint32_t>((walk.max_l_seq + 31u) / 32u * 16u, 16u);
+  st.qual_stride = std::max<uint32_t>((walk.max_l_seq + 3u) & ~3u, 4u);
+  st.n_reads = walk.n_reads;
+  st.n_cigar = static_cast<uint32_t>(walk.n_cigar);
+  if (!made(d_offsets, st.n_reads, s, "record offsets") || !made(st.reads, st.n_reads, s, "reads") ||
+      !made(st.planes, static_cast<size_t>(st.n_reads) * st.plane_stride, s, "plane rows") ||
+      !made(st.qual, static_cast<size_t>(st.n_reads) * st.qual_stride, s, "qualities", 2 * static_cast<size_t>(st.plane_stride)) ||
+      !made(st.cigar, st.n_cigar, s, "cigar words"))
+    return GTX_ERR_HIP;
+  if (st.n_reads)
+    if (int const rc = disc_bam_walk_emit(d_stream, static_cast<uint32_t>(n_bytes), d_cuts.get(), n_cuts, d_segs.get(), d_offsets.get(), st.reads.get(), s))
+      return rc;
+  // disc_bam_unpack_check wants the two tables on the host; they are not there, and a walk that ended BAM_WALK_OK has held every one of
+  // its conditions (gtx_disc_bam_walk_dev.hpp; tests/test_gpu_disc_bam_walk.py and tests/test_gpu_discover_front.py hold each):
+  //   the strides            are made above from max_l_seq, the longest l_seq of the records the walk took: l_qseq <= qual_stride and
+  //                          l_qseq <= 2 * plane_stride for every one of them, and plane_stride is a multiple of 16;
+  //   cigar_off + n_cigar    cigar_off is the exclusive sum of n_cigar over the records in chain order and n_cigar their total (below
+  //                          2^32, looked at above): every record's words lie inside the array by construction;
+  //   the record             offsets[i] = o + 4 with 32 <= block <= n_bytes - o - 4 (the chain's test) and the counts within the block:
+  //                          offsets[i] + 32 + l_read_name + 4 n_cigar + (l_seq + 1) / 2 + l_seq <= o + 4 + block <= n_bytes;
+  //   the name's byte        is the stream's own, and it is the l_read_name of that same sum: the kernel, which takes it from the
+  //                          stream, stays inside the block -- no 254 bytes of doubt as with a stream of another origin.
+  if (int const rc = disc_bam_unpack_launch(d_stream, d_offsets.get(), st.reads.get(), st.n_reads, st.planes.get(), st.plane_stride, st.qual.get(), st.qual_stride,
+                                            st.cigar.get(), s))
+    return rc;
+  if (!waited(s))
+    return GTX_ERR_HIP;
+  st.front.members_device = n_members;
+  st.front.segments_hit = walk.segments_hit;
+  st.front.segments_rewalked = walk.segments_rewalked;
+  *sound = true;
+  return GTX_OK;
+}
+
+int load_bam_front(Worker & w, char const * path, FileState & st)
+{
+  bool sound = false;
+  if (int const rc = load_bam_device(w, path, st, &sound))
+    return rc;
+  if (sound)
+    return GTX_OK;
+  st.front = gtx_discover_front_stats{st.front.members, 0, 0, 0, 1, 0};
+  return load_bam(w, path, st);
 }
 
 // a file's first pass over its arrays on the device
@@ -467,6 +646,7 @@ int discover(char const * who, char const * reference, uint64_t reference_len, i
     st.stats.n_list = static_cast<uint32_t>(st.second.list.size());
     st.stats.rounds = st.second.stats;
     res.stats.push_back(st.stats);
+    res.front.push_back(st.front);
   }
   res.good.resize(nt);
   for (uint32_t t = 0; t < nt; ++t)
@@ -623,6 +803,50 @@ extern "C" int gtx_discover_files(const char * reference, uint64_t reference_len
     g_last_error = std::string("gtx_discover_files: ") + e.what();
     return GTX_ERR_CAPACITY;
   }
+}
+
+extern "C" int gtx_discover_files_front(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const char * const * bam_paths,
+                                        uint32_t n_files, const gtx_discover_params * params, uint32_t front, gtx_discover_result ** out)
+{
+  if (front == 0)
+    return gtx_discover_files(reference, reference_len, region_begin, contig, bam_paths, n_files, params, out);
+  if (!out)
+    return bad("gtx_discover_files_front");
+  *out = nullptr;
+  if (front != 1)
+    return bad("gtx_discover_files_front", "no such front");
+  if (!reference || reference_len == 0 || !contig || !bam_paths || n_files == 0 || !params || params->bucket_size == 0 || params->n_threads == 0 ||
+      params->n_threads > 8)
+    return bad("gtx_discover_files_front");
+  for (uint32_t i = 0; i < n_files; ++i)
+    if (!bam_paths[i])
+      return bad("gtx_discover_files_front", "a path");
+  if (params->device < 0) // (before any file is opened)
+  {
+    g_last_error = "gtx_discover_files_front: no device (libgtx has no CPU path)";
+    return GTX_ERR_NO_DEVICE;
+  }
+  try
+  {
+    auto res = std::make_unique<gtx_discover_result>();
+    int const rc = discover("gtx_discover_files_front", reference, reference_len, region_begin, contig, n_files, *params, *res,
+                            [&](Worker & w, size_t i, FileState & st) { return load_bam_front(w, bam_paths[i], st); });
+    if (rc == GTX_OK)
+      *out = res.release();
+    return rc;
+  }
+  catch (std::exception const & e)
+  {
+    g_last_error = std::string("gtx_discover_files_front: ") + e.what();
+    return GTX_ERR_CAPACITY;
+  }
+}
+
+extern "C" const gtx_discover_front_stats * gtx_discover_front(const gtx_discover_result * r, uint32_t * n_files)
+{
+  if (n_files)
+    *n_files = r ? static_cast<uint32_t>(r->front.size()) : 0;
+  return r ? r->front.data() : nullptr;
 }
 
 extern "C" void gtx_discover_destroy(gtx_discover_result * r) { delete r; }

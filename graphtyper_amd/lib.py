@@ -40,6 +40,7 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_disc_variants", "gtx_disc_vcf_sites", "gtx_disc_second_file", "gtx_discover_params_default", "gtx_discover_region", "gtx_discover_destroy",
            "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats",
            "gtx_disc_bam_read", "gtx_disc_bam_destroy", "gtx_disc_bam_stream", "gtx_disc_bam_reads", "gtx_disc_bam_info", "gtx_disc_bam_unpack", "gtx_discover_files",
+           "gtx_disc_bam_walk", "gtx_discover_files_front", "gtx_discover_front",
            "gtx_wave_probe"]
 
 
@@ -172,6 +173,19 @@ class DiscoverParams(C.Structure):
 
 class DiscoverFileStats(C.Structure):
     _fields_ = [("events", C.c_uint64), ("events_passes", C.c_uint32), ("n_list", C.c_uint32), ("rounds", DiscRoundsStats)]
+
+
+class DiscoverFrontStats(C.Structure):
+    _fields_ = [("members", C.c_uint32), ("members_device", C.c_uint32), ("segments_hit", C.c_uint32), ("segments_rewalked", C.c_uint32), ("fell_back", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class BamWalkOut(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("max_l_seq", C.c_uint32), ("bad_at", C.c_uint64), ("n_cigar", C.c_uint64), ("n_reads", C.c_uint32), ("segments_hit", C.c_uint32),
+                ("segments_rewalked", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BAM_WALK_OK, BAM_WALK_TRUNCATED, BAM_WALK_MALFORMED, BAM_WALK_LONG_READ = 0, 1, 2, 3
 
 
 def build(force=False):
@@ -325,6 +339,13 @@ def lib():
                                               C.c_void_p, C.c_uint32, C.c_void_p]
             L.gtx_discover_files.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(DiscoverParams),
                                              C.POINTER(C.c_void_p)]
+        if hasattr(L, "gtx_discover_files_front"):  # (GTX_LIB= a build of an earlier commit has no device front)
+            L.gtx_disc_bam_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(BamWalkOut),
+                                            C.c_void_p]
+            L.gtx_discover_files_front.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(DiscoverParams),
+                                                   C.c_uint32, C.POINTER(C.c_void_p)]
+            L.gtx_discover_front.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.gtx_discover_front.restype = C.POINTER(DiscoverFrontStats)
         L.gtx_wave_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         L.gtx_vcf_header.argtypes = [C.POINTER(VcfHeaderRequest), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.gtx_bgzf_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -820,8 +841,9 @@ def _discover_params(device, bucket_size, max_read_len, n_threads, first_event_c
     return params
 
 
-def _discover_result(h):
-    """what a gtx_discover_result holds, as discover_region documents it; the handle is destroyed"""
+def _discover_result(h, front=False):
+    """what a gtx_discover_result holds, as discover_region documents it (front: and, as "front", what gtx_discover_front says of each
+    file); the handle is destroyed"""
     L = lib()
     try:
         def view(ptr, dtype, count):
@@ -839,20 +861,33 @@ def _discover_result(h):
         st = L.gtx_discover_stats(h, C.byref(n32))
         out["stats"] = [dict(events=int(st[i].events), events_passes=int(st[i].events_passes), n_list=int(st[i].n_list), rounds=st[i].rounds.as_dict())
                         for i in range(n32.value)]
+        if front:
+            fr = L.gtx_discover_front(h, C.byref(n32))
+            out["front"] = [{name: int(getattr(fr[i], name)) for name, _ in DiscoverFrontStats._fields_ if name != "reserved"} for i in range(n32.value)]
         return out
     finally:
         L.gtx_discover_destroy(h)
 
 
-def discover_files(reference, region_begin, contig, paths, device=0, bucket_size=50, max_read_len=0, n_threads=1, first_event_cap=0, second_event_cap=0):
-    """gtx_discover_files: discover_region from BAM paths (one sample each, read whole and in file order) -> what discover_region returns"""
+FRONTS = {"host": 0, "device": 1}
+
+
+def discover_files(reference, region_begin, contig, paths, device=0, bucket_size=50, max_read_len=0, n_threads=1, first_event_cap=0, second_event_cap=0, front=None):
+    """gtx_discover_files: discover_region from BAM paths (one sample each, read whole and in file order) -> what discover_region returns.
+    front: None is gtx_discover_files; "host" (the same front end) and "device" (the files inflated, walked and unpacked on the device)
+    go through gtx_discover_files_front and add "front": per file dict(members, members_device, segments_hit, segments_rewalked,
+    fell_back)"""
     L = lib()
     refb = reference.encode("latin-1") if isinstance(reference, str) else bytes(reference)
     arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
     params = _discover_params(device, bucket_size, max_read_len, n_threads, first_event_cap, second_event_cap)
     h = C.c_void_p()
-    check(L.gtx_discover_files(refb, len(refb), region_begin, contig.encode(), arr, len(paths), C.byref(params), C.byref(h)))
-    return _discover_result(h)
+    if front is None:
+        check(L.gtx_discover_files(refb, len(refb), region_begin, contig.encode(), arr, len(paths), C.byref(params), C.byref(h)))
+        return _discover_result(h)
+    check(L.gtx_discover_files_front(refb, len(refb), region_begin, contig.encode(), arr, len(paths), C.byref(params), FRONTS[front] if front in FRONTS else int(front),
+                                     C.byref(h)))
+    return _discover_result(h, front=True)
 
 
 def disc_bam_read(path):
@@ -881,6 +916,19 @@ def disc_bam_unpack(handle, d_stream, n_bytes, d_offsets, d_reads, n_reads, d_pl
     """gtx_disc_bam_unpack over device arrays of the caller's (pointers as integers): the stream, offsets and reads of disc_bam_read,
     uploaded -> the plane rows, quality rows and CIGAR words written; raises GtxError on any status but GTX_OK"""
     check(lib().gtx_disc_bam_unpack(handle, d_stream, n_bytes, d_offsets, d_reads, n_reads, d_planes, plane_stride, d_qual, qual_stride, d_cigar, n_cigar, stream))
+
+
+def disc_bam_walk(handle, d_stream, n_bytes, cuts, d_offsets=None, d_reads=None, cap=0, stream=None):
+    """gtx_disc_bam_walk over a record stream in device memory of the caller's (pointers as integers); cuts: strictly ascending offsets
+    in (0, n_bytes), a host list.  d_offsets / d_reads: device tables of `cap` entries, or None and cap 0 for the counts alone.
+    -> (status of the call, dict(status, bad_at, n_reads, n_cigar, max_l_seq, segments_hit, segments_rewalked)); the call's status is
+    GTX_OK or GTX_ERR_CAPACITY (n_reads > cap: the dict is filled, no table entry written), any other raises GtxError"""
+    cuts = np.ascontiguousarray(cuts, np.uint32)
+    out = BamWalkOut()
+    rc = lib().gtx_disc_bam_walk(handle, d_stream, n_bytes, cuts.ctypes.data if len(cuts) else None, len(cuts), d_offsets, d_reads, cap, C.byref(out), stream)
+    if rc not in (0, 5):
+        check(rc)
+    return rc, {name: int(getattr(out, name)) for name, _ in BamWalkOut._fields_ if name != "reserved"}
 
 
 def disc_realign_target(handle, max_read_size, events):

@@ -1599,6 +1599,72 @@ int gtx_disc_bam_unpack(gtx_disc *, const uint8_t * d_stream, uint64_t n_bytes, 
 int gtx_discover_files(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const char * const * bam_paths,
                        uint32_t n_files, const gtx_discover_params * params, gtx_discover_result ** out);
 
+/* ---- discovery from BAM files, the device front (opt-in; gtx_discover_files is as it was): the file's BGZF members are inflated
+ * by the device (gtx_inflate_batch), the records are found and checked there (gtx_disc_bam_walk), and gtx_disc_bam_unpack's kernel
+ * runs over them -- the inflated bytes never come back to the host.
+ *   gtx_disc_bam_walk      device: the host walk of gtx_disc_bam_read over a record stream in device memory (kernel text and the
+ *                          definition: graphtyper_amd/csrc/gtx_disc_bam_walk_dev.hpp).  d_stream[0, n_bytes): records as they lie in
+ *                          a file, each behind its block_size word.  cuts (HOST, n_cuts strictly ascending offsets in (0, n_bytes))
+ *                          divide it into n_cuts + 1 segments that are walked side by side from the guess "a record begins at the
+ *                          segment's start" and put in order by one wavefront; in the library a segment is what one BGZF member
+ *                          inflated to, for the call a cut is any offset.  THE RESULT DOES NOT DEPEND ON THE CUTS: they decide
+ *                          segments_hit (segments whose guess held) and segments_rewalked (segments walked again from their true
+ *                          entry; a segment a record spans is neither) and nothing else.  out (HOST): status -- GTX_BAM_WALK_OK,
+ *                          _TRUNCATED (fewer than 4 bytes left, a block below 32 as a signed word, a block that ends behind
+ *                          n_bytes), _MALFORMED (l_seq < 0, or 32 + l_read_name + 4 n_cigar + (l_seq + 1) / 2 + l_seq beyond the
+ *                          block), _LONG_READ (l_seq > 65 535) -- of the first bad record in chain order, bad_at its block_size
+ *                          word's offset; n_reads, n_cigar, max_l_seq: of the sound records in front of it (all of them with
+ *                          GTX_BAM_WALK_OK).  d_offsets[i] = the offset of record i's 32 fixed bytes, d_reads[i] = its gtx_disc_read
+ *                          as gtx_disc_bam_read makes it, i < n_reads; nothing else is written.  d_offsets == d_reads == NULL with
+ *                          cap == 0 asks for `out` alone.  n_reads > cap: GTX_ERR_CAPACITY, out is filled and no table entry is
+ *                          written.  A walk status other than OK is no error of the call (GTX_OK).  Cuts that do not ascend, a cut
+ *                          outside (0, n_bytes), n_bytes >= 2^32, one table NULL and not the other, tables not 4-byte aligned, NULL
+ *                          out or stream bytes: GTX_ERR_ARG.  n_bytes == 0: GTX_OK, no records, nothing launched.  A gtx_disc made
+ *                          with device -1: GTX_ERR_NO_DEVICE.  Every load lies inside d_stream[0, n_bytes) whatever the bytes hold.
+ *                          The call waits for `stream`.
+ *   gtx_discover_files_front   gtx_discover_files with its front end chosen: front 0 is gtx_discover_files itself; front 1 is the
+ *                          device front -- per file, on its worker: the file's bytes read and its members' headers parsed on the
+ *                          host, the BAM header read as today (only the members it needs are inflated on the host), one upload of
+ *                          the compressed bytes and the member descriptors, gtx_inflate_batch over all members (the CRC-32 compared
+ *                          unless GTX_BGZF_CRC=0), gtx_disc_bam_walk behind the header with the member ends as cuts, one download
+ *                          of `out` and the member statuses, the arrays with gtx_discover_files' strides, the unpack kernel; then
+ *                          what gtx_discover_region does.  A file with anything unsound -- members that do not parse, a member
+ *                          status other than GTX_INFLATE_OK, a walk status other than OK, 2^32 inflated bytes or CIGAR words or more
+ *                          -- goes through gtx_disc_bam_read as with front 0: that call's status and message are the call's, and
+ *                          when it succeeds its tables are used (fell_back 1).  Any other front: GTX_ERR_ARG.
+ *   gtx_discover_front     per file of a result what its front end did (zeros for front 0 and gtx_discover_region): members (BGZF
+ *                          members with data), members_device (those the device inflated and the walk took), segments_hit,
+ *                          segments_rewalked, fell_back. */
+enum
+{
+  GTX_BAM_WALK_OK = 0,
+  GTX_BAM_WALK_TRUNCATED = 1,
+  GTX_BAM_WALK_MALFORMED = 2,
+  GTX_BAM_WALK_LONG_READ = 3
+};
+typedef struct gtx_bam_walk_out
+{
+  uint32_t status;
+  uint32_t max_l_seq;
+  uint64_t bad_at;
+  uint64_t n_cigar;
+  uint32_t n_reads;
+  uint32_t segments_hit, segments_rewalked;
+  uint32_t reserved;
+} gtx_bam_walk_out;
+typedef struct gtx_discover_front_stats
+{
+  uint32_t members, members_device;
+  uint32_t segments_hit, segments_rewalked;
+  uint32_t fell_back;
+  uint32_t reserved;
+} gtx_discover_front_stats;
+int gtx_disc_bam_walk(gtx_disc *, const uint8_t * d_stream, uint64_t n_bytes, const uint32_t * cuts, uint32_t n_cuts, uint32_t * d_offsets, gtx_disc_read * d_reads,
+                      uint32_t cap, gtx_bam_walk_out * out, void * stream);
+int gtx_discover_files_front(const char * reference, uint64_t reference_len, int64_t region_begin, const char * contig, const char * const * bam_paths,
+                             uint32_t n_files, const gtx_discover_params * params, uint32_t front, gtx_discover_result ** out);
+const gtx_discover_front_stats * gtx_discover_front(const gtx_discover_result *, uint32_t * n_files);
+
 /* Inspection of the wavefront primitives every kernel is written against (csrc/graph_dev.hpp: the wave policy's table): runs
  * csrc/wave_probe.hpp on `device`, one wavefront per input set.  in: n_sets x 200 words, out: n_sets x 340 words, both HOST
  * arrays (the layout: the WP_* constants of wave_probe.hpp; tests/wave_probe_cases.py states what must come out).  n_sets = 0:
