@@ -41,7 +41,8 @@ EXPORTS = ["gtx_strerror", "gtx_last_error", "gtx_ctx_create", "gtx_ctx_destroy"
            "gtx_discover_text", "gtx_discover_variants", "gtx_discover_words", "gtx_discover_good", "gtx_discover_stats",
            "gtx_disc_bam_read", "gtx_disc_bam_destroy", "gtx_disc_bam_stream", "gtx_disc_bam_reads", "gtx_disc_bam_info", "gtx_disc_bam_unpack", "gtx_discover_files",
            "gtx_disc_bam_walk", "gtx_discover_files_front", "gtx_discover_front",
-           "gtx_wave_probe"]
+           "gtx_wave_probe",
+           "gtx_dstream_create", "gtx_dstream_destroy", "gtx_dstream_push", "gtx_dstream_finish", "gtx_dstream_counts"]
 
 
 class GraphView(C.Structure):
@@ -409,6 +410,13 @@ def lib():
         L.gtx_stream_set_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.gtx_stream_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.gtx_stream_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.gtx_dstream_create.argtypes = [C.POINTER(Params), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.gtx_dstream_destroy.argtypes = [C.c_void_p]
+        L.gtx_dstream_destroy.restype = None
+        L.gtx_dstream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
+        L.gtx_dstream_finish.argtypes = [C.c_void_p, C.c_void_p]
+        L.gtx_dstream_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.gtx_graph_build.argtypes = [C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]
         L.gtx_graph_from_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p),
@@ -1548,6 +1556,50 @@ class Stream:
     def counts(self):
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(lib().gtx_stream_counts(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(records=int(a.value), duplicated=int(b.value), parked=int(c.value))
+
+
+class DeviceStream:
+    """gtx_dstream: gtx_stream's decisions for records that are in device memory, the outputs left there (no SV graphs)"""
+
+    def __init__(self, params, n_read_groups=1, device=0, max_batch=1 << 16, parked_cap=1 << 16):
+        h = C.c_void_p()
+        check(lib().gtx_dstream_create(C.byref(params), n_read_groups, device, max_batch, parked_cap, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().gtx_dstream_destroy(self.h)
+            self.h = None
+
+    def push_raw(self, d_recs, d_seq, seq_stride, n, d_planes, plane_stride, d_meta, align_cap, d_items, item_cap, stream=None):
+        """device pointers in and out -> (status, n_align, n_items); nothing is raised"""
+        na, ni = C.c_uint32(), C.c_uint32()
+        rc = lib().gtx_dstream_push(self.h, d_recs, d_seq, seq_stride, n, d_planes, plane_stride, d_meta, align_cap, d_items, item_cap, C.byref(na), C.byref(ni), stream)
+        return rc, int(na.value), int(ni.value)
+
+    def push(self, recs, seq, plane_stride, stream=None):
+        """recs: a uint8 torch tensor on the device holding n STREAM_RECORD, seq: a uint8 tensor [n, seq_stride] of packed bases there ->
+        (planes [n_align, plane_stride], meta [n_align * 20 bytes], items [n_items * 40 bytes]) as uint8 tensors on the device"""
+        import torch
+        n, seq_stride = seq.shape
+        assert recs.numel() == n * STREAM_RECORD.itemsize and recs.is_contiguous() and seq.is_contiguous()
+        planes = torch.empty((max(n, 1), plane_stride), dtype=torch.uint8, device=seq.device)
+        meta = torch.empty(max(n, 1) * READ_META.itemsize, dtype=torch.uint8, device=seq.device)
+        items = torch.empty(max(n, 1) * SCORE_ITEM.itemsize, dtype=torch.uint8, device=seq.device)
+        if stream is None:
+            torch.cuda.current_stream().synchronize()  # (the tensors above and the caller's are made on torch's stream; the push runs on the null stream)
+        rc, na, ni = self.push_raw(recs.data_ptr(), seq.data_ptr(), seq_stride, n, planes.data_ptr(), plane_stride, meta.data_ptr(), n, items.data_ptr(), n, stream)
+        check(rc)
+        return planes[:na], meta[:na * READ_META.itemsize], items[:ni * SCORE_ITEM.itemsize]
+
+    def finish(self, stream=None):
+        """end of the stream: the parked mates are forgotten"""
+        check(lib().gtx_dstream_finish(self.h, stream))
+
+    def counts(self):
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().gtx_dstream_counts(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return dict(records=int(a.value), duplicated=int(b.value), parked=int(c.value))
 
 

@@ -1671,6 +1671,41 @@ const gtx_discover_front_stats * gtx_discover_front(const gtx_discover_result *,
  * GTX_OK, nothing is written.  device < 0: GTX_ERR_NO_DEVICE. */
 int gtx_wave_probe(int device, const uint32_t * in, uint32_t n_sets, uint32_t * out);
 
+/* ---- the record stream's decisions on the device: gtx_stream for small-variant calling over records that are in device memory,
+ * its outputs left there.  The same records in the same split into pushes give the bytes gtx_stream_push gives after
+ * gtx_stream_set_planes(plane_stride): the plane rows and gtx_read_meta of the alignment tasks, the score items, the counts.  What a
+ * push leaves is stated without the host's loop-carried map in csrc/gtx_dstream_dev.hpp (and in plain Python in tests/dstream_cases.py).
+ *   gtx_dstream_create     on `device` (device < 0 or no such HIP device: GTX_ERR_NO_DEVICE -- no CPU path).  max_batch: the most
+ *                          records one push may hold; parked_cap: the most mates that may wait for theirs at the end of a push.  All
+ *                          device memory of the stream is made here, sized from these two and max_read_len: a push allocates nothing.
+ *                          params->is_sv_graph != 0: GTX_ERR_UNSUPPORTED (the SV record filter's coverage bins depend on the order of
+ *                          the records, and the host's leftover items follow the order of its hash map).  max_read_len as for
+ *                          gtx_stream_create; n_read_groups or max_batch 0, max_batch + parked_cap of 2^28 or more: GTX_ERR_ARG.
+ *   gtx_dstream_push       d_recs: n records, d_seq: n rows of seq_stride bytes of BAM 4-bit packed bases, d_planes: align_cap rows of
+ *                          plane_stride bytes (a multiple of 16; 16-byte aligned), d_meta: align_cap, d_items: item_cap entries --
+ *                          all DEVICE pointers.  n_align, n_items: HOST words.  The work is enqueued on `stream`, and the call ends
+ *                          by WAITING for `stream` for one small download: the two counts, the status and the three counters.
+ *                          Checked over all n records -- those the flag filter drops too -- before anything is consumed, in the
+ *                          host's order and with its statuses: n > align_cap, item_cap or max_batch GTX_ERR_CAPACITY; then per
+ *                          record rg >= n_read_groups GTX_ERR_ARG, l_qseq above the stream's max_read_len GTX_ERR_UNSUPPORTED (the
+ *                          message names the length), a read longer than its nibble row or than 2 x plane_stride bases GTX_ERR_ARG.
+ *                          Two reads of one name with the same IS_FIRST_IN_PAIR: GTX_ERR_ARG; more than parked_cap mates waiting at
+ *                          the end of the push: GTX_ERR_CAPACITY.  ON EVERY FAILING STATUS THE STREAM IS AS IT WAS BEFORE THE CALL
+ *                          (the next state is built beside the old one and adopted at the end) -- stricter than the host, which
+ *                          stops half-way through the batch at the IS_FIRST_IN_PAIR clash; what the output arrays hold then is not
+ *                          defined (nothing is written outside of them).  n == 0: GTX_OK, nothing launched.  Nibble-row and packed-row
+ *                          outputs are not offered.  One push at a time per stream object.
+ *   gtx_dstream_finish     forgets the parked mates (what gtx_stream_finish does for a graph without SVs); nothing is launched.
+ *   gtx_dstream_counts     as gtx_stream_counts, from the last push's download. */
+typedef struct gtx_dstream gtx_dstream;
+int gtx_dstream_create(const gtx_params *, uint32_t n_read_groups, int device, uint32_t max_batch, uint32_t parked_cap, gtx_dstream ** out);
+void gtx_dstream_destroy(gtx_dstream *);
+int gtx_dstream_push(gtx_dstream *, const gtx_stream_record * d_recs, const uint8_t * d_seq, uint32_t seq_stride, uint32_t n,
+                     uint8_t * d_planes, uint32_t plane_stride, gtx_read_meta * d_meta, uint32_t align_cap,
+                     gtx_score_item * d_items, uint32_t item_cap, uint32_t * n_align, uint32_t * n_items, void * stream);
+int gtx_dstream_finish(gtx_dstream *, void * stream);
+int gtx_dstream_counts(const gtx_dstream *, uint64_t * n_records, uint64_t * n_duplicated, uint64_t * n_parked);
+
 #ifdef __cplusplus
 }
 #endif
