@@ -452,7 +452,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GTX_WIDE_WAV
 // Pass 0 (hinted.hpp): ONE READ PER LANE.  Every read of the batch comes through here first: the reverse-orientation
 // task is settled (empty record, or queued for pass 2 when align_read asks for it), reads outside the length limits get
 // their empty records, and the forward task is finished from the position hint where the flags of that place prove the
-// global lookups -- else the read is queued for pass 1 (express4 over the queue).  One atomic per wavefront and queue.
+// global lookups -- else the read is queued for pass 1 (express4 over the queue).  One atomic for both queues per wavefront that
+// has a read to queue.
 template <uint32_t WAVES, bool DENSE, uint32_t NK = AlignCfg::KC, bool META_LDS = true>
 __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const & ix, uint8_t const * __restrict__ seq, uint32_t seq_stride,
                                             gtx_read_meta const * __restrict__ meta, uint32_t n_reads, uint32_t * __restrict__ records,
@@ -473,11 +474,8 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
   //  wavefront's 1 280 bytes still ten whole lines -- and the workgroup's 5 KB of LDS for them are not taken: 20.5 KB per
   //  workgroup are SEVEN workgroups per CU where 25.6 were six, and the kernel's 67 registers allow seven wavefronts per SIMD)
   __shared__ uint32_t s_meta[META_LDS ? WAVES : 1][META_LDS ? 64 * META_WORDS : 1];
-  // (the queue appends' few words live in the rows the wavefronts are through with by then -- wavefront w's two counts in the
-  //  first words of its own rows, the workgroup's two bases behind wavefront 0's counts: with no LDS besides the rows a workgroup
-  //  of the lean build takes 20 KB exactly and eight of them fit a CU)
-  auto s_count = [&](uint32_t q, uint32_t w) -> uint32_t & { return reinterpret_cast<uint32_t *>(&s_seq[w][0])[q]; };
-  auto s_base = [&](uint32_t q) -> uint32_t & { return reinterpret_cast<uint32_t *>(&s_seq[0][0])[2 + q]; };
+  // (no LDS besides the rows, and a wavefront touches its own rows only -- no barrier in the kernel: a workgroup of the lean build
+  //  takes 20 KB exactly and eight of them fit a CU)
   static_assert(sizeof(gtx_read_meta) % 4 == 0, "meta records are staged word-wise");
   uint32_t const lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t const wave_first = blockIdx.x * blockDim.x + wave * 64u;
@@ -527,7 +525,8 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
   uint32_t fwd_flag = 0;
   // (dense records: whole wavefronts only -- the block of 64 compact records is written as two stores over whole lines)
   bool const compact_wave = compact != nullptr && task_flags != nullptr && full;
-  static_assert(HINT_STAGE_WORDS == 16 && HINT_STAGE_WORDS * 4 <= ROW_BYTES, "a staged record is four 16-byte parts inside the read's row");
+  static_assert(HINT_STAGE_WORDS == 16 && (HINT_STAGE_WORDS + 4) * 4 <= ROW_BYTES,
+                "a staged record is four 16-byte parts inside the read's row, with four spare words behind it");
   if (read < n_reads)
   {
     gtx_read_meta m;
@@ -660,18 +659,27 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
     unsigned long long const S = __ballot(staged_rec);
     if (S != 0)
     {
-      // records of HINT_STAGE_WORDS words: lanes 4r .. 4r+3 of a round carry record 16 * round + r, 16 bytes each
+      // records of HINT_STAGE_WORDS words: lanes 4j .. 4j+3 of a round carry the j-th staged record of that round, 16 bytes each.
+      // As many rounds as there are staged records to fill them (cfg2: ten records per wavefront, one round -- four rounds over all
+      // 64 rows were a 64-bit shift and test, an LDS read and a slot address each, whatever the number): the staged lanes leave
+      // their numbers, in the order of the lanes, in the spare word behind the record of row 0, 1, 2, ...
       uint32_t const part = lane & 3u;
-#pragma unroll
-      for (uint32_t round = 0; round < 4; ++round)
+      uint32_t const n_staged = static_cast<uint32_t>(__builtin_popcountll(S));
+      uint32_t * const rows = reinterpret_cast<uint32_t *>(&s_seq[wave][0]);
+      if (staged_rec)
+        rows[static_cast<uint32_t>(__builtin_popcountll(S & ((1ull << lane) - 1ull))) * (ROW_PITCH * 4u) + HINT_STAGE_WORDS] = lane;
+      WaveHip::lds_sync();
+#pragma unroll 1
+      for (uint32_t first = 0; first < n_staged; first += 16u)
       {
-        uint32_t const r = round * 16u + (lane >> 2);
+        uint32_t const j = first + (lane >> 2);
         // (All four 16-byte parts of the staged record leave, 64 bytes for a record of 24: storing only the parts the record
         //  reaches into -- round 4, WRITE_SIZE 66 -> 34 B per read -- made this kernel SLOWER, 0.44 -> 0.565 ms: a store that
         //  covers half of a 64-byte piece of a line presumably becomes a read-modify-write at the memory side.  Fewer bytes need a
         //  denser record layout, not narrower stores.)
-        if ((S >> r) & 1ull)
+        if (j < n_staged)
         {
+          uint32_t const r = rows[j * (ROW_PITCH * 4u) + HINT_STAGE_WORDS]; // (< 64: a lane of this wavefront wrote it above)
           uint4_t const v = s_seq[wave][r * ROW_PITCH + part];
           uint32_t const rd = wave_first + r;
           uint32_t * dst = records + static_cast<uint64_t>(rd) * 2 * rec_words;
@@ -680,46 +688,29 @@ __device__ __forceinline__ void hinted_pass(GraphView const & g, IndexView const
       }
     }
   }
-  // Queue appends: ONE atomic per workgroup for BOTH queues (a device counter takes ~100 M returning atomics a second; one
-  // per wavefront -- 156 k per 10 M reads -- set the pace of this kernel, and so did a second counter per workgroup once a
-  // quarter of the workgroups had something for each queue).  The two fill counts are neighbouring words -- queue 2's low,
-  // queue 1's high -- and take one 64-bit add.  Every wavefront posts its counts, the first thread claims room for the
-  // workgroup, every wavefront writes at its offset.
+  // Queue appends: ONE atomic per wavefront that has something to append, for BOTH queues -- the two fill counts are neighbouring
+  // words, queue 2's low, queue 1's high, and take one 64-bit add.  A wavefront none of whose reads leaves the pass (cfg2: nineteen
+  // in twenty) is through here without one: a scalar branch, no LDS, no barrier.  (One atomic per WORKGROUP, the wavefronts' counts
+  // collected through LDS between two barriers, dates from when every wavefront appended: a device counter takes ~100 M returning
+  // atomics a second.  Every wavefront paid the barriers and the sums for it, and in a workgroup of two the earlier one waited in
+  // its slot for the later one.  Where nearly every wavefront appends -- the repeats leg -- the lean build now makes twice the
+  // atomics: its pass 0.079 -> 0.091-0.097 ms of a 21 ms step.)  Only the order of the entries inside a queue depends on who comes first; no later pass reads it.
   unsigned long long const F = __ballot(fwd), R = __ballot(rev), F2 = __ballot(fwd2);
-  if (lane == 0) // (a wavefront is through with its own rows here, and wavefront 0 with its own when it writes the bases)
-  {
-    s_count(0, wave) = static_cast<uint32_t>(__builtin_popcountll(F));
-    s_count(1, wave) = static_cast<uint32_t>(__builtin_popcountll(R) + __builtin_popcountll(F2));
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    uint32_t total1 = 0, total2 = 0;
-    for (uint32_t w = 0; w < WAVES; ++w)
-    {
-      total1 += s_count(0, w);
-      total2 += s_count(1, w);
-    }
-    unsigned long long base = 0;
-    if (total1 | total2)
-      base = atomicAdd(queue_counts, (static_cast<unsigned long long>(total1) << 32) | total2);
-    s_base(0) = static_cast<uint32_t>(base >> 32);
-    s_base(1) = static_cast<uint32_t>(base);
-  }
-  __syncthreads();
-  uint32_t off1 = s_base(0), off2 = s_base(1);
-  for (uint32_t w = 0; w < WAVES; ++w)
-    if (w < wave)
-    {
-      off1 += s_count(0, w);
-      off2 += s_count(1, w);
-    }
+  if ((F | R | F2) == 0)
+    return;
+  uint32_t const n_rev = static_cast<uint32_t>(__builtin_popcountll(R));
+  unsigned long long base = 0;
+  if (lane == 0)
+    base = atomicAdd(queue_counts, (static_cast<unsigned long long>(__builtin_popcountll(F)) << 32) |
+                                     (n_rev + static_cast<uint32_t>(__builtin_popcountll(F2))));
+  uint32_t const off1 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base >> 32));
+  uint32_t const off2 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base));
   if (fwd)
     queue1[off1 + static_cast<uint32_t>(__builtin_popcountll(F & ((1ull << lane) - 1ull)))] = read;
   if (rev)
     queue2[off2 + static_cast<uint32_t>(__builtin_popcountll(R & ((1ull << lane) - 1ull)))] = read * 2 + 1;
   if (fwd2)
-    queue2[off2 + static_cast<uint32_t>(__builtin_popcountll(R) + __builtin_popcountll(F2 & ((1ull << lane) - 1ull)))] = read * 2;
+    queue2[off2 + n_rev + static_cast<uint32_t>(__builtin_popcountll(F2 & ((1ull << lane) - 1ull)))] = read * 2;
 }
 
 #define GTX_HINTED_ARGS                                                                                                            \

@@ -783,7 +783,8 @@ GTX_DEV HintWalk hint_tail_walk(GraphView const & g, IndexView const & ix, Row r
 
 // The forward task of one read.  Returns true when the record was written, false = declined (nothing written).
 // `row`: the read in plane form as words (global memory, or the copy the kernel staged in LDS).
-// `stage` (may be NULL): room for HINT_STAGE_WORDS words; a record that fits is written there instead (zeros behind its
+// `stage` (may be NULL): room for HINT_STAGE_WORDS + 4 words -- the kernel gives the read's own row, whose bases are overwritten
+// once the path's sites are listed; a record that fits HINT_STAGE_WORDS is written there instead (zeros behind its
 // end) and the caller moves it to its slot -- the kernel does that four lanes per record.  Returns 0 = declined, 1 = the
 // record is in `rec`, 2 = it is in `stage`, HINT_TO_GENERAL = declined and known to be declined by the express pass too.
 constexpr uint32_t HINT_STAGE_WORDS = 16; // a record of up to three variant sites (6 + 3 * 3 words)
@@ -1245,10 +1246,63 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
   }
   // ---- variant sites of the path, most recent k-mer first (Path(p1, p2), path.cpp:38-82); a site under two
   //      neighbouring k-mers is one entry (the same base, hence the same allele)
-  uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0; // site << 16 | allele mask (named registers: an indexed array would live in scratch)
+  // Lean build: an entry is written where the record is being built, at an offset computed from `nvar` -- the staged row (nothing
+  // reads it as bases any more from here on: the compare, the probes and the walks are through), or the slot when records are not
+  // staged.  Only `nvar`, `last` and `clash` stay in registers.  A read that is declined further down leaves its entries behind
+  // in the row, where they are dead with the row (its side byte stays clear, so the compact block's reader passes it over), and
+  // takes them out of a slot again (`entries_back`).
+  // The staged row is zeroed behind its header FIRST, so that an entry is two stores and the slot gets the same sixteen words
+  // as ever.  A fifth and sixth entry have no room among the row's sixteen record words: such a record is not staged (18 words
+  // and more), so they are parked whole in words 18 and 19 of the row -- `stage` is HINT_STAGE_WORDS + 4 words -- and unpacked
+  // into the slot at the end.
+  // Dense build: the entries stay in six named registers v0..v5 (site << 16 | allele mask), written out at the end: a k-mer there
+  // may name a site again that is not the last one (`meet` below reads them all), and hinted_one tries a declined read again on
+  // an allele's window, for which the row must still hold the bases.
+  bool const to_row = stage != nullptr && rec_words >= HINT_STAGE_WORDS; // (the same for every lane)
+  uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0;
   uint32_t nvar = 0;
   uint32_t last = 0xFFFFFFFFu;
   bool clash = false;
+  if constexpr (!DENSE)
+    if (to_row)
+    {
+#pragma unroll
+      for (uint32_t k = 2; k < HINT_STAGE_WORDS; ++k)
+        stage[k] = 0u;
+    }
+  auto entry_out = [&](uint32_t k, uint32_t entry) // (lean build) entry k of the list
+  {
+    if (to_row)
+    {
+      if (k < 4)
+      {
+        stage[6 + 3 * k] = entry >> 16;
+        stage[7 + 3 * k] = entry & 0xFFFFu;
+      }
+      else if (k < 6)
+        stage[HINT_STAGE_WORDS - 2 + k] = entry;
+    }
+    else if (9 + 3 * k <= rec_words) // (past the slot's end the read is declined below)
+    {
+      uint32_t * const slot = hint_rec_ptr(rec_at);
+      slot[6 + 3 * k] = entry >> 16;
+      slot[7 + 3 * k] = entry & 0xFFFFu;
+      slot[8 + 3 * k] = 0u;
+    }
+  };
+  // (records that are not staged: a read declined from here on, or left without a path, takes its entries out of the slot again --
+  //  whichever pass writes the slot's record, the words behind it are the same)
+  auto entries_back = [&]()
+  {
+    if constexpr (!DENSE)
+      if (!to_row && nvar != 0)
+      {
+        uint32_t * const slot = hint_rec_ptr(rec_at);
+#pragma unroll 1
+        for (uint32_t k = 6; k + 3 <= rec_words && k < 6 + 3 * nvar; k += 3)
+          slot[k] = slot[k + 1] = slot[k + 2] = 0u;
+      }
+  };
   auto append = [&](uint32_t entry)
   {
     if constexpr (DENSE)
@@ -1287,21 +1341,11 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       // the site again (under the neighbouring k-mer, or the walk's): the allele sets are intersected (path.cpp:38-82)
       last &= entry | 0xFFFF0000u;
       clash = clash || (last & 0xFFFFu) == 0;
-      v0 = nvar == 1 ? last : v0;
-      v1 = nvar == 2 ? last : v1;
-      v2 = nvar == 3 ? last : v2;
-      v3 = nvar == 4 ? last : v3;
-      v4 = nvar == 5 ? last : v4;
-      v5 = nvar == 6 ? last : v5;
+      entry_out(nvar - 1, last);
     }
     else
     {
-      v0 = nvar == 0 ? entry : v0;
-      v1 = nvar == 1 ? entry : v1;
-      v2 = nvar == 2 ? entry : v2;
-      v3 = nvar == 3 ? entry : v3;
-      v4 = nvar == 4 ? entry : v4;
-      v5 = nvar == 5 ? entry : v5;
+      entry_out(nvar, entry);
       ++nvar;
       last = entry;
     }
@@ -1331,9 +1375,10 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
   push(0, k0);
   if (head_mask != 0) // (Path(pp, original), genotype_paths.cpp:262: the original's sites stay in front, the start walk's come last)
     append((head_site << 16) | head_mask);
-  if (clash || nvar > 6 || 6 + 3 * nvar > rec_words) // (six named registers hold the sites)
+  if (clash || nvar > 6 || 6 + 3 * nvar > rec_words) // (a record holds six sites at the most)
   {
     GTX_HINT_NOTE(13);
+    entries_back();
     return false;
   }
   uint32_t np = 1, longest = re - rs + 1;
@@ -1365,6 +1410,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
         // (neighbours that are not a SNP's alleles; a SNP on the k-mer's last base -- the next k-mer's first: whether the
         //  other allele's chain lives on depends on what kind of list that k-mer brings)
         GTX_HINT_NOTE(106);
+        entries_back();
         return HINT_TO_GENERAL;
       }
       two_chains = off != 0;
@@ -1398,6 +1444,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
         if (!ok)
         {
           GTX_HINT_NOTE(107); // twin chains over a run with a set of alleles, or with another allele and a substitution
+          entries_back();
           return HINT_TO_GENERAL;
         }
       }
@@ -1407,6 +1454,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
         // (the fifth k-mer of a read of 156 bases and more: whether its substitution sits on its last base -- base 155, the
         //  tail walk's first -- is not among the compare's counts)
         GTX_HINT_NOTE(108);
+        entries_back();
         return HINT_TO_GENERAL;
       }
       bool const last_only = mm_run == (1u << hi) && hc_edge(h, hi + 1) == 1 && ((km_hi >> HK_SET_SHIFT) & 255u) == 0;
@@ -1414,6 +1462,7 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
       if (pre == L - 1 || re != L - 1 || (twin && nvar > 1))
       {
         GTX_HINT_NOTE(109); // twin chains: no tail, a failed tail walk, or twins over several sites
+        entries_back();
         return HINT_TO_GENERAL;
       }
       if (twin && mm_run == 0)
@@ -1429,41 +1478,84 @@ GTX_DEV uint32_t hinted_on_path(GraphView const & g, IndexView const & ix, Row r
   }
   uint32_t const path_words = 4 + 3 * nvar;
   if (2 + np * path_words > rec_words)
+  {
+    entries_back();
     return false;
-  bool const to_stage = stage != nullptr && rec_words >= HINT_STAGE_WORDS && 2 + (np ? np : 1u) * path_words <= HINT_STAGE_WORDS;
-  uint32_t * rec = to_stage ? stage : hint_rec_ptr(rec_at);
-  if (to_stage)
-  {
-#pragma unroll
-    for (uint32_t k = 2; k < HINT_STAGE_WORDS; ++k)
-      rec[k] = 0u;
   }
-  rec[0] = np;
-  rec[1] = longest | (L << 16) | ((np && nvar) ? GTX_REC_HAS_VARIANTS : 0u);
-  if (np)
+  bool const to_stage = to_row && 2 + (np ? np : 1u) * path_words <= HINT_STAGE_WORDS;
+  // the header, the path's four words and the twin's copy, around the entries
+  auto finish = [&](uint32_t * rec)
   {
-    rec[2] = start;
-    rec[3] = end;
-    rec[4] = rs | (re << 16);
-    rec[5] = mism | (nvar << 16);
-    auto put = [&](uint32_t k, uint32_t entry)
+    rec[0] = np;
+    rec[1] = longest | (L << 16) | ((np && nvar) ? GTX_REC_HAS_VARIANTS : 0u);
+    if (np)
     {
-      if (k < nvar)
+      rec[2] = start;
+      rec[3] = end;
+      rec[4] = rs | (re << 16);
+      rec[5] = mism | (nvar << 16);
+      if (np == 2) // the twin: the same words again
+        for (uint32_t k = 0; k < path_words; ++k)
+          rec[2 + path_words + k] = rec[2 + k];
+    }
+  };
+  if constexpr (DENSE)
+  {
+    uint32_t * rec = to_stage ? stage : hint_rec_ptr(rec_at);
+    if (to_stage)
+    {
+#pragma unroll
+      for (uint32_t k = 2; k < HINT_STAGE_WORDS; ++k)
+        rec[k] = 0u;
+    }
+    if (np)
+    {
+      auto put = [&](uint32_t k, uint32_t entry)
       {
-        rec[6 + 3 * k] = entry >> 16;
-        rec[7 + 3 * k] = entry & 0xFFFFu;
-        rec[8 + 3 * k] = 0u;
+        if (k < nvar)
+        {
+          rec[6 + 3 * k] = entry >> 16;
+          rec[7 + 3 * k] = entry & 0xFFFFu;
+          rec[8 + 3 * k] = 0u;
+        }
+      };
+      put(0, v0);
+      put(1, v1);
+      put(2, v2);
+      put(3, v3);
+      put(4, v4);
+      put(5, v5);
+    }
+    finish(rec);
+  }
+  else if (to_stage)
+  {
+    // (a record without a path, more than ten mismatches: its entries go back to the zeros the slot has always got there)
+    if (np == 0 && nvar != 0)
+    {
+#pragma unroll 1
+      for (uint32_t k = 6; k < 6 + 3 * nvar; ++k)
+        stage[k] = 0u;
+    }
+    finish(stage);
+  }
+  else
+  {
+    uint32_t * const slot = hint_rec_ptr(rec_at);
+    if (to_row && np) // (four sites and more: out of the row, where the entries were put before this was known)
+    {
+#pragma unroll 1
+      for (uint32_t k = 0; k < nvar; ++k)
+      {
+        uint32_t const entry = k < 4 ? (stage[6 + 3 * k] << 16) | stage[7 + 3 * k] : stage[HINT_STAGE_WORDS - 2 + k];
+        slot[6 + 3 * k] = entry >> 16;
+        slot[7 + 3 * k] = entry & 0xFFFFu;
+        slot[8 + 3 * k] = 0u;
       }
-    };
-    put(0, v0);
-    put(1, v1);
-    put(2, v2);
-    put(3, v3);
-    put(4, v4);
-    put(5, v5);
-    if (np == 2) // the twin: the same words again
-      for (uint32_t k = 0; k < path_words; ++k)
-        rec[2 + path_words + k] = rec[2 + k];
+    }
+    if (np == 0)
+      entries_back();
+    finish(slot);
   }
   return to_stage ? 2u : 1u;
 }

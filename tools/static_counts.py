@@ -14,4 +14,5 @@ for name in sys.argv[2:] or ["gtx_align_hinted_kernel", "gtx_align_express4q_ker
     lines = [l.strip() for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith((".", ";"))]
     lines = [l for l in lines if not l.endswith(":")]
     count = lambda *p: sum(1 for l in lines if l.startswith(p))
-    print("%-30s static: VALU %5d  SALU %5d  LDS %4d  VMEM %4d  total %5d" % (name, count("v_"), count("s_"), count("ds_"), count("global_", "buffer_", "flat_", "scratch_"), len(lines)))
+    print("%-30s static: VALU %5d (selects %4d)  SALU %5d  LDS %4d  VMEM %4d  barriers %d  total %5d" % (
+        name, count("v_"), count("v_cndmask"), count("s_"), count("ds_"), count("global_", "buffer_", "flat_", "scratch_"), count("s_barrier"), len(lines)))
