@@ -4,7 +4,9 @@
 // case.bin: 12 uint32 (sam_flag_filter, force_align_both_orientations, max_read_len, n_read_groups, max_batch, parked_cap, seq_stride,
 // plane_stride, waves, n_pushes, n_records, 0); the records; their rows; per push 6 uint32 (lo, hi, align_cap, item_cap, and the
 // entries its output arrays hold: tasks, items).
-// out.bin: per push 4 uint32 (status, n_align, n_items, 0), 3 uint64 (records, duplicated, parked), then the three output arrays.
+// out.bin: per push 8 uint32 (status, n_align, n_items, 0, and the four words of the download that say why a push failed: why, record,
+// l_qseq, n_parked -- of a push that runs no kernel 0, 0, 0 and the mates that wait), 3 uint64 (records, duplicated, parked), then the
+// three output arrays.
 // Per push the steps as the library launches them, each over `waves` wavefronts (wavefront w takes the tiles w, w + waves, ...).  A
 // STABLE HOST SORT AND HOST LOOPS STAND IN FOR THE rocPRIM CALLS between the kernels (the scans and the two sorts by key): what is
 // emulated is the kernels' text, not rocPRIM.  The push's records and rows are copied into heap blocks of exactly their sizes, the
@@ -128,6 +130,7 @@ int main(int argc, char ** argv)
       std::memcpy(rows.p, all_rows.data() + static_cast<size_t>(lo) * seq_stride, static_cast<size_t>(n) * seq_stride);
     }
     uint32_t status = GTX_OK, n_align = 0, n_items = 0;
+    uint32_t reason[4] = {0, 0, 0, n_parked};
     if (n > align_cap || n > item_cap || n > max_batch)
       status = GTX_ERR_CAPACITY;
     else if (n != 0)
@@ -207,6 +210,10 @@ int main(int argc, char ** argv)
         dstream_emit_items_wave<WaveSeq>(a, w, waves);
       dstream_finish_wave<WaveSeq>(a);
       status = out.p->status;
+      reason[0] = out.p->why;
+      reason[1] = out.p->record;
+      reason[2] = out.p->l_qseq;
+      reason[3] = out.p->n_parked;
       if (status == GTX_OK)
       {
         cur ^= 1u;
@@ -217,7 +224,7 @@ int main(int argc, char ** argv)
         n_items = out.p->n_items;
       }
     }
-    uint32_t const head_words[4] = {status, n_align, n_items, 0};
+    uint32_t const head_words[8] = {status, n_align, n_items, 0, reason[0], reason[1], reason[2], reason[3]};
     uint64_t const counts[3] = {n_kept_records, n_duplicated, n_parked};
     if (!write_exact(o, head_words, sizeof head_words) || !write_exact(o, counts, sizeof counts) || !write_exact(o, planes.p, planes.n) ||
         !write_exact(o, meta.p, meta.n * sizeof(gtx_read_meta)) || !write_exact(o, items.p, items.n * sizeof(gtx_score_item)))

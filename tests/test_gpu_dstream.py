@@ -3,7 +3,8 @@
 Every case of tests/dstream_cases.py under every one of its scripts, judged by its judge: the status, the counts and every byte of the
 plane rows, the read meta and the items equal the plain definition.  A script's pushes write into one block per output, preset to 0xA5,
 each push's part sized to exactly what the definition leaves with a guard behind it that stays untouched.  Then the launch shapes (1, 63,
-64, 65, 257 and 5 000 records a push), two runs that leave the same bytes, a stream that is not the null stream, the refusals, and the
+64, 65, 257 and 5 000 records a push), two runs that leave the same bytes, a stream that is not the null stream, the refusals, what a
+failing push says of its reason (gtx_last_error), gtx_dstream_finish beside gtx_stream_finish, and the
 stream's outputs going straight into gtx_align_batch_planes and gtx_score_batch_flags without a host copy: the accumulators of the host
 stream's run.  All values are bytes and words; there is no tolerance."""
 import ctypes as C
@@ -127,6 +128,64 @@ def test_the_refusals():
     assert (rc, na, ni) == (dc.OK, len(want["meta"]), len(want["items"])) and ds.counts()["duplicated"] == want["counts"][1]
     ds.finish()
     assert ds.counts()["parked"] == 0
+
+
+def case_labelled(name, start):
+    c, = [c for c in dc.cases(name) if c.label.startswith(start)]
+    return c
+
+
+def test_a_failing_push_says_which_record_and_how_many_wait():
+    """the four words of the download that no output carries reach the caller as gtx_last_error: the length of the FIRST record beyond
+    max_read_len -- a record the filter drops, in front of a read group out of range; a shorter one in front of a longer one -- and
+    the mates that would wait.  The numbers are the definition's (dstream_cases.define: reason)"""
+    L = gtx.lib()
+    for c, status, why, message in (
+            (case_labelled("limits", "a read of 257 bases in front of a read group out of range"), dc.ERR_UNSUPPORTED, (dc.WHY_LONG, 2, 257, 0),
+             b"gtx_dstream_push: a read of 257 bases (the stream's max_read_len is 256)"),
+            (case_labelled("fail_order", "a read of 300 bases behind a read of 260"), dc.ERR_UNSUPPORTED, (dc.WHY_LONG, 1, 260, 0),
+             b"gtx_dstream_push: a read of 260 bases (the stream's max_read_len is 256)"),
+            (case_labelled("limits", "parked_cap one over"), dc.ERR_CAPACITY, (dc.WHY_PARKED, 0, 0, 3),
+             b"gtx_dstream_push: 3 mates wait at the end of the push, the stream was made with parked_cap 2")):
+        want, = c.want("whole")
+        assert (want["status"], want["reason"]) == (status, why)
+        got, = device_run(c, dict(c.scripts)["whole"], c.rooms("whole"))
+        assert got["status"] == status and L.gtx_last_error() == message, (c.label, got["status"], L.gtx_last_error())
+        assert got["counts"] == (0, 0, 0)
+
+
+def test_a_mate_of_a_read_parked_before_finish_waits_anew():
+    """gtx_dstream_finish forgets the parked mates as gtx_stream_finish does: the second mate of a read parked before it makes no item and
+    waits itself -- the device stream and the host stream side by side, byte for byte, the carried record and next_align_index kept"""
+    import torch
+    b = dc.Builder()
+    b.add(dc.bases(40, 1), pos=100, flag=dc.PAIRED | dc.FIRST | dc.MATE_REVERSED, isize=200, name=1, sample=1)
+    b.add(dc.bases(40, 2), pos=101, name=2)
+    b.add(dc.bases(40, 2), pos=101, flag=dc.PAIRED | dc.SECOND | dc.REVERSED, isize=-200, name=1, sample=2)  # (a duplicate of the record carried over finish)
+    b.add(dc.bases(40, 3), pos=102, name=3)
+    c = b.case("a mate on either side of finish")
+    cuts = ((0, 2), (2, 4))
+    # without finish the second push pairs the two
+    unfinished = c.want_of([dc.push(lo, hi) for lo, hi in cuts])
+    assert [len(w["items"]) for w in unfinished] == [1, 2] and unfinished[1]["counts"] == (4, 1, 0)
+    hs = gtx.Stream(params_of(c), 1)
+    hs.set_planes(c.plane_stride)
+    ds = gtx.DeviceStream(params_of(c), 1, 0, len(c.recs), len(c.recs))
+    for k, (lo, hi) in enumerate(cuts):
+        recs, rows = np.ascontiguousarray(c.recs[lo:hi]), np.ascontiguousarray(c.rows[lo:hi])
+        host = hs.push(recs, rows)
+        d_recs, d_rows = torch.from_numpy(recs.view(np.uint8).reshape(-1).copy()).to("cuda:0"), torch.from_numpy(rows).to("cuda:0")
+        dev = [t.cpu().numpy() for t in ds.push(d_recs, d_rows, c.plane_stride)]
+        assert [len(x) for x in host] == ([2, 2, 1], [1, 1, 1])[k]  # (tasks: the second push's first record is a duplicate; items: the unpaired ones only)
+        for h, d in zip(host, dev):
+            assert h.tobytes() == d.tobytes(), (k, h, d)
+        assert ds.counts() == hs.counts() and ds.counts()["parked"] == 1
+        if k == 0:
+            hs.finish()
+            ds.finish()
+            assert ds.counts() == hs.counts() == dict(records=2, duplicated=0, parked=0)
+    assert ds.counts() == dict(records=4, duplicated=1, parked=1)
+    assert host[2]["first"]["align_index"].tolist() == [2] and host[2]["second"]["align_index"].tolist() == [dc.INVALID]
 
 
 def test_the_outputs_go_straight_into_alignment_and_scoring():
