@@ -40,6 +40,7 @@ struct AlignCfg
   static constexpr uint32_t MW = 2;          // 32-bit words of an allele set: alleles 0..63 (a label beyond is an overflow)
   static constexpr bool DYN = false;         // tables are arrays of the sizes above (true: pointers into a slab of HBM, sizes at run time)
 };
+static_assert(AlignCfg::LBL_CAP == 40 && AlignCfg::KEY_CAP == 192 && AlignCfg::XL_CAP == 2 && !AlignCfg::DYN, "the main pass' tables");
 
 #include "align_core.inl"
 #include "express4.inl"
@@ -49,29 +50,51 @@ struct AlignCfg
 namespace gtx
 {
 
+// The passes behind the general one keep their tables in HBM.  What their configurations share is stated here once, each
+// namespace states its own numbers: two families, tables of a fixed size (big, wide, longr) and tables cut out of a slab at run
+// time (exact, exactw, exactl, exactlw: by read length and by the words of an allele set).
+struct HbmCfg
+{
+  static constexpr uint32_t LOC_CAP = 256;  // MAX_NUM_LOCATIONS_PER_PATH (beyond it the reference skips the path)
+  static constexpr uint32_t WLISTS = 256;   // MAX_SEED_NUMBER_FOR_WALKING
+  static constexpr uint32_t KEY_CAP = 388;  // 4 * 97 (type_conversions.cpp:207-266)
+  static constexpr uint32_t KC = AlignCfg::KC, HE_CAP = AlignCfg::HE_CAP; // (the lookups issued up front: as in the main pass)
+  static constexpr uint32_t XL_CAP = 4;
+};
+struct FixedTablesCfg : HbmCfg
+{
+  static constexpr uint32_t LBL_CAP = 2048; // a single exact key may have thousands of occurrences in repeats
+  static constexpr uint32_t WL_CAP = 2048;
+  static constexpr bool DYN = false;
+};
+// The sizes that stay constants in the exact pass are proven bounds, not budgets (see namespace exact, below)
+template <uint32_t READ, uint32_t KMERS, uint32_t MASK_WORDS>
+struct RunTimeTablesCfg : HbmCfg
+{
+  static constexpr uint32_t MAX_READ = READ;
+  static constexpr uint32_t MAX_KMERS = KMERS; // get_num_kmers(MAX_READ)
+  static constexpr uint32_t LBL_CAP = 1, MAXP = 1, MAXPP = 1, CAND_CAP = 1, WL_CAP = 1; // (run-time sizes: DynTables)
+  static constexpr uint32_t MAXV = READ;   // variant sites of a path
+  static constexpr uint32_t MAXIDS = READ; // variant nodes of a walked sequence
+  static constexpr uint32_t MW = MASK_WORDS;
+  static constexpr bool DYN = true;
+};
+
 // second pass: the same code over large tables that live in HBM (one workspace per workgroup)
 namespace big
 {
-struct AlignCfg
+struct AlignCfg : FixedTablesCfg
 {
   static constexpr uint32_t MAX_READ = 256;
   static constexpr uint32_t MAX_KMERS = 8;
-  static constexpr uint32_t LBL_CAP = 2048;  // a single exact key may have thousands of occurrences in repeats
   static constexpr uint32_t MAXP = 512;      // (the reference stops walking above 256 seeds)
   static constexpr uint32_t MAXPP = 512;
   static constexpr uint32_t MAXV = 40;
   static constexpr uint32_t CAND_CAP = 512;  // the reference stops branching at 128 but one round may overshoot
   static constexpr uint32_t MAXIDS = 40;
-  static constexpr uint32_t LOC_CAP = 256;   // MAX_NUM_LOCATIONS_PER_PATH
-  static constexpr uint32_t WL_CAP = 2048;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
   static constexpr uint32_t MW = 2;
-  static constexpr bool DYN = false;
 };
+static_assert(AlignCfg::LBL_CAP == 2048 && AlignCfg::MAXV == 40 && !AlignCfg::DYN, "the HBM-table pass' tables");
 #include "align_core.inl"
 } // namespace big
 
@@ -80,26 +103,18 @@ struct AlignCfg
 // passes in front hand on every task that meets an allele number >= 64 (GTX_ST_WIDE_ALLELE).
 namespace wide
 {
-struct AlignCfg // (a path with its allele sets is 5 KB here: fewer of them than in big::, what exceeds them keeps its status)
+struct AlignCfg : FixedTablesCfg // (a path with its allele sets is 5 KB here: fewer of them than in big::, what exceeds them keeps its status)
 {
   static constexpr uint32_t MAX_READ = 256;
   static constexpr uint32_t MAX_KMERS = 8;
-  static constexpr uint32_t LBL_CAP = 2048;
   static constexpr uint32_t MAXP = 128;
   static constexpr uint32_t MAXPP = 128;
   static constexpr uint32_t MAXV = 16;
   static constexpr uint32_t CAND_CAP = 8192; // one round of a walk over a site branches into every allele within the mismatch budget
   static constexpr uint32_t MAXIDS = 24;
-  static constexpr uint32_t LOC_CAP = 256;
-  static constexpr uint32_t WL_CAP = 2048;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
   static constexpr uint32_t MW = GTX_WIDE_MASK_WORDS;
-  static constexpr bool DYN = false;
 };
+static_assert(AlignCfg::WL_CAP == 2048 && AlignCfg::CAND_CAP == 8192 && AlignCfg::MW > 2 && !AlignCfg::DYN, "the wide-site pass' tables");
 #include "align_core.inl"
 } // namespace wide
 
@@ -115,43 +130,19 @@ struct AlignCfg // (a path with its allele sets is 5 KB here: fewer of them than
 // MAX_SEED_NUMBER_FOR_WALKING paths, a multi-key list is cut at max_index_labels.
 namespace exact
 {
-struct AlignCfg
+struct AlignCfg : RunTimeTablesCfg<256, 8, 2>
 {
-  static constexpr uint32_t MAX_READ = 256;
-  static constexpr uint32_t MAX_KMERS = 8;
-  static constexpr uint32_t LBL_CAP = 1, MAXP = 1, MAXPP = 1, CAND_CAP = 1, WL_CAP = 1; // (run-time sizes: DynTables)
-  static constexpr uint32_t MAXV = MAX_READ;    // variant sites of a path
-  static constexpr uint32_t MAXIDS = MAX_READ;  // variant nodes of a walked sequence
-  static constexpr uint32_t LOC_CAP = 256;      // MAX_NUM_LOCATIONS_PER_PATH (beyond it the reference skips the path)
-  static constexpr uint32_t WLISTS = 256;       // MAX_SEED_NUMBER_FOR_WALKING
-  static constexpr uint32_t KEY_CAP = 388;      // 4 * 97 (type_conversions.cpp:207-266)
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
-  static constexpr uint32_t MW = 2;
-  static constexpr bool DYN = true;
 };
+static_assert(AlignCfg::MAXV == 256 && AlignCfg::LBL_CAP == 1 && AlignCfg::MW == 2 && AlignCfg::DYN, "the exact pass' bounds");
 #include "align_core.inl"
 } // namespace exact
 
 namespace exactw // ... for graphs that have a site of more than 64 alleles
 {
-struct AlignCfg
+struct AlignCfg : RunTimeTablesCfg<256, 8, GTX_WIDE_MASK_WORDS>
 {
-  static constexpr uint32_t MAX_READ = 256;
-  static constexpr uint32_t MAX_KMERS = 8;
-  static constexpr uint32_t LBL_CAP = 1, MAXP = 1, MAXPP = 1, CAND_CAP = 1, WL_CAP = 1;
-  static constexpr uint32_t MAXV = MAX_READ;
-  static constexpr uint32_t MAXIDS = MAX_READ;
-  static constexpr uint32_t LOC_CAP = 256;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
-  static constexpr uint32_t MW = GTX_WIDE_MASK_WORDS;
-  static constexpr bool DYN = true;
 };
+static_assert(AlignCfg::MAXV == 256 && AlignCfg::LBL_CAP == 1 && AlignCfg::MW > 2 && AlignCfg::DYN, "the exact pass' bounds");
 #include "align_core.inl"
 } // namespace exactw
 

@@ -3156,6 +3156,53 @@ GTX_DEV uint32_t align_one(GraphView const & g, IndexView const & ix, AlignWorks
   return status;
 }
 
+// ... and of the passes behind it (the HBM-table pass, the wide-site pass, the exact pass, tier 1 of the long reads): a record
+// longer than its slot goes to the big-record arena -- `claim(n)` takes n words of it and returns their offset; the slot keeps
+// the header, GTX_ST_EXTERNAL and the offset -- or, when the arena is full, the slot gets GTX_ST_RECORD_OVERFLOW.  Returns the
+// raw status: non-zero (a table overflowed, or an allele number beyond this pass' sets) and the caller hands the task on.
+template <class W, class Claim>
+GTX_DEV uint32_t align_one_arena(GraphView const & g, IndexView const & ix, AlignWorkspace & ws, uint8_t const * seq4, uint32_t len,
+                                 bool reverse, uint32_t * rec, uint32_t rec_words, uint32_t * arena, uint64_t arena_words, Claim && claim)
+{
+  uint32_t np = 0, longest = 0, ext = 0;
+  uint32_t const raw = GTX_U(align_paths<W>(g, ix, ws, seq4, len, reverse, np, longest));
+  np = GTX_U(np);
+  longest = GTX_U(longest);
+  uint32_t status = raw & ~GTX_ST_WIDE_ALLELE;
+  uint32_t * body = rec + 2;
+  uint64_t off = 0;
+  if (status)
+    np = 0;
+  else
+  {
+    uint32_t const size = GTX_U(record_size<W>(Here{}, ws, np));
+    if (size > rec_words)
+    {
+      off = claim(size - 2);
+      if (off + (size - 2) > arena_words || off + (size - 2) > 0xFFFFFFFFull)
+      {
+        status = GTX_ST_RECORD_OVERFLOW;
+        np = 0;
+      }
+      else
+      {
+        body = arena + off;
+        ext = GTX_ST_EXTERNAL;
+      }
+    }
+  }
+  uint32_t const has_var = write_record_body<W>(Here{}, ws, np, body);
+  GTX_LEAD
+  {
+    rec[0] = np | ((status | ext) << 16);
+    rec[1] = (np == 0 ? 0 : longest) | (len << 16) | (np == 0 ? 0u : has_var);
+    if (ext)
+      rec[2] = static_cast<uint32_t>(off);
+  }
+  W::lds_sync();
+  return raw;
+}
+
 // First pass, one (read, orientation): the read either is one of the simple ones -- fast seeding gives its single path and
 // finish_single_path completes it -- and its record is written, or nothing is written and the caller queues it for the
 // general pass (returns false).
@@ -3189,3 +3236,22 @@ GTX_DEV bool express_one(GraphView const & g, IndexView const & ix, SeedWorkspac
 #endif
   return true;
 }
+
+// This instantiation as a type, so that a template can be written over the namespaces (gtx_hbm_passes.hip: one text for the
+// kernels of big, wide, exact, ...): names and forwards only.
+struct Instance
+{
+  using Cfg = AlignCfg;
+  using Workspace = AlignWorkspace;
+  template <class W, class Claim>
+  static GTX_DEV uint32_t task(GraphView const & g, IndexView const & ix, Workspace & ws, uint8_t const * seq4, uint32_t len, bool reverse,
+                               uint32_t * rec, uint32_t rec_words, uint32_t * arena, uint64_t arena_words, Claim && claim)
+  {
+    return align_one_arena<W>(g, ix, ws, seq4, len, reverse, rec, rec_words, arena, arena_words, claim);
+  }
+  template <class W>
+  static GTX_DEV bool setup(Workspace * ws_at_slab_head, uint64_t slab_bytes, uint32_t cand_cap, uint32_t cap_v)
+  {
+    return exact_setup<W>(ws_at_slab_head, slab_bytes, cand_cap, cap_v);
+  }
+};

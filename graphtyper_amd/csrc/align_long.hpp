@@ -11,27 +11,19 @@ namespace gtx
 // crosses about 40 sites of a graph with a SNP every 25 bases).  What exceeds them goes on to tier 2.
 namespace longr
 {
-struct AlignCfg
+struct AlignCfg : FixedTablesCfg
 {
   static constexpr uint32_t MAX_READ = GTX_MAX_READ_LONG;
   static constexpr uint32_t MAX_KMERS = 32; // get_num_kmers(MAX_READ)
-  static constexpr uint32_t LBL_CAP = 2048;
   static constexpr uint32_t MAXP = 512;
   static constexpr uint32_t MAXPP = 512;
   static constexpr uint32_t MAXV = 64;
   static constexpr uint32_t CAND_CAP = 512;
   static constexpr uint32_t MAXIDS = 64;
-  static constexpr uint32_t LOC_CAP = 256;
-  static constexpr uint32_t WL_CAP = 2048;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
   static constexpr uint32_t MW = 2;
-  static constexpr bool DYN = false;
 };
 static_assert(1 + (AlignCfg::MAX_READ - 32) / 31 <= AlignCfg::MAX_KMERS, "k-mers of the longest read");
+static_assert(AlignCfg::LBL_CAP == 2048 && AlignCfg::MAXV == 64 && !AlignCfg::DYN, "tier 1's tables");
 #include "align_core.inl"
 } // namespace longr
 
@@ -39,43 +31,19 @@ static_assert(1 + (AlignCfg::MAX_READ - 32) / 31 <= AlignCfg::MAX_KMERS, "k-mers
 // bounds of a read of MAX_READ bases
 namespace exactl
 {
-struct AlignCfg
+struct AlignCfg : RunTimeTablesCfg<GTX_MAX_READ_LONG, 32, 2>
 {
-  static constexpr uint32_t MAX_READ = GTX_MAX_READ_LONG;
-  static constexpr uint32_t MAX_KMERS = 32;
-  static constexpr uint32_t LBL_CAP = 1, MAXP = 1, MAXPP = 1, CAND_CAP = 1, WL_CAP = 1;
-  static constexpr uint32_t MAXV = MAX_READ;
-  static constexpr uint32_t MAXIDS = MAX_READ;
-  static constexpr uint32_t LOC_CAP = 256;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
-  static constexpr uint32_t MW = 2;
-  static constexpr bool DYN = true;
 };
+static_assert(AlignCfg::MAXV == GTX_MAX_READ_LONG && AlignCfg::MAX_KMERS == 32 && AlignCfg::MW == 2 && AlignCfg::DYN, "tier 2's bounds");
 #include "align_core.inl"
 } // namespace exactl
 
 namespace exactlw // ... for graphs that have a site of more than 64 alleles
 {
-struct AlignCfg
+struct AlignCfg : RunTimeTablesCfg<GTX_MAX_READ_LONG, 32, GTX_WIDE_MASK_WORDS>
 {
-  static constexpr uint32_t MAX_READ = GTX_MAX_READ_LONG;
-  static constexpr uint32_t MAX_KMERS = 32;
-  static constexpr uint32_t LBL_CAP = 1, MAXP = 1, MAXPP = 1, CAND_CAP = 1, WL_CAP = 1;
-  static constexpr uint32_t MAXV = MAX_READ;
-  static constexpr uint32_t MAXIDS = MAX_READ;
-  static constexpr uint32_t LOC_CAP = 256;
-  static constexpr uint32_t WLISTS = 256;
-  static constexpr uint32_t KEY_CAP = 388;
-  static constexpr uint32_t KC = 5;
-  static constexpr uint32_t HE_CAP = 4;
-  static constexpr uint32_t XL_CAP = 4;
-  static constexpr uint32_t MW = GTX_WIDE_MASK_WORDS;
-  static constexpr bool DYN = true;
 };
+static_assert(AlignCfg::MAXV == GTX_MAX_READ_LONG && AlignCfg::MAX_KMERS == 32 && AlignCfg::MW > 2 && AlignCfg::DYN, "tier 2's bounds");
 #include "align_core.inl"
 } // namespace exactlw
 } // namespace gtx

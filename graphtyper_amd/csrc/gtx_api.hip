@@ -991,11 +991,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GTX_GENERAL_
     if (big_tasks && ((st & (GTX_ST_LABEL_OVERFLOW | GTX_ST_PATH_OVERFLOW | GTX_ST_DFS_OVERFLOW | GTX_ST_RECORD_OVERFLOW)) || (force_big & 1u)) &&
         (threadIdx.x & 63u) == 0)
     {
-      uint32_t const slot = atomicAdd(big_state, 1u);
-      if (slot < big_task_cap)
-        big_tasks[slot] = task_base + task; // (the HBM-table pass runs once over the whole batch)
-      else
-        atomicAdd(big_state + 3, 1u);
+      queue_push(big_tasks, big_task_cap, big_state, task_base + task); // (the HBM-table pass runs once over the whole batch)
 #ifdef GTX_PROF // (profiling build: why the tasks leave this pass -- [29] = labels | paths << 32, [30] = walk | record << 32)
       atomicAdd(g.prof + 29, ((st & GTX_ST_LABEL_OVERFLOW) ? 1ull : 0ull) | ((st & GTX_ST_PATH_OVERFLOW) ? 1ull << 32 : 0ull));
       atomicAdd(g.prof + 30, ((st & GTX_ST_DFS_OVERFLOW) ? 1ull : 0ull) | ((st & GTX_ST_RECORD_OVERFLOW) ? 1ull << 32 : 0ull));
@@ -1084,9 +1080,9 @@ __global__ __launch_bounds__(64) void gtx_seen_kernel(uint32_t * __restrict__ se
 {
   if (threadIdx.x == 0)
   {
-    __hip_atomic_store(seen + 0, big_state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(seen + 0, big_state[Q_QUEUED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (exact_state)
-      __hip_atomic_store(seen + 2, exact_state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(seen + 2, exact_state[Q_QUEUED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -1504,10 +1500,10 @@ static void counter_set_select(CallScratch & s, uint32_t k)
 {
   s.counter_set = k;
   s.d_counters = s.d_counter_sets.get() + static_cast<size_t>(k) * CallScratch::COUNTER_PITCH;
-  s.d_span = reinterpret_cast<unsigned long long *>(s.d_counters + 8 + 48); // (its pinned home is made by the first timed call)
-  s.d_big_state = s.has_big ? s.d_counters + 8 : nullptr;
-  s.d_wide_state = s.has_wide ? s.d_big_state + 8 : nullptr;
-  s.d_exact_state = s.has_big ? s.d_big_state + 16 : nullptr;
+  s.d_span = reinterpret_cast<unsigned long long *>(s.d_counters + CallScratch::PASS_COUNTERS + HBM_STATE_WORDS); // (its pinned home is made by the first timed call)
+  s.d_big_state = s.has_big ? s.d_counters + CallScratch::PASS_COUNTERS : nullptr;
+  s.d_wide_state = s.has_wide ? s.d_big_state + HBM_STATE_WIDE : nullptr;
+  s.d_exact_state = s.has_big ? s.d_big_state + HBM_STATE_EXACT : nullptr;
 }
 
 static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
@@ -1516,7 +1512,7 @@ static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
   hipEvent_t ev = nullptr;
   bool ok = hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "scratch event");
   s->done.reset(ev);
-  static_assert(CallScratch::COUNTER_WORDS == 8 + 48 + 4 && CallScratch::COUNTER_WORDS <= CallScratch::COUNTER_PITCH, "counter sets");
+  static_assert(CallScratch::COUNTER_WORDS <= CallScratch::COUNTER_PITCH && (CallScratch::PASS_COUNTERS + HBM_STATE_WORDS) % 2 == 0, "counter sets");
   ok = ok && dev_alloc(s->d_counter_sets, 2 * CallScratch::COUNTER_PITCH, "task counters + second-pass state", true); // (two sets: gtx_ctx.hpp)
   s->has_big = !c.params.no_second_pass;
   s->has_wide = s->has_big && c.has_wide_sites;
@@ -1529,18 +1525,18 @@ static std::unique_ptr<CallScratch> scratch_new(gtx_ctx & c)
     ok = ok && dev_alloc(s->d_big_ws, static_cast<size_t>(s->big_blocks) * sizeof(big::AlignWorkspace), "second-pass workspaces");
     if (ok && c.has_wide_sites)
     {
-      ok = ok && dev_alloc(s->d_wide_tasks, CallScratch::WIDE_TASK_CAP, "wide-site pass queue");
+      ok = ok && dev_alloc(s->d_wide_tasks, WIDE_TASK_CAP, "wide-site pass queue");
       ok = ok && dev_alloc(s->d_wide_ws, static_cast<size_t>(CallScratch::WIDE_BLOCKS) * sizeof(wide::AlignWorkspace), "wide-site pass workspaces");
     }
     // the exact pass: two queues (what did not fit the tables above; what did not fit a part of the slab) and the slab
-    ok = ok && dev_alloc(s->d_exact_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "exact pass queues");
+    ok = ok && dev_alloc(s->d_exact_tasks, EXACT_LAUNCHES * static_cast<size_t>(EXACT_TASK_CAP), "exact pass queues");
     if (ok && c.params.max_read_len > GTX_MAX_READ)
     {
       // the long reads' passes: tier 1's workspaces (four workgroups per CU), tier 2's queues and the state words of both
       s->long_blocks = static_cast<uint32_t>(c.n_cu > 0 ? c.n_cu : 256) * 4u;
       ok = ok && dev_alloc(s->d_long_ws, static_cast<size_t>(s->long_blocks) * long_workspace_bytes(), "long-read pass workspaces");
-      ok = ok && dev_alloc(s->d_long_tasks, 3 * static_cast<size_t>(CallScratch::EXACT_TASK_CAP), "long-read exact pass queues");
-      ok = ok && dev_alloc(s->d_long_state, 8 + 32, "long-read pass state", true);
+      ok = ok && dev_alloc(s->d_long_tasks, EXACT_LAUNCHES * static_cast<size_t>(EXACT_TASK_CAP), "long-read exact pass queues");
+      ok = ok && dev_alloc(s->d_long_state, LONG_STATE_WORDS, "long-read pass state", true);
     }
     ok = ok && dev_alloc(s->d_score_state, 8, "second-pass score state", true); // (two sets of four words; [2]: the work queue's count)
     ok = ok && dev_alloc(s->d_score_queue, gtx_ctx::SCORE_QUEUE_CAP, "second-pass score queue");
@@ -2358,7 +2354,7 @@ static int align_hbm(AlignCall & a)
   h.exact_slab = nullptr;
   h.exact_slab_bytes = c->exact_slab_bytes;
   h.exact_cand_cap = c->exact_cand_cap;
-  h.exact_part_cand_cap = std::min<uint32_t>(c->exact_cand_cap, CallScratch::EXACT_PART_CANDIDATES);
+  h.exact_part_cand_cap = std::min<uint32_t>(c->exact_cand_cap, EXACT_PART_CANDIDATES);
   h.exact_parts = c->exact_parts;
   h.exact_fixed_parts = c->exact_fixed_parts;
   h.wide_sites = c->has_wide_sites;
@@ -2391,7 +2387,7 @@ static int align_hbm(AlignCall & a)
     // the long reads (gtx_params::max_read_len > GTX_MAX_READ): tier 1 over the batch, tier 2 with the same slab, behind the above
     if (!what && s->d_long_state.get())
     {
-      if (!hip_ok(hipMemsetAsync(s->d_long_state.get(), 0, (8 + 32) * sizeof(uint32_t), a.sq), "long-read pass state"))
+      if (!hip_ok(hipMemsetAsync(s->d_long_state.get(), 0, LONG_STATE_WORDS * sizeof(uint32_t), a.sq), "long-read pass state"))
         return GTX_ERR_HIP;
       what = launch_long_passes(h, long_args(a), a.sq);
     }
@@ -2747,7 +2743,7 @@ static int kernel_times(gtx_ctx * c, float * ms, uint32_t * tasks)
   uint32_t const queued2 = cnt[2], queued1 = cnt[3], handed = cnt[4];
   uint32_t const direct = cnt[5] - std::min(cnt[5], cnt[4]); // forward tasks of the general pass that did not come through pass 1
   // forward tasks only: reverse-orientation tasks all go to the general pass
-  uint32_t const hbm = std::min<uint32_t>(big[0], s->big_task_cap);
+  uint32_t const hbm = std::min<uint32_t>(big[Q_QUEUED], s->big_task_cap);
   bool const hinted = ms[0] > 0.0f;
   tasks[0] = hinted ? s->timed_reads - queued1 - direct : 0; // (direct: forward tasks the position-hinted pass sent straight to the general pass)
   tasks[1] = hinted ? queued1 - handed : s->timed_reads - std::min(queued2, s->timed_reads);
@@ -3216,7 +3212,7 @@ extern "C" int gtx_ctx_big_records(gtx_ctx * c, const uint32_t ** d_words, uint6
     if (tasks && s && s->d_big_state)
     {
       uint32_t queued = 0;
-      if (!hip_ok(hipMemcpy(&queued, s->d_big_state, sizeof(queued), hipMemcpyDeviceToHost), "second-pass state"))
+      if (!hip_ok(hipMemcpy(&queued, s->d_big_state + Q_QUEUED, sizeof(queued), hipMemcpyDeviceToHost), "second-pass state"))
         return GTX_ERR_HIP;
       *tasks = std::min<uint32_t>(queued, s->big_task_cap);
     }
@@ -3240,13 +3236,10 @@ extern "C" int gtx_ctx_exact_pass_tasks(gtx_ctx * c, uint64_t * out)
     return GTX_OK;
   if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
     return GTX_ERR_HIP;
-  uint32_t st[32]; // 8 words per launch (small parts, large parts, whole slab), then what the last handed on (nothing takes it: the count is what is left)
+  uint32_t st[EXACT_STATE_WORDS];
   if (!hip_ok(hipDeviceSynchronize(), "exact-pass state") || !hip_ok(hipMemcpy(st, s->d_exact_state, sizeof(st), hipMemcpyDeviceToHost), "exact-pass state"))
     return GTX_ERR_HIP;
-  out[0] = st[0];
-  out[1] = st[8];
-  out[2] = st[16];
-  out[3] = st[24] + st[3] + st[11] + st[19]; // (+ tasks a full queue dropped)
+  exact_pass_counts(st, out);
   return GTX_OK;
 }
 
@@ -3267,15 +3260,11 @@ extern "C" int gtx_ctx_long_pass_tasks(gtx_ctx * c, uint64_t * out)
     return GTX_OK;
   if (!hip_ok(hipSetDevice(c->device), "hipSetDevice"))
     return GTX_ERR_HIP;
-  uint32_t st[8 + 32]; // tier 1's 8 words, then tier 2's 8 per launch and what the last launch handed on (as d_exact_state)
+  uint32_t st[LONG_STATE_WORDS];
   if (!hip_ok(hipDeviceSynchronize(), "long-read pass state") || !hip_ok(hipMemcpy(st, s->d_long_state.get(), sizeof(st), hipMemcpyDeviceToHost), "long-read pass state"))
     return GTX_ERR_HIP;
-  uint32_t const * x = st + 8;
-  out[0] = st[1];
-  out[1] = x[0];
-  out[2] = x[8];
-  out[3] = x[16];
-  out[4] = x[24] + x[3] + x[11] + x[19]; // (+ tasks a full queue dropped)
+  out[0] = st[LONG_TASKS];
+  exact_pass_counts(st + LONG_STATE_EXACT, out + 1);
   return GTX_OK;
 }
 

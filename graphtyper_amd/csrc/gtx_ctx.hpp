@@ -8,6 +8,7 @@
 
 #include "gtx_devmem.hpp"
 #include "gtx_flat.hpp"
+#include "gtx_pass_queue.hpp"
 
 namespace gtx
 {
@@ -36,7 +37,7 @@ struct CallScratch
   // launch on its last stream, for the call after it -- the reset used to be a hipMemsetAsync in FRONT of the position-hinted pass
   // on the caller's stream: a fill kernel and the gaps around it, 25 us of an idle chip per step of 0.72 ms.  d_counters and
   // the pointers into the set (d_big_state, d_wide_state, d_exact_state, d_span) name the set of the last call.
-  static constexpr uint32_t COUNTER_WORDS = 8 + 48 + 4, COUNTER_PITCH = 64; // (the pass counters; state of the HBM-table, wide-site, exact pass: 8 + 8 + 32 words; span: 2 x 64 bits)
+  static constexpr uint32_t PASS_COUNTERS = 8, COUNTER_WORDS = PASS_COUNTERS + HBM_STATE_WORDS + 4, COUNTER_PITCH = 64; // (the pass counters; the queue states of the HBM-table, wide-site and exact pass: gtx_pass_queue.hpp; span: 2 x 64 bits)
   DevPtr<uint32_t> d_counter_sets;     // [2][COUNTER_PITCH]
   uint32_t counter_set = 0;            // the set of the last call
   bool spare_set_clean = true;         // the other one is zero (false after a call that failed on its way)
@@ -60,24 +61,20 @@ struct CallScratch
   // HBM-table pass (reads that overflowed the LDS-sized tables)
   DevPtr<uint32_t> d_big_tasks;
   uint32_t big_task_cap = 0;
-  uint32_t * d_big_state = nullptr; // inside d_counter_sets, like the two states below: [0] tasks queued, [1] claim cursor, [3] tasks dropped (list full)
+  uint32_t * d_big_state = nullptr; // inside d_counter_sets, like the two states below: a queue's state words (gtx_pass_queue.hpp)
   DevPtr<> d_big_ws;
   uint32_t big_blocks = 0;   // workspaces d_big_ws holds (grown to gtx_ctx::big_blocks by the first large batch)
   // wide-site pass (graphs with a site of more than 64 alleles only): tasks that met an allele number >= 64
   DevPtr<uint32_t> d_wide_tasks;
   uint32_t * d_wide_state = nullptr; // inside d_big_state's allocation (same layout)
   DevPtr<> d_wide_ws;
-  static constexpr uint32_t WIDE_TASK_CAP = 1u << 20, WIDE_BLOCKS = 64;
+  static constexpr uint32_t WIDE_BLOCKS = 64;
   // exact pass (align_core.hpp: namespace exact): tasks that exceeded the tables of the passes above; tables cut out of a slab
   // at run time -- gtx_ctx::exact_parts workgroups with a part of it each, then one workgroup with all of it
   DevPtr<uint32_t> d_exact_tasks;     // three queues of EXACT_TASK_CAP (small parts, large parts, the whole slab)
-  uint32_t * d_exact_state = nullptr; // inside d_big_state's allocation: 8 words per launch (same layout) + 8 for what is left
-  static constexpr uint32_t EXACT_TASK_CAP = 1u << 20;
-  static constexpr uint32_t EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64; // the launch between the small parts and the whole slab
-  static constexpr uint32_t EXACT_PART_SITES = 24;       // variant sites a path has room for while a task has a small part of the slab
-  static constexpr uint32_t EXACT_PART_CANDIDATES = 8256; // ... and walk candidates (128 live sequences x 64 alleles + a round's slack)
+  uint32_t * d_exact_state = nullptr; // inside d_big_state's allocation: EXACT_STATE_WORDS
   // the long reads' passes (gtx_params::max_read_len > GTX_MAX_READ only; gtx_hbm_passes.hpp: LongPassArgs)
-  DevPtr<uint32_t> d_long_state;     // 8 + 32 words, zeroed by every call: tier 1's read cursor and task count, tier 2's queue states
+  DevPtr<uint32_t> d_long_state;     // LONG_STATE_WORDS, zeroed by every call: tier 1's read cursor and task count, tier 2's queue states
   DevPtr<uint32_t> d_long_tasks;     // tier 2's three queues of EXACT_TASK_CAP
   DevPtr<> d_long_ws;                // long_blocks x longr::AlignWorkspace
   uint32_t long_blocks = 0;

@@ -30,8 +30,8 @@ struct HbmPassArgs
   uint32_t * wide_state;
   void * wide_ws; // CallScratch::WIDE_BLOCKS x wide::AlignWorkspace
   // exact pass
-  uint32_t * exact_tasks; // three queues of CallScratch::EXACT_TASK_CAP
-  uint32_t * exact_state; // 4 x 8 words
+  uint32_t * exact_tasks; // EXACT_LAUNCHES queues of EXACT_TASK_CAP (gtx_pass_queue.hpp)
+  uint32_t * exact_state; // EXACT_STATE_WORDS
   uint8_t * exact_slab;
   uint64_t exact_slab_bytes;
   uint32_t exact_cand_cap;      // walk candidates of a task that has the whole slab (the proven bound)
@@ -67,8 +67,8 @@ struct LongPassArgs
   bool force_both;
   uint32_t blocks;  // workgroups (= workspaces) of tier 1
   void * ws;        // blocks x longr::AlignWorkspace
-  uint32_t * tasks; // tier 2's three queues of CallScratch::EXACT_TASK_CAP
-  uint32_t * state; // 8 words (tier 1: [0] the read cursor, [1] its tasks), then tier 2's 4 x 8 (as HbmPassArgs::exact_state), zeroed
+  uint32_t * tasks; // tier 2's EXACT_LAUNCHES queues of EXACT_TASK_CAP
+  uint32_t * state; // LONG_STATE_WORDS (tier 1: the read cursor and its tasks, then tier 2's words, as HbmPassArgs::exact_state), zeroed
 };
 char const * launch_long_passes(HbmPassArgs const & a, LongPassArgs const & l, hipStream_t stream);
 // the side bytes (and variant masks) of the long reads from their final records, behind the position-hinted pass' own

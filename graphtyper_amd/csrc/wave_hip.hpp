@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "gtx_pass_queue.hpp"
+
 namespace gtx
 {
 struct WaveHip
@@ -144,6 +146,17 @@ static __device__ inline unsigned long long wave_claim64(unsigned long long * co
   if ((threadIdx.x & 63u) == 0)
     v = atomicAdd(counter, n);
   return WaveHip::uni(static_cast<uint64_t>(v));
+}
+
+// The calling lane (a wavefront's leader) hands a task on to the queue of the pass behind (gtx_pass_queue.hpp): a slot of
+// `tasks` while there is one, else a count in the queue's state words -- gtx_ctx_exact_pass_tasks reports what was dropped.
+static __device__ inline void queue_push(uint32_t * tasks, uint32_t cap, uint32_t * state, uint32_t task)
+{
+  uint32_t const slot = atomicAdd(state + Q_QUEUED, 1u);
+  if (slot < cap)
+    tasks[slot] = task;
+  else
+    atomicAdd(state + Q_DROPPED, 1u);
 }
 
 } // namespace gtx

@@ -179,7 +179,7 @@ typedef struct gtx_label
  * that takes them straight from the batch, then an exact pass for what it refuses), and those reads get the records
  * gtx_align_batch gives any read -- never compact ones (gtx_align_batch_planes_compact).  Reads longer than max_read_len
  * keep GTX_ST_RECORD_OVERFLOW.  The first pass takes any number of long reads; its hand-over to the exact pass holds 1 Mi
- * tasks per batch (CallScratch::EXACT_TASK_CAP, as for short reads): a batch with more long tasks than that which exceed the
+ * tasks per batch (EXACT_TASK_CAP in gtx_pass_queue.hpp, as for short reads): a batch with more long tasks than that which exceed the
  * first pass' tables leaves the rest with a table-overflow status (counted in gtx_ctx_long_pass_tasks' out[4]).  gtx_pipeline_run
  * takes every read its context aligns (GTX_MAX_READ, or max_read_len), and gtx_regions_run every read of a job whose plane rows
  * hold it. */

@@ -14,6 +14,7 @@
 
 #include "../../graphtyper_amd/csrc/gtx_flat.hpp"
 #include "../../graphtyper_amd/csrc/gtx_switches.hpp"
+#include "../../graphtyper_amd/csrc/gtx_pass_queue.hpp"
 #include "../../graphtyper_amd/csrc/align_core.hpp"
 #include "../../graphtyper_amd/csrc/score_core.hpp"
 #include "../../graphtyper_amd/csrc/score_replay.hpp"
@@ -50,6 +51,15 @@ struct Emu
   gtx::HostIndex index;
   std::vector<uint32_t> arena; // big-record arena (see gtx_align_batch)
   uint64_t arena_used = 0;
+  // the arena claim of a task behind the general pass (align_core.inl: align_one_arena) -- here the cursor stays where it is
+  // when the record does not fit
+  uint64_t arena_claim(uint32_t n)
+  {
+    uint64_t const off = arena_used;
+    if (off + n <= arena.size())
+      arena_used += n;
+    return off;
+  }
   uint64_t second_pass_tasks = 0; // tasks that reached the last pass (HBM tables)
   uint64_t wide_pass_tasks = 0;   // tasks that went on to the pass with wide allele sets
   uint64_t exact_pass_tasks[4] = {0, 0, 0, 0}; // tasks that reached the exact pass (a small part of the slab / a large part / the whole slab / still refused)
@@ -221,7 +231,6 @@ extern "C"
     for (uint32_t n : e.graph.ref_nvar)
       widest_site = std::max(widest_site, n);
     // the exact pass' slab (gtx_api.hip: exact_slab_mb; here one slab, used by one task at a time)
-    constexpr uint32_t EXACT_PART_SITES = 24, EXACT_PART_CANDIDATES = 8256, EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64; // (gtx_ctx.hpp: CallScratch)
     uint64_t const mb_env = sw::exact_pass_mb();
     std::vector<uint8_t> & exact_slab = e.exact_slab;
     if (exact_slab.empty())
@@ -232,42 +241,7 @@ extern "C"
     if (fixed_parts)
       exact_parts = parts_env;
     e.exact_pass_tasks[0] = e.exact_pass_tasks[1] = e.exact_pass_tasks[2] = e.exact_pass_tasks[3] = 0;
-    // one task through an HBM-table pass (the body of GTX_HBM_PASS_KERNEL in gtx_api.hip); returns the pass' status
-    auto hbm_pass = [&](auto &, auto && align, auto && size_of, auto && write_body, uint32_t * rec, uint32_t len) -> uint32_t
-    {
-      uint32_t np = 0, longest = 0, ext = 0;
-      uint32_t const raw = align(np, longest);
-      uint32_t status = raw & ~GTX_ST_WIDE_ALLELE;
-      uint32_t * body = rec + 2;
-      uint64_t off = 0;
-      if (status)
-        np = 0;
-      else
-      {
-        uint32_t const size = size_of(np);
-        if (size > rec_words)
-        {
-          off = e.arena_used;
-          if (off + (size - 2) > e.arena.size())
-          {
-            status = GTX_ST_RECORD_OVERFLOW;
-            np = 0;
-          }
-          else
-          {
-            e.arena_used += size - 2;
-            body = e.arena.data() + off;
-            ext = GTX_ST_EXTERNAL;
-          }
-        }
-      }
-      uint32_t const has_var = write_body(np, body);
-      rec[0] = np | ((status | ext) << 16);
-      rec[1] = (np == 0 ? 0 : longest) | (len << 16) | (np == 0 ? 0u : has_var);
-      if (ext)
-        rec[2] = static_cast<uint32_t>(off);
-      return raw;
-    };
+    auto claim = [&](uint32_t n) { return e.arena_claim(n); };
     // passes 2 and 3 for one task
     auto general = [&](uint32_t t)
     {
@@ -288,11 +262,8 @@ extern "C"
       big_ws->pp_start = big_keys.data(); // (the kernel points them at LDS)
       big_ws->pp_end = big_keys.data() + big::AlignCfg::MAXPP;
       big_ws->bits_pp = big_bits.data();
-      uint32_t const bst = hbm_pass(
-        *big_ws, [&](uint32_t & np, uint32_t & longest)
-        { return big::align_paths<WaveEmu>(g, ix, *big_ws, seq + static_cast<uint64_t>(read) * seq_stride, len, orient == 1, np, longest); },
-        [&](uint32_t np) { return big::record_size<WaveEmu>(big::Here{}, *big_ws, np); },
-        [&](uint32_t np, uint32_t * body) { return big::write_record_body<WaveEmu>(big::Here{}, *big_ws, np, body); }, rec, len);
+      uint8_t const * row = seq + static_cast<uint64_t>(read) * seq_stride;
+      uint32_t const bst = big::align_one_arena<WaveEmu>(g, ix, *big_ws, row, len, orient == 1, rec, rec_words, e.arena.data(), e.arena.size(), claim);
       uint32_t last = bst;
       if (bst && has_wide_sites)
       {
@@ -301,42 +272,28 @@ extern "C"
         wide_ws->pp_start = wide_keys.data();
         wide_ws->pp_end = wide_keys.data() + wide::AlignCfg::MAXPP;
         wide_ws->bits_pp = wide_bits.data();
-        last = hbm_pass(
-          *wide_ws, [&](uint32_t & np, uint32_t & longest)
-          { return wide::align_paths<WaveEmu>(g, ix, *wide_ws, seq + static_cast<uint64_t>(read) * seq_stride, len, orient == 1, np, longest); },
-          [&](uint32_t np) { return wide::record_size<WaveEmu>(wide::Here{}, *wide_ws, np); },
-          [&](uint32_t np, uint32_t * body) { return wide::write_record_body<WaveEmu>(wide::Here{}, *wide_ws, np, body); }, rec, len);
+        last = wide::align_one_arena<WaveEmu>(g, ix, *wide_ws, row, len, orient == 1, rec, rec_words, e.arena.data(), e.arena.size(), claim);
       }
-      // the exact pass (gtx_align_exact_kernel): first with a part of the slab, then with all of it
+      // the exact pass (gtx_align_exact_kernel): first with a small part of the slab, then a large one, then all of it
       constexpr uint32_t TABLES = GTX_ST_LABEL_OVERFLOW | GTX_ST_PATH_OVERFLOW | GTX_ST_DFS_OVERFLOW;
-      for (uint32_t level = 0; level < 3 && (last & TABLES); ++level)
+      uint32_t const cand_cap = exact::exact_cand_cap(widest_site);
+      for (uint32_t level = 0; level < EXACT_LAUNCHES && (last & TABLES); ++level)
       {
         ++e.exact_pass_tasks[level];
         uint64_t const bytes = level == 0 ? ((exact_slab.size() / exact_parts) & ~255ull) : (level == 1 && !fixed_parts) ? ((exact_slab.size() / EXACT_LARGE_PARTS) & ~255ull) : exact_slab.size();
         uint32_t const cap_v = level == 0 ? EXACT_PART_SITES : level == 1 ? EXACT_LARGE_SITES : exact::AlignCfg::MAXV;
         std::memset(exact_slab.data(), fill, 65536);
+        auto with_slab = [&](auto inst) // (a part that cannot hold one path: the task goes on as it came)
+        {
+          using I = decltype(inst);
+          auto * xws = reinterpret_cast<typename I::Workspace *>(exact_slab.data());
+          if (I::template setup<WaveEmu>(xws, bytes, level == 0 ? std::min(cand_cap, EXACT_PART_CANDIDATES) : cand_cap, cap_v))
+            last = I::template task<WaveEmu>(g, ix, *xws, row, len, orient == 1, rec, rec_words, e.arena.data(), e.arena.size(), claim);
+        };
         if (has_wide_sites)
-        {
-          auto * xws = reinterpret_cast<exactw::AlignWorkspace *>(exact_slab.data());
-          if (!exactw::exact_setup<WaveEmu>(xws, bytes, level == 0 ? std::min(exactw::exact_cand_cap(widest_site), EXACT_PART_CANDIDATES) : exactw::exact_cand_cap(widest_site), cap_v))
-            continue;
-          last = hbm_pass(
-            *xws, [&](uint32_t & np, uint32_t & longest)
-            { return exactw::align_paths<WaveEmu>(g, ix, *xws, seq + static_cast<uint64_t>(read) * seq_stride, len, orient == 1, np, longest); },
-            [&](uint32_t np) { return exactw::record_size<WaveEmu>(exactw::Here{}, *xws, np); },
-            [&](uint32_t np, uint32_t * body) { return exactw::write_record_body<WaveEmu>(exactw::Here{}, *xws, np, body); }, rec, len);
-        }
+          with_slab(exactw::Instance{});
         else
-        {
-          auto * xws = reinterpret_cast<exact::AlignWorkspace *>(exact_slab.data());
-          if (!exact::exact_setup<WaveEmu>(xws, bytes, level == 0 ? std::min(exact::exact_cand_cap(widest_site), EXACT_PART_CANDIDATES) : exact::exact_cand_cap(widest_site), cap_v))
-            continue;
-          last = hbm_pass(
-            *xws, [&](uint32_t & np, uint32_t & longest)
-            { return exact::align_paths<WaveEmu>(g, ix, *xws, seq + static_cast<uint64_t>(read) * seq_stride, len, orient == 1, np, longest); },
-            [&](uint32_t np) { return exact::record_size<WaveEmu>(exact::Here{}, *xws, np); },
-            [&](uint32_t np, uint32_t * body) { return exact::write_record_body<WaveEmu>(exact::Here{}, *xws, np, body); }, rec, len);
-        }
+          with_slab(exact::Instance{});
       }
       if (last & TABLES)
         ++e.exact_pass_tasks[3];

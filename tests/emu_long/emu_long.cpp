@@ -36,79 +36,37 @@ extern "C"
       has_wide_sites = has_wide_sites || n > 64;
       widest_site = std::max(widest_site, n);
     }
-    // (the slab emu_align made, cut as there: CallScratch's constants)
-    constexpr uint32_t EXACT_PART_SITES = 24, EXACT_PART_CANDIDATES = 8256, EXACT_LARGE_PARTS = 32, EXACT_LARGE_SITES = 64;
+    // (the slab emu_align made, cut as there)
     std::vector<uint8_t> & slab = e.exact_slab;
     uint64_t const exact_parts = std::min<uint64_t>(256u, std::max<uint64_t>(1u, (slab.size() >> 20) / (has_wide_sites ? 32u : 2u)));
     auto ws = std::make_unique<longr::AlignWorkspace>();
     std::vector<uint32_t> keys(2 * longr::AlignCfg::MAXPP, 0xABABABABu);
     std::vector<uint64_t> bits(longr::AlignCfg::MAXPP / 64 + 1, 0xABABABABABABABABull);
-    // one task through a pass: the body of GTX_HBM_PASS_BODY (gtx_hbm_passes.hip); returns the pass' raw status
-    auto pass = [&](auto && align, auto && size_of, auto && write_body, uint32_t * rec, uint32_t len) -> uint32_t
-    {
-      uint32_t np = 0, longest = 0, ext = 0;
-      uint32_t const raw = align(np, longest);
-      uint32_t status = raw & ~GTX_ST_WIDE_ALLELE;
-      uint32_t * body = rec + 2;
-      uint64_t off = 0;
-      if (status)
-        np = 0;
-      else
-      {
-        uint32_t const size = size_of(np);
-        if (size > rec_words)
-        {
-          off = e.arena_used;
-          if (off + (size - 2) > e.arena.size())
-          {
-            status = GTX_ST_RECORD_OVERFLOW;
-            np = 0;
-          }
-          else
-          {
-            e.arena_used += size - 2;
-            body = e.arena.data() + off;
-            ext = GTX_ST_EXTERNAL;
-          }
-        }
-      }
-      uint32_t const has_var = write_body(np, body);
-      rec[0] = np | ((status | ext) << 16);
-      rec[1] = (np == 0 ? 0 : longest) | (len << 16) | (np == 0 ? 0u : has_var);
-      if (ext)
-        rec[2] = static_cast<uint32_t>(off);
-      return raw;
-    };
+    auto claim = [&](uint32_t n) { return e.arena_claim(n); };
     // tier 2, the exact pass: a small part of the slab, a large part, all of it
     auto tier2 = [&](uint32_t read, uint32_t orient, uint32_t * rec, uint32_t len)
     {
       constexpr uint32_t TABLES = GTX_ST_LABEL_OVERFLOW | GTX_ST_PATH_OVERFLOW | GTX_ST_DFS_OVERFLOW;
       uint32_t last = TABLES;
       uint8_t const * row = seq + static_cast<uint64_t>(read) * seq_stride;
-      for (uint32_t level = 0; level < 3 && (last & TABLES); ++level)
+      uint32_t const cand_cap = exactl::exact_cand_cap(widest_site);
+      for (uint32_t level = 0; level < EXACT_LAUNCHES && (last & TABLES); ++level)
       {
         ++tasks[1 + level];
         uint64_t const bytes = level == 0 ? ((slab.size() / exact_parts) & ~255ull) : level == 1 ? ((slab.size() / EXACT_LARGE_PARTS) & ~255ull) : slab.size();
         uint32_t const cap_v = level == 0 ? EXACT_PART_SITES : level == 1 ? EXACT_LARGE_SITES : has_wide_sites ? GTX_MAX_READ : GTX_MAX_READ_LONG;
         std::memset(slab.data(), fill, 65536);
+        auto with_slab = [&](auto inst) // (a part that cannot hold one path: the task goes on as it came)
+        {
+          using I = decltype(inst);
+          auto * xws = reinterpret_cast<typename I::Workspace *>(slab.data());
+          if (I::template setup<WaveEmu>(xws, bytes, level == 0 ? std::min(cand_cap, EXACT_PART_CANDIDATES) : cand_cap, cap_v))
+            last = I::template task<WaveEmu>(g, ix, *xws, row, len, orient == 1, rec, rec_words, e.arena.data(), e.arena.size(), claim);
+        };
         if (has_wide_sites)
-        {
-          auto * xws = reinterpret_cast<exactlw::AlignWorkspace *>(slab.data());
-          if (!exactlw::exact_setup<WaveEmu>(xws, bytes, level == 0 ? std::min(exactlw::exact_cand_cap(widest_site), EXACT_PART_CANDIDATES) : exactlw::exact_cand_cap(widest_site), cap_v))
-            continue;
-          last = pass([&](uint32_t & np, uint32_t & longest) { return exactlw::align_paths<WaveEmu>(g, ix, *xws, row, len, orient == 1, np, longest); },
-                      [&](uint32_t np) { return exactlw::record_size<WaveEmu>(exactlw::Here{}, *xws, np); },
-                      [&](uint32_t np, uint32_t * body) { return exactlw::write_record_body<WaveEmu>(exactlw::Here{}, *xws, np, body); }, rec, len);
-        }
+          with_slab(exactlw::Instance{});
         else
-        {
-          auto * xws = reinterpret_cast<exactl::AlignWorkspace *>(slab.data());
-          if (!exactl::exact_setup<WaveEmu>(xws, bytes, level == 0 ? std::min(exactl::exact_cand_cap(widest_site), EXACT_PART_CANDIDATES) : exactl::exact_cand_cap(widest_site), cap_v))
-            continue;
-          last = pass([&](uint32_t & np, uint32_t & longest) { return exactl::align_paths<WaveEmu>(g, ix, *xws, row, len, orient == 1, np, longest); },
-                      [&](uint32_t np) { return exactl::record_size<WaveEmu>(exactl::Here{}, *xws, np); },
-                      [&](uint32_t np, uint32_t * body) { return exactl::write_record_body<WaveEmu>(exactl::Here{}, *xws, np, body); }, rec, len);
-        }
+          with_slab(exactl::Instance{});
       }
       if (last & TABLES)
         ++tasks[4];
@@ -123,9 +81,7 @@ extern "C"
       ws->pp_end = keys.data() + longr::AlignCfg::MAXPP;
       ws->bits_pp = bits.data();
       uint8_t const * row = seq + static_cast<uint64_t>(read) * seq_stride;
-      uint32_t const st = pass([&](uint32_t & np, uint32_t & longest) { return longr::align_paths<WaveEmu>(g, ix, *ws, row, len, orient == 1, np, longest); },
-                               [&](uint32_t np) { return longr::record_size<WaveEmu>(longr::Here{}, *ws, np); },
-                               [&](uint32_t np, uint32_t * body) { return longr::write_record_body<WaveEmu>(longr::Here{}, *ws, np, body); }, rec, len);
+      uint32_t const st = longr::align_one_arena<WaveEmu>(g, ix, *ws, row, len, orient == 1, rec, rec_words, e.arena.data(), e.arena.size(), claim);
       if (st)
         tier2(read, orient, rec, len);
     };

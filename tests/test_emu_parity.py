@@ -401,6 +401,40 @@ def test_second_pass(kind):
     second_pass_case(harness.EmuBackend, kind, 500)
 
 
+FULL_ARENA_EXTERNAL = {"snp7": 300, "snp100": 3}  # records of the case below that need the arena (of 600 slots)
+
+
+def full_arena_case(Backend, kind, rec_words=16, read_len=150):
+    """a big-record arena that is full (gtx_params::big_record_words = 8: no body that leaves a slot of 16 words is shorter than
+    15): exactly the slots whose records go to the arena otherwise carry GTX_ST_RECORD_OVERFLOW with no paths, every other
+    slot is word for word what it is with room in the arena.  Returns both record sets and the backend of the second.
+    Backend: a backend class, or anything else that makes one from (graph, **params)."""
+    ref, recs, codes, pos = scenarios.synthetic_case(kind, n_ref=30000, n_reads=300, region_begin=1000, read_len=read_len)
+    g = gtx.graph_from_records(ref, recs, region_begin=1000)
+    seq, lens = harness.pack_ragged(list(codes))
+    meta = harness.read_meta(lens, pos=pos)
+    roomy = Backend(g).align(seq, meta, rec_words=rec_words).reshape(-1, rec_words).copy()
+    b = Backend(g, big_record_words=8)
+    full = b.align(seq, meta, rec_words=rec_words).reshape(-1, rec_words).copy()
+    external = ((roomy[:, 0] >> 16) & gtx.ST_EXTERNAL) != 0
+    status = full[:, 0] >> 16
+    full_arena_case.external = int(external.sum())
+    assert (((roomy[:, 0] >> 16) & gtx.ST_ERROR_MASK) == 0).all()
+    assert (((status & gtx.ST_RECORD_OVERFLOW) != 0) == external).all()
+    assert ((full[external, 0] & 0xFFFF) == 0).all() and ((full[external, 1] & 0xFFFF) == 0).all()
+    assert (full[~external] == roomy[~external]).all()
+    assert ((status[~external] & gtx.ST_ERROR_MASK) == 0).all()
+    return roomy, full, b
+
+
+@pytest.mark.parametrize("kind", ["snp7", "snp100"])
+def test_full_arena(kind):
+    roomy, _, _ = full_arena_case(harness.EmuBackend, kind)
+    assert full_arena_case.external == FULL_ARENA_EXTERNAL[kind]
+    if kind == "snp7":  # (every forward record, no reverse one)
+        assert (((roomy[0::2, 0] >> 16) & gtx.ST_EXTERNAL) != 0).all()
+
+
 def satellite_case(Backend, n_reads, read_len=150, seed=0, exact_pass_mb=0, monkeypatch=None):
     """Low-complexity repeats (a 280-bp homopolymer, two copies of a dinucleotide repeat, a 2 kb array of a 171-bp unit, a
     trinucleotide repeat, SNPs every 50 bp inside them): one k-mer has hundreds of places there and the reference keeps

@@ -11,7 +11,7 @@ import scenarios
 import ctypes as C
 from graphtyper_amd import lib as gtx, synth
 from oracle_lib import Oracle, encode
-from test_emu_parity import check_align, five_kmer_case, cfg3_case, neardup_case, direct_probes_case, n_runs_case, three_n_case, sv_deletion_case, edge_case, express_variants_case, forced_second_pass_case, iupac_case, run_stream, second_pass_case, sv_stream_case, satellite_case, homopolymer_case, dinucleotide_case
+from test_emu_parity import check_align, five_kmer_case, cfg3_case, neardup_case, direct_probes_case, n_runs_case, three_n_case, sv_deletion_case, edge_case, express_variants_case, forced_second_pass_case, iupac_case, run_stream, second_pass_case, full_arena_case, FULL_ARENA_EXTERNAL, sv_stream_case, satellite_case, homopolymer_case, dinucleotide_case
 
 pytestmark = pytest.mark.gpu
 
@@ -106,6 +106,23 @@ def test_cfg3_graph():
 @pytest.mark.parametrize("kind", ["repeat", "snp7"])
 def test_second_pass(kind):
     second_pass_case(harness.GpuBackend, kind, 5000 if kind == "repeat" else 3000)  # (snp7: ~200 connection entries per read)
+
+
+@pytest.mark.parametrize("kind", ["snp7", "snp100"])
+def test_full_arena(kind):
+    """a full big-record arena: the device's slots are the emulation's, word for word, and gtx_records_failed counts the overflowed ones"""
+    emu_roomy, emu_full, _ = full_arena_case(harness.EmuBackend, kind)
+    roomy, full, b = full_arena_case(harness.GpuBackend, kind)
+    assert full_arena_case.external == FULL_ARENA_EXTERNAL[kind]
+    assert (full == emu_full).all()
+    # (with room in the arena an external record's slot keeps its offset there, which depends on the order of the claims)
+    external = ((roomy[:, 0] >> 16) & gtx.ST_EXTERNAL) != 0
+    same = roomy == emu_roomy
+    same[external, 2:] = True
+    assert same.all()
+    failed = C.c_uint64()
+    gtx.check(gtx.lib().gtx_records_failed(b.ctx.h, b.d_rec.data_ptr(), full.shape[1], len(full) // 2, None, C.byref(failed)))
+    assert failed.value == int(external.sum())
 
 
 def test_satellite_repeats_reach_the_exact_pass():

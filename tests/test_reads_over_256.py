@@ -13,7 +13,7 @@ import scenarios
 from graphtyper_amd import lib as gtx
 from graphtyper_amd import synth
 from oracle_lib import Oracle
-from test_emu_parity import check_align, run_stream
+from test_emu_parity import check_align, full_arena_case, run_stream
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ERR_ARG, ERR_UNSUPPORTED = 1, 4
@@ -173,6 +173,12 @@ def test_emu_long_reads_reach_tier2(emu_long_lib):
     check_align(b, o, ragged(codes, seed=2, lo=300, hi=600))
     assert b.tier_tasks[1] > 0, b.tier_tasks
     assert b.tier_tasks[4] == 0
+
+
+def test_emu_long_reads_full_arena(emu_long_lib):
+    """tier 1's use of the arena task: 300-base reads on snp100 in slots of 16 words, with room in the arena and without"""
+    full_arena_case(lambda g, **p: LongEmu(emu_long_lib, g, max_read_len=300, **p), "snp100", read_len=300)
+    assert full_arena_case.external == 4
 
 
 def wide_long_case(n_reads, seed=0, err=0.004):
