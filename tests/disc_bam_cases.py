@@ -2,8 +2,8 @@
 the plain definition of its three outputs, made here in numpy from the record FIELDS and never from the library: the plane rows
 (the layout of gtx_pack_planes), the quality rows, the CIGAR words.  Hand-made record sets, each for one thing that can go wrong
 (FACTS states what a set holds; tests/test_disc_bam_cases.py runs the facts), and judge(name, run): None, or how the outputs of the
-program behind `run` differ -- shared by the emulation (tests/test_disc_bam_emu.py), the device (tests/test_gpu_disc_bam.py) and a
-later mutation audit.  A set is a list of files; a file is its records and the strides it is unpacked with.  The record bytes, the
+program behind `run` differ -- shared by the emulation (tests/test_disc_bam_emu.py), the device (tests/test_gpu_disc_bam.py) and the
+mutation audit (tests/disc_bam_mutants/), which asked for the sets names and far_cigar.  A set is a list of files; a file is its records and the strides it is unpacked with.  The record bytes, the
 stream, the offsets and the gtx_disc_read table are written here too (SAM spec 4.2), so that what gtx_disc_bam_read returns can be
 held to them (tests/test_disc_bam_read.py).  All values are bytes and words; there is no tolerance."""
 import functools
@@ -122,7 +122,28 @@ def _wide():
     return [File(records, plane_stride=96, qual_stride=131), File(records, plane_stride=48, qual_stride=70), File(records[2:], plane_stride=1024, qual_stride=1)]
 
 
-SETS = dict(lengths=_lengths, codes=_codes, shift=_shift, cigars=_cigars, quals=_quals, counts=_counts, wide=_wide)
+NAMES = (127, 128, 129, 200, 255)  # l_read_name: the name's bytes and its NUL
+
+
+def _names():
+    """names whose length does not fit a signed byte, or seven bits; behind them everything at every residue again"""
+    rng = np.random.default_rng(78)
+    records = []
+    for k in range(40):
+        aux = bytes(rng.integers(0, 256, int(rng.integers(0, 10)), dtype=np.uint8))
+        records.append(rec(29 + k % 5, name="m" * (NAMES[k % 5] - 1), n_cigar=1 + k % 3, aux=aux, seed=100 + k))
+    return [File(records)]
+
+
+FAR = (65535, 0, 1, 65, 65535, 2)
+
+
+def _far_cigar():
+    """CIGAR words at offsets that do not fit 16 bits, and 17"""
+    return [File([rec(10 + k, n_cigar=n, seed=200 + k) for k, n in enumerate(FAR)])]
+
+
+SETS = dict(lengths=_lengths, codes=_codes, shift=_shift, cigars=_cigars, quals=_quals, counts=_counts, wide=_wide, names=_names, far_cigar=_far_cigar)
 
 
 @functools.lru_cache(maxsize=None)
@@ -188,7 +209,31 @@ def facts_wide(fs):
         assert not planes[:, (longest + 31) // 32 * 16:].any() and not qual[:, longest:].any()
 
 
-FACTS = dict(lengths=facts_lengths, codes=facts_codes, shift=facts_shift, cigars=facts_cigars, quals=facts_quals, counts=facts_counts, wide=facts_wide)
+def facts_names(fs):
+    f = fs[0]
+    stream, offsets = f.tables[0], f.tables[1]
+    assert {int(stream[o + 8]) for o in offsets} == set(NAMES) and {len(r["name"]) + 1 for r in f.records} == set(NAMES)
+    assert {len(r["cigar"]) for r in f.records} == {1, 2, 3} and {len(r["codes"]) for r in f.records} == {29, 30, 31, 32, 33}
+    for n in NAMES:  # behind each length of name: the words, the codes, the qualities at every residue
+        behind = [s for s, r in zip(starts(f), f.records) if len(r["name"]) + 1 == n]
+        assert len(behind) == 8
+    for k in range(3):
+        assert {s[k] % 4 for s, r in zip(starts(f), f.records) if len(r["name"]) + 1 >= 128} == set(range(4)) and {s[k] % 4 for s in starts(f)} == set(range(4))
+    assert min(NAMES) == 127 and {n - 256 if n > 127 else n for n in NAMES} != set(NAMES) and {n & 127 for n in NAMES} != set(NAMES)
+
+
+def facts_far_cigar(fs):
+    f = fs[0]
+    assert tuple(len(r["cigar"]) for r in f.records) == FAR
+    assert f.tables[2]["cigar_off"].tolist() == [0, 65535, 65535, 65536, 65601, 131136] and f.tables[3] == 131138 and 131136 > 1 << 17
+    words = f.expected[2]
+    assert len(words) * 4 < 1 << 20 and len({int(w) for w in words[[0, 65535, 65536, 65601, 131136, 131137]]}) == 6  # no two of the words a wrong offset would mix are equal
+    for off in (65536, 65601, 131136):  # what an offset cut to 16 bits would write over, and with other words
+        assert off & 0xFFFF != off and int(words[off]) != int(words[off & 0xFFFF])
+
+
+FACTS = dict(lengths=facts_lengths, codes=facts_codes, shift=facts_shift, cigars=facts_cigars, quals=facts_quals, counts=facts_counts, wide=facts_wide,
+             names=facts_names, far_cigar=facts_far_cigar)
 
 
 # ---- the judge ------------------------------------------------------------------------------------------------------------------------

@@ -11,9 +11,11 @@ The definition knows no segments, no wavefronts and nothing of the library -- it
 Hand-made streams, each with the cut lists it is walked with -- none, every record start, every 777 bytes, every byte of a short
 stream, and the lists the set is made for --, in sets that each stand for one thing that can go wrong (FACTS states what a set holds;
 tests/test_disc_bam_walk_cases.py runs the facts), and judge(name, run): None, or how the results of the program behind `run` differ
--- shared by the emulation (tests/test_disc_bam_walk_emu.py), the device (tests/test_gpu_disc_bam_walk.py) and a later mutation
-audit.  What the cuts decide, the segments whose guess held and those walked again, follows from the definition's chain alone
+-- shared by the emulation (tests/test_disc_bam_walk_emu.py), the device (tests/test_gpu_disc_bam_walk.py) and the mutation audit
+(tests/disc_bam_walk_mutants/), which asked for the sets order, precedence, smallest, odd and turns.  The definition's second witness
+is the host walk itself: tests/test_disc_bam_read.py puts every stream through gtx_disc_bam_read as a file.  What the cuts decide, the segments whose guess held and those walked again, follows from the definition's chain alone
 (segments()).  All values are bytes and words; there is no tolerance."""
+import bisect
 import functools
 import struct
 
@@ -75,9 +77,10 @@ def segments(stream, cuts):
     hit = rewalked = spanned = 0
     bounds = [0] + list(cuts) + [n]
     for b, e in zip(bounds[:-1], bounds[1:]):
-        entry = next((o for o in chain if o >= b), None)
-        if entry is None:
+        at = bisect.bisect_left(chain, b)  # (the chain ascends)
+        if at == len(chain):
             continue
+        entry = chain[at]
         if entry >= e:
             spanned += 1
         elif entry == b:
@@ -235,7 +238,98 @@ def _damage():
     return out
 
 
-SETS = dict(align=_align, straddle=_straddle, span=_span, resync=_resync, decoy=_decoy, counts=_counts, damage=_damage)
+def full(k, l_seq=None, **more):
+    """plain(k) without aux data: its counts fill its block"""
+    return plain(k, l_seq, aux=b"", **more)
+
+
+def one_over(record):
+    """the record with a name one byte longer than its block has room for: counts one byte beyond the block"""
+    return patched(record, l_read_name=record[12] + 1)
+
+
+def past_end(records, i):
+    """the records with the block word of record i one byte past the end of the stream they make"""
+    return records[:i] + [patched(records[i], block=sum(len(r) for r in records[i:]) - 4 + 1)] + records[i + 1:]
+
+
+def _order():
+    """two bad records in one stream: the first in chain order is the one reported, whatever the second is and wherever the cuts fall"""
+    def stream(recs, first, second, label):
+        o = starts(recs)
+        own = [("every record of the stream", o[1:-1]), ("between the two bad records", [o[first + 1]]), ("inside the first bad record", [o[first] + 17])]
+        return Stream(b"".join(recs), own, label)
+    near = past_end([plain(0), plain(1), plain(2), one_over(full(3)), plain(4), plain(5), plain(6)], 5)
+    far = past_end([plain(0), plain(1), plain(2), one_over(full(3))] + [plain(k) for k in range(4, 75)], 73)
+    long_first = [plain(0), plain(1), plain(2, l_seq=65536), plain(3), one_over(full(4)), plain(5)]
+    long_last = [plain(0), plain(1), one_over(full(4)), plain(3), plain(2, l_seq=65536), plain(5)]
+    return [stream(near, 3, 5, "counts beyond the block, two records on a block past the end"), stream(far, 3, 73, "the same pair 70 records apart"),
+            stream(long_first, 2, 4, "65 536 bases in front of counts beyond the block"), stream(long_last, 2, 4, "counts beyond the block in front of 65 536 bases")]
+
+
+def _precedence():
+    """l_seq beyond 65 535 in a record whose counts exceed its block: MALFORMED; in one that holds its bases: LONG_READ"""
+    out = []
+    for l_seq in (65536, 0x7FFFFFFF):
+        recs = [plain(0), plain(1), patched(plain(2), l_seq=l_seq), plain(3), plain(4)]
+        out.append(Stream(b"".join(recs), [("inside the bad record", [starts(recs)[2] + 21])], "l_seq %d in a block of %d bytes" % (l_seq, len(recs[2]) - 4)))
+    recs = [plain(0), plain(1), plain(2, l_seq=65536), plain(3), plain(4)]
+    out.append(Stream(b"".join(recs), [("inside the bad record", [starts(recs)[2] + 21])], "65 536 bases that are there"))
+    return out
+
+
+def least(k):
+    """the smallest sound record: block 32, no name, no cigar word, no base -- 36 bytes, with fields of its own"""
+    pos = -1 if k % 5 == 4 else (0x00F00000 + k * 0x01010101) & 0x7FFFFFFF  # (all four bytes of pos differ from record to record)
+    return struct.pack("<iiiBBHHHiiii", 32, 0, pos, 0, k % 61, 4680, 0, (k * 41 + 1) & 0xFFFF, 0, -1, -1, 0)
+
+
+def _smallest():
+    between = [plain(0), least(1), plain(2), least(3), least(4), plain(5)]
+    out = [Stream(least(0), label="alone"), Stream(b"".join(between), [("every record of the stream", starts(between)[1:-1])], "between ordinary records")]
+    for n in (64, 65):
+        data = b"".join(least(k) for k in range(n))
+        out.append(Stream(data, [("every byte of it", range(1, len(data)))], "a run of %d" % n))
+    return out
+
+
+ODD = (1, 3, 65535)
+
+
+def _odd():
+    """an odd l_seq whose counts fill the block to the byte, and the same one byte over"""
+    out = []
+    for l_seq in ODD:
+        for over in (False, True):
+            bad = full(2, l_seq=l_seq, n_cigar=2)
+            recs = [plain(0), plain(1), one_over(bad) if over else bad, plain(3)]
+            out.append(Stream(b"".join(recs), [("inside it", [starts(recs)[2] + 9])], "l_seq %d, counts %s" % (l_seq, "one byte over" if over else "that fill the block")))
+    return out
+
+
+TURNS = (63, 64, 65, 127, 128)  # the bad record's number: lane 63 of a turn, lanes 0 and 1 of the next, and the same a turn on
+BAD = (TRUNCATED, MALFORMED, LONG_READ)
+
+
+def _turns():
+    """one bad record at the seam of two turns of 64, between two sound records whose counts would show in the totals if they leaked"""
+    out = []
+    for at in TURNS:
+        for status in BAD:
+            recs = [plain(k) for k in range(at - 1)] + [plain(at - 1, l_seq=200, n_cigar=1000)]
+            bad = {TRUNCATED: plain(at), MALFORMED: one_over(full(at, l_seq=400, n_cigar=7)), LONG_READ: plain(at, l_seq=65536, n_cigar=9)}[status]
+            recs += [bad, plain(at + 1, l_seq=300, n_cigar=3000), plain(at + 2), plain(at + 3)]
+            if status == TRUNCATED:
+                recs = past_end(recs, at)
+            o = starts(recs)
+            own = [("every record of the stream", o[1:-1]), ("one record in front of the bad one", [o[at - 1]]), ("one byte into the bad one", [o[at] + 1]),
+                   ("one byte into the first record", [1])]
+            out.append(Stream(b"".join(recs), own, "record %d is bad (%d)" % (at, status)))
+    return out
+
+
+SETS = dict(align=_align, straddle=_straddle, span=_span, resync=_resync, decoy=_decoy, counts=_counts, damage=_damage, order=_order, precedence=_precedence,
+            smallest=_smallest, odd=_odd, turns=_turns)
 
 
 @functools.lru_cache(maxsize=None)
@@ -323,7 +417,85 @@ def facts_damage(ss):
     assert (true.want["status"], true.want["n_reads"]) == (MALFORMED, 4)
 
 
-FACTS = dict(align=facts_align, straddle=facts_straddle, span=facts_span, resync=facts_resync, decoy=facts_decoy, counts=facts_counts, damage=facts_damage)
+def fields(data, o):
+    """-> (block, l_read_name, n_cigar, l_seq, the counts' sum) of the record at o"""
+    block, = struct.unpack_from("<i", data, o)
+    l_read_name, n_cigar, l_seq = data[o + 12], struct.unpack_from("<H", data, o + 16)[0], struct.unpack_from("<i", data, o + 20)[0]
+    return block, l_read_name, n_cigar, l_seq, 32 + l_read_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq
+
+
+def alone(data, o):
+    """the status of the record at o, were it the stream's first"""
+    return define(data[o:])["status"] if define(data[o:])["n_reads"] == 0 else OK
+
+
+def facts_order(ss):
+    near, far, long_first, long_last = ss
+    for s, apart in ((near, 2), (far, 70)):
+        every = own(s, "every record of the stream")
+        first, second = s.want["bad_at"], every[2 + apart]
+        assert (s.want["status"], s.want["n_reads"]) == (MALFORMED, 3) and first == every[2]
+        block, _, _, _, total = fields(s.data, first)
+        assert total == block + 1 and first + 4 + block == every[3]  # one byte beyond a block that is sound: the chain goes on behind it
+        assert second + 4 + fields(s.data, second)[0] == len(s.data) + 1 and alone(s.data, second) == TRUNCATED
+        assert all(alone(s.data, o) == OK for o in every[3:2 + apart])  # sound records between the two
+        assert own(s, "between the two bad records") == [every[3]] and first < own(s, "inside the first bad record")[0] < every[3]
+        assert (s.want["n_cigar"], s.want["max_l_seq"]) == (sum(fields(s.data, o)[2] for o in [0] + every[:2]), max(fields(s.data, o)[3] for o in [0] + every[:2]))
+    assert 2 < 3 + 2 < 64 < 3 + 70  # the pair in one turn of 64 records, and in two
+    for s, (a, b) in ((long_first, (LONG_READ, MALFORMED)), (long_last, (MALFORMED, LONG_READ))):
+        every = own(s, "every record of the stream")
+        assert (s.want["status"], s.want["n_reads"], s.want["bad_at"]) == (a, 2, every[1]) and (alone(s.data, every[1]), alone(s.data, every[3])) == (a, b)
+        assert alone(s.data, every[2]) == OK and own(s, "between the two bad records") == [every[2]]
+
+
+def facts_precedence(ss):
+    for s, l_seq in zip(ss, (65536, 0x7FFFFFFF, 65536)):
+        o = s.want["chain"][2]
+        block, _, _, got, total = fields(s.data, o)
+        assert got == l_seq > 65535 and o == s.want["bad_at"] and s.want["n_reads"] == 2 and o + 4 + block < len(s.data)
+        assert (s.want["status"], total > block) == ((MALFORMED, True) if s is not ss[2] else (LONG_READ, False))
+        assert o < own(s, "inside the bad record")[0] < o + 4 + block
+
+
+def facts_smallest(ss):
+    assert len(least(0)) == 36 and fields(least(0), 0) == (32, 0, 0, 0, 32) and len({least(k)[4:] for k in range(65)}) == 65
+    pos = [struct.unpack_from("<i", least(k), 8)[0] for k in range(65)]
+    assert min(pos) == -1 and max(pos) > 1 << 24 and len({p & 0xFFFF for p in pos}) > 50 and len({p >> 16 for p in pos}) > 50  # pos beyond 16 bits, and none
+    assert [s.want["status"] for s in ss] == [OK] * 4 and [s.want["n_reads"] for s in ss] == [1, 6, 64, 65]
+    assert ss[0].data == least(0) and dict(ss[0].cut_lists)["every byte"] == list(range(1, 36))
+    assert sorted(fields(ss[1].data, o)[0] for o in ss[1].want["chain"][:-1])[:3] == [32, 32, 32] and fields(ss[1].data, 0)[0] > 32 < fields(ss[1].data, ss[1].want["chain"][-2])[0]
+    for s in ss[2:]:
+        assert s.want["chain"] == list(range(0, len(s.data) + 1, 36)) and own(s, "every byte of it") == list(range(1, len(s.data)))
+        assert segments(s.data, own(s, "every byte of it"))[:2] == (s.want["n_reads"], 0)  # every record start is a cut: nothing is walked again
+
+
+def facts_odd(ss):
+    assert len(ss) == 6
+    for k, l_seq in enumerate(ODD):
+        fits, over = ss[2 * k], ss[2 * k + 1]
+        o = fits.want["chain"][2]
+        assert over.want["chain"][-1] == o and (fits.want["status"], fits.want["n_reads"]) == (OK, 4) and (over.want["status"], over.want["n_reads"]) == (MALFORMED, 2)
+        a, b = fields(fits.data, o), fields(over.data, o)
+        assert a[3] == b[3] == l_seq and l_seq % 2 == 1 and a[4] == a[0] == b[0] and b[4] == b[0] + 1  # to the byte, and one byte over: half a byte less and it fits
+        assert 32 + b[1] + 4 * b[2] + l_seq // 2 + l_seq == b[0]
+
+
+def facts_turns(ss):
+    assert [(s.want["bad_at"] == s.want["chain"][-1], s.want["n_reads"], s.want["status"]) for s in ss] == [(True, at, status) for at in TURNS for status in BAD]
+    assert {at % 64 for at in TURNS} == {63, 0, 1} and {at // 64 for at in TURNS} == {0, 1, 2} and max(TURNS) - 1 > 64  # (and a segment walked again over more than a turn)
+    for s in ss:
+        every, at = [0] + own(s, "every record of the stream"), s.want["n_reads"]
+        front, bad, behind = (fields(s.data, every[k]) for k in (at - 1, at, at + 1))
+        assert alone(s.data, every[at - 1]) == alone(s.data, every[at + 1]) == OK and alone(s.data, every[at]) == s.want["status"]
+        assert front[3] == s.want["max_l_seq"] == 200 < behind[3] == 300 and front[2] == 1000 and behind[2] == 3000  # what leaks from behind is larger than all in front
+        assert s.want["n_cigar"] == 1000 + sum(k % 4 for k in range(at - 1)) and int(s.want["reads"]["cigar_off"][-1]) == s.want["n_cigar"] - 1000
+        assert s.want["status"] == TRUNCATED or (bad[2] > 0 and bad[3] > 200)  # a bad record that is parsed has counts that would show, too
+        assert own(s, "one record in front of the bad one") == [every[at - 1]] and own(s, "one byte into the bad one") == [every[at] + 1]
+        assert len(every) == at + 4 and segments(s.data, own(s, "one byte into the first record")) == (1, 1, 0)  # one walk again of all but the first record
+
+
+FACTS = dict(align=facts_align, straddle=facts_straddle, span=facts_span, resync=facts_resync, decoy=facts_decoy, counts=facts_counts, damage=facts_damage,
+             order=facts_order, precedence=facts_precedence, smallest=facts_smallest, odd=facts_odd, turns=facts_turns)
 
 
 # ---- the judge ------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """gtx_disc_bam_read (include/gtx.h): a BAM file of discovery read whole on the host -- the record stream, the offsets, the gtx_disc_read
 table, the longest read, the CIGAR words' number, the sample -- against the records that were written (tests/disc_bam_cases.py), from
 files with whole records per BGZF member and from files cut into members of 777 bytes, so that records, their fixed bytes and their
-block_size words straddle members.  Then the empty file, an unmapped tail, every damage with its status -- the one gtx_reads_open /
+block_size words straddle members.  Then every stream of the record walk's sets (tests/disc_bam_walk_cases.py), whose definition claims
+to be this walk: the same tables, or the error of the first bad record's class.  Then the empty file, an unmapped tail, every damage with its status -- the one gtx_reads_open /
 gtx_reads_next give for the same file --, the two refusals, and gtx_discover_files' answer without a device.  No device."""
 import struct
 
@@ -10,6 +11,7 @@ import pytest
 
 import bam_writer as bw
 import disc_bam_cases as bc
+import disc_bam_walk_cases as wc
 from graphtyper_amd import lib as gtx
 
 ERR_ARG, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_IO = 1, 2, 4, 5, 7
@@ -128,6 +130,26 @@ def test_a_read_of_65536_bases_and_two_samples_are_refused(tmp_path):
     bc.write_bam(path, [bc.rec(10, seed=1)], header_text="@RG\tID:a\tSM:one\n@RG\tID:b\tSM:two\n")
     got, message = status_of(gtx.disc_bam_read, str(path))
     assert got == ERR_UNSUPPORTED and "sample" in message and str(path) in message
+
+
+@pytest.mark.parametrize("name", sorted(wc.SETS))
+def test_the_walk_sets_definition_is_the_host_walk(tmp_path, name):
+    """the second witness of tests/disc_bam_walk_cases.py: define() claims to be this walk (append_bam_block, parse_bam_core and the bound
+    of 65 535 bases, in that order per record).  Every stream of the set written as a file: a sound one comes back with byte-identical
+    tables, a bad one fails as its class does -- TRUNCATED: GTX_ERR_IO "truncated BAM record"; MALFORMED: GTX_ERR_IO "malformed BAM
+    record"; LONG_READ: GTX_ERR_UNSUPPORTED "more than 65535 bases" --, whatever lies behind the first bad record"""
+    errors = {wc.TRUNCATED: (ERR_IO, "truncated BAM record"), wc.MALFORMED: (ERR_IO, "malformed BAM record"), wc.LONG_READ: (ERR_UNSUPPORTED, "more than 65535 bases")}
+    for k, s in enumerate(wc.streams(name)):
+        path = tmp_path / ("%s%d.bam" % (name, k))
+        bc.write_bam(path, [s.data], block=60000)
+        want = s.want
+        if want["status"] == wc.OK:
+            got = gtx.disc_bam_read(str(path))
+            assert got["stream"].tobytes() == s.data and got["offsets"].tobytes() == want["offsets"].tobytes() and got["reads"].tobytes() == want["reads"].tobytes(), s.label
+            assert got["offsets"].dtype == want["offsets"].dtype and (got["max_l_seq"], got["n_cigar"], len(got["reads"])) == (want["max_l_seq"], want["n_cigar"], want["n_reads"])
+        else:
+            status, message = status_of(gtx.disc_bam_read, str(path))
+            assert status == errors[want["status"]][0] and errors[want["status"]][1] in message, (s.label, want["status"], status, message)
 
 
 def test_null_arguments():

@@ -3,7 +3,8 @@
 gtx_disc_bam_unpack over every record set of tests/disc_bam_cases.py, judged by its judge: every byte of the plane rows, the quality
 rows and the CIGAR words equals the plain definition, outputs preset to 0xA5 between guards that stay untouched.  The library's grid
 gives a wavefront four records wherever there are that many, so the sets of 63 and more records run the loop over a wavefront's
-records.  Then the argument errors, each leaving the outputs as they were.  gtx_discover_files over the end-to-end set of
+records.  Then the argument errors, each leaving the outputs as they were, and rows that begin behind byte 2^32 of their arrays, judged
+on the device.  gtx_discover_files over the end-to-end set of
 tests/disc_variants_cases.py, its three files written as BAM with names of mixed length, aux tags and members of 777 bytes: the words,
 the good flags, the records, the text and the per-file statistics are those of gtx_discover_region over the arrays
 tests/disc_event_cases.py makes of the same reads, and those of the host chain -- with one, three and eight threads, the smallest
@@ -91,6 +92,65 @@ def test_the_unpack_argument_errors(disc):
     assert status(n_reads=0) == 0 and status(n_reads=0, d_stream=None, d_offsets=None, d_reads=None, d_planes=None, d_qual=None, d_cigar=None, n_bytes=0, n_cigar=0) == 0
     assert d.untouched()  # none of them launched anything
     assert status() == 0 and bc.file_differs(f, d.outputs()) is None
+
+
+def test_rows_behind_2_32_bytes(disc):
+    """65 537 records of one base and one CIGAR word at strides of 65 536: the last plane row and the last quality row begin at byte
+    2^32, where `i * stride` made in 32 bits would be 0 again and the record would be written over the first one's rows.  The 8 GB stay
+    on the device and are judged there -- word 0 of the four planes of group 0 and byte 0 of every quality row against the definition
+    (a base of code c is bit 0 of the words b with c's bit b set), every other byte zero, the guards as they were; only the verdicts
+    and the CIGAR words come back.  The emulation cannot hold this (tests/disc_bam_mutants: ad_row_product_32_bits,
+    ad_qual_product_32_bits).  Skipped, with the reason, where the device refuses the 8 GB: the addressing is then held by reading only."""
+    import torch
+    n, stride = 65537, 65536
+    assert (n - 1) * stride == 1 << 32
+    i = np.arange(n, dtype=np.uint64)
+    codes, quals, words = ((i * 7 + 1) % 16).astype(np.uint8), ((i * 13 + 5) % 256).astype(np.uint8), ((i * 2654435761 + 12345) % (1 << 32)).astype(np.uint32)
+    some = [0, 1, 255, n - 2, n - 1]
+    small = bc.File([bc.rec(name="r", codes=[int(codes[k])], qual=[int(quals[k])], cigar=[int(words[k])], pos=100 + k % 7) for k in some], plane_stride=16, qual_stride=4)
+    one = len(bc.record_bytes(small.records[0]))
+    stream = np.tile(np.frombuffer(bc.record_bytes(small.records[0]), np.uint8), n).reshape(n, one).copy()
+    at_cigar, at_seq, at_qual = 4 + 32 + 2, 4 + 32 + 2 + 4, 4 + 32 + 2 + 4 + 1
+    assert one == at_qual + 1
+    stream[:, 8:12] = (100 + i % 7).astype(np.uint32).view(np.uint8).reshape(n, 4)
+    stream[:, at_cigar:at_cigar + 4] = words.view(np.uint8).reshape(n, 4)
+    stream[:, at_seq] = (codes << 4) | 15
+    stream[:, at_qual] = quals
+    assert all(stream[k].tobytes() == bc.record_bytes(r) for k, r in zip(some, small.records))  # the records are the case module's
+    want_rows = np.zeros((n, 16), np.uint8)
+    for b in range(4):
+        want_rows[:, 4 * b] = (codes >> b) & 1
+    assert np.array_equal(want_rows[some], small.expected[0]) and np.array_equal(quals[some], small.expected[1][:, 0])  # ... and so is what they unpack to
+    offsets = (np.arange(n, dtype=np.uint32) * one + 4).astype(np.uint32)
+    reads = np.zeros(n, gtx.DISC_READ)
+    reads["pos"], reads["flag"], reads["mapq"], reads["l_qseq"], reads["n_cigar"], reads["cigar_off"] = 100 + i % 7, 3, 60, 1, 1, np.arange(n)
+    up = lambda a: torch.from_numpy(np.concatenate([np.ascontiguousarray(a).view(np.uint8).reshape(-1), np.zeros(16, np.uint8)])).to("cuda:0")  # noqa: E731
+    planes = qual = None
+    try:
+        try:
+            planes = torch.full((bc.GUARD + n * stride + bc.GUARD,), bc.FILL, dtype=torch.uint8, device="cuda:0")
+            qual = torch.full((bc.GUARD + n * stride + bc.GUARD,), bc.FILL, dtype=torch.uint8, device="cuda:0")
+        except RuntimeError as e:  # (torch.OutOfMemoryError is one)
+            pytest.skip("the device refuses two arrays of 4 GB: %s" % str(e).splitlines()[0])
+        d_stream, d_offsets, d_reads = up(stream), up(offsets), up(reads)
+        cigar = torch.from_numpy(bc.guarded(4 * n)).to("cuda:0")
+        torch.cuda.synchronize()
+        gtx.disc_bam_unpack(disc, d_stream.data_ptr(), stream.size, d_offsets.data_ptr(), d_reads.data_ptr(), n, planes.data_ptr() + bc.GUARD, stride,
+                            qual.data_ptr() + bc.GUARD, stride, cigar.data_ptr() + bc.GUARD, n)
+        torch.cuda.synchronize()
+        def verdicts(out, want):
+            """on the device -> (the guards are as they were, the bytes a record decides are the definition's, every other byte is zero)"""
+            want = torch.from_numpy(want).to("cuda:0")
+            rows = out[bc.GUARD:-bc.GUARD].view(n, stride)
+            return (bool((out[:bc.GUARD] == bc.FILL).all()) and bool((out[-bc.GUARD:] == bc.FILL).all()), bool(torch.equal(rows[:, :want.shape[1]], want)),
+                    int(torch.count_nonzero(rows)) == int(torch.count_nonzero(want)))
+        assert verdicts(planes, want_rows) == (True, True, True)  # (the last row begins at byte 2^32 of the planes)
+        assert verdicts(qual, quals.reshape(n, 1).copy()) == (True, True, True)
+        got = cigar.cpu().numpy()
+        assert (got[:bc.GUARD] == bc.FILL).all() and (got[-bc.GUARD:] == bc.FILL).all() and got[bc.GUARD:-bc.GUARD].tobytes() == words.tobytes()
+    finally:
+        planes = qual = None
+        torch.cuda.empty_cache()
 
 
 # ---- the region from files --------------------------------------------------------------------------------------------------------------

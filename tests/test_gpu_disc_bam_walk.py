@@ -3,7 +3,7 @@
 Every stream of tests/disc_bam_walk_cases.py with every one of its cut lists, judged by its judge: the status and its offset, the
 counts, every byte of the two tables and the segments whose guess held or that were walked again equal the plain definition, the tables
 preset to 0xA5 between guards that stay untouched.  Each list runs twice, for the counts alone and with tables of exactly the count,
-and the two calls say the same.  Then the argument errors and a table that is too small, each leaving the tables as they were, and
+and the two calls say the same.  Then a stream cut into more segments than the launch has wavefronts, the argument errors and a table that is too small, each leaving the tables as they were, and
 the tables of gtx_disc_bam_read for the same records written as a file.  All values are bytes and words; there is no tolerance."""
 import ctypes as C
 
@@ -53,6 +53,21 @@ def walk(disc, data, lists):
 @pytest.mark.parametrize("name", sorted(wc.SETS))
 def test_every_walk_equals_the_definition(disc, name):
     assert wc.judge(name, lambda data, lists: walk(disc, data, lists)) is None
+
+
+def test_more_segments_than_wavefronts(disc):
+    """the launch gives guess and emit a wavefront per segment up to 65 536 segments (16 384 blocks of four), and the sets' longest cut
+    list is below 1 000 cuts: only here do the device's wavefronts stride over the segments (`s += step`), which the emulation alone ran
+    before.  900 records cut at every byte: more than 65 536 segments, of which the 900 that begin with a record do any work"""
+    s = wc.Stream(b"".join(wc.plain(k) for k in range(900)), label="900 records")
+    n = len(s.data)
+    assert n >= 65538 and s.want["status"] == wc.OK and s.want["n_reads"] == 900
+    cuts = list(range(1, n))
+    assert len(cuts) + 1 > 65536 and wc.segments(s.data, cuts)[:2] == (900, 0)
+    cut, whole = walk(disc, s.data, [cuts, []])
+    assert wc.differs(s, cuts, cut) is None and wc.differs(s, [], whole) is None
+    assert all(cut[key] == whole[key] for key in ("status", "n_reads", "n_cigar", "max_l_seq")) and (cut["segments_hit"], whole["segments_hit"]) == (900, 1)
+    assert cut["offsets"].tobytes() == whole["offsets"].tobytes() and cut["reads"].tobytes() == whole["reads"].tobytes()
 
 
 def test_the_argument_errors_and_a_table_too_small(disc):
